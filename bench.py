@@ -23,6 +23,10 @@ Extra objects on the same JSON line:
 ranks with jatsr_amd.dist.shard_range (28 -> 14,14 -> 7,7,7,7 -> 4,4,4,4,3,3,3,3), value = 28*T*steps / max-over-ranks time.
 --dry-run: CPU-only rehearsal of the launcher / rendezvous / timing contract (gloo, a stand-in numpy step) — what the
 world_size-2 CPU test runs; never a measurement.
+--dump-outputs DIR: after the timed steps, rank 0 writes what the timed path returned in its last step as DIR/<name>.npy
+(float32 / float64, at most 64 MB in all).  Inputs are seeded, so two builds run with the same arguments compare output for
+output.  sample: `out` (the sampler's [B, C, T] latents); long: `out` (the crossfaded [1, C, long_T] file); train: `loss`,
+`grad_norm`, `lr` and `params` (a fixed, seeded sample of the flat fp32 weights after the step).
 """
 import argparse
 import ctypes as C
@@ -41,6 +45,37 @@ PEAK_HBM_GBS = 8000.0
 # 2.1 GHz, torch 2.10 CPU, 8 threads).  Carried beside the port's number so that the CPU baseline never flatters the ratio.
 REFERENCE_TORCH_CPU_SURVEY = {"forward_latent_frames_per_s": [1408.0, 1548.0], "cores": 8,
                               "what": "reference JaT_AudioSR_V3 fp32 eval forward, B=2 / B=1, T=512, survey container"}
+DUMP_LIMIT_BYTES = 64 * 10 ** 6     # --dump-outputs: the whole dump stays under 64 MB
+DUMP_SMALL = 4096                   # arrays up to this many elements are always written whole
+DUMP_SEED = 20240917                # fixes which elements a sampled array keeps
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write {name: tensor | ndarray | scalar} as path/<name>.npy; float64 stays float64, everything else is
+    written as float32.  If the set is larger than DUMP_LIMIT_BYTES, every array of more than DUMP_SMALL elements keeps the
+    same share of its flattened elements, at sorted positions drawn from a generator seeded by DUMP_SEED and the array's size
+    (the same positions on every run), and is written 1-D.  Returns {name: (elements written, elements in the array)}."""
+    import numpy as np
+    import torch
+    items = {}
+    for name, a in arrays.items():
+        t = a.detach() if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))
+        items[name] = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32)
+    big = [k for k, t in items.items() if t.numel() > DUMP_SMALL]
+    nbytes = {k: t.numel() * t.element_size() for k, t in items.items()}
+    budget = DUMP_LIMIT_BYTES - 4096 * len(items) - sum(v for k, v in nbytes.items() if k not in big)   # 4096: .npy headers
+    scale = min(1.0, budget / max(sum(nbytes[k] for k in big), 1))
+    os.makedirs(path, exist_ok=True)
+    written = {}
+    for name, t in items.items():
+        n = t.numel()
+        keep = int(n * scale) if name in big else n
+        if keep < n:
+            idx = np.sort(np.random.default_rng([DUMP_SEED, n]).integers(0, n, size=keep))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+        written[name] = (keep, n)
+    return written
 
 
 def launch_ranks(args, argv):
@@ -121,10 +156,12 @@ def dry_run(args):
         dist.barrier()
     t1 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        out = step()
     if world > 1:
         dist.barrier()
     elapsed = max_over_ranks(time.perf_counter() - t1)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"out": np.float64(out)})
     seen = world
     if world > 1:
         t = torch.tensor([1.0])
@@ -171,18 +208,17 @@ def main():
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="weak: B per GPU fixed; strong: one batch of B sharded over the GPUs (dist.shard_range)")
     ap.add_argument("--dry-run", action="store_true", help="CPU/gloo rehearsal of the launcher and timing contract (tests)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (rank 0; <= 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return launch_ranks(args, sys.argv[1:])     # before anything touches a GPU
     if args.dry_run:
         return dry_run(args)
 
-    if args.mode == "train":
-        # the trainer overlaps the gradient exchange (its own stream) with the backward; with ROCm's default of four hardware
-        # queues two streams of one process can land on the same queue and run one after the other (seen with two sampler
-        # graphs on two streams: profiles/r03/two_stream_half_batches.log) — must be set before the HIP runtime starts
-        os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
     import numpy as np
     import torch
 
@@ -280,6 +316,8 @@ def main():
             elapsed = float(tt.item())
         if rank == 0:
             assert out.shape == (1, C_lat, T_long) and bool(torch.isfinite(out).all())
+            if args.dump_outputs:
+                dump_outputs(args.dump_outputs, {"out": out})
             print(json.dumps({
                 "metric": "DiT long-sequence latent-frames/sec (one file, T=%d, 50-step CFG)" % T_long,
                 "value": T_long * args.steps / elapsed, "unit": "latent-frames/s", "n_gpus": world, "steps": args.steps,
@@ -325,6 +363,9 @@ def main():
             elapsed = float(tt.item())
         assert np.isfinite(st["loss"]) and np.isfinite(st["grad_norm"])
         tfl = 3 * recipe.forward_flops(cfg, B, Tt) * args.steps / elapsed / 1e12
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"loss": np.float64(st["loss"]), "grad_norm": np.float64(st["grad_norm"]),
+                                             "lr": np.float64(st["lr"]), "params": trainer.params})
         if rank == 0:
             print(json.dumps({
                 "metric": "DiT training latent-frames/sec (B=28/GPU, C=1024, T=%d)" % Tt,
@@ -356,6 +397,8 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     assert bool(torch.isfinite(out).all()), "sampler produced non-finite values"
+    if rank == 0 and args.dump_outputs:     # before the diagnostics below reuse the model and the sampler
+        dump_outputs(args.dump_outputs, {"out": out})
     total_B = args.B if args.scaling == "strong" else world * B
     frames = total_B * T * args.steps
     value = frames / elapsed

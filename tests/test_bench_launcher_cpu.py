@@ -42,3 +42,35 @@ def test_bench_launcher_other_modes_world2(mode):
     r = _run(["--gpus", "2", "--mode", mode])
     assert r["n_gpus"] == 2 and r["ranks_seen"] == 2 and r["dry_run"] is True and r["config"]["mode"] == mode
     assert r["steps"] == 3 and r["value"] > 0 and ("training" in r["metric"] if mode == "train" else "long-sequence" in r["metric"])
+
+
+def test_bench_dump_outputs_dry_run(tmp_path):
+    """--dump-outputs DIR: rank 0 writes what the last timed step returned as DIR/<name>.npy, the same on every run with the
+    same arguments (the GPU modes write the sampler / trainer outputs through the same function)."""
+    import numpy as np
+    got = []
+    for d in ("a", "b"):
+        r = _run(["--gpus", "2", "--dump-outputs", str(tmp_path / d)])
+        assert r["steps"] == 3 and r["ms_per_step"] > 0
+        assert sorted(os.listdir(tmp_path / d)) == ["out.npy"]
+        got.append(np.load(tmp_path / d / "out.npy"))
+    assert got[0].dtype == np.float64 and np.array_equal(got[0], got[1])
+
+
+def test_dump_outputs_cap_and_seeded_sample(tmp_path):
+    """Above 64 MB in all, large arrays are cut to a fixed, seeded sample of their elements (sorted positions, written 1-D);
+    small arrays and the dtypes (float64 kept, everything else float32) are left as they are."""
+    import numpy as np
+    import bench
+    big = np.arange(10_000_000, dtype=np.float64)                  # 80 MB: its values are its positions
+    small = np.arange(6, dtype=np.int32).reshape(2, 3)
+    out = {}
+    for d in ("a", "b"):
+        w = bench.dump_outputs(str(tmp_path / d), {"big": big, "small": small, "loss": np.float64(0.25)})
+        assert w["small"] == (6, 6) and w["loss"] == (1, 1) and 0 < w["big"][0] < w["big"][1]
+        assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= bench.DUMP_LIMIT_BYTES
+        out[d] = {k: np.load(tmp_path / d / (k + ".npy")) for k in ("big", "small", "loss")}
+    a, b = out["a"], out["b"]
+    assert np.array_equal(a["big"], b["big"]) and a["big"].dtype == np.float64 and a["big"].ndim == 1
+    assert np.all(np.diff(a["big"]) >= 0) and a["big"].min() >= 0 and a["big"].max() < big.size
+    assert a["small"].dtype == np.float32 and np.array_equal(a["small"], small) and a["loss"] == 0.25

@@ -775,7 +775,7 @@ def test_second_trainer_supersedes_the_first_and_batch_cap_is_reported():
         Trainer(m, batch_size=33, frames=meta["T"])
 
 
-def test_skipped_step_advances_the_schedule_counter_not_adamw():
+def test_skipped_step_advances_the_schedule_counter_not_adamw(tmp_path):
     """train_ddp_v3m2.py:634 increments global_step every batch; AdamW's own step (bias correction) only counts updates that
     happened.  A non-finite gradient (scaler skip) must advance the first and not the second, and the checkpoint stores both."""
     z, meta = load_golden("train_micro_T24")
@@ -794,7 +794,7 @@ def test_skipped_step_advances_the_schedule_counter_not_adamw():
     assert tr.step_seed() != seed1                          # a retried batch draws fresh dropout masks
     sd = tr.optimizer_state_dict()
     assert float(sd["state"][0]["step"]) == 1.0
-    ck = tr.save_checkpoint("/tmp/_jat_ck_counters.pt")
+    ck = tr.save_checkpoint(str(tmp_path / "ck.pt"))
     assert ck["global_step"] == 2
 
 
