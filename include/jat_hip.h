@@ -262,6 +262,50 @@ int jat_prof_gemm_site(jat_model* m, int32_t site, int32_t max_launches);
  * synchronises on the recorded events and switches the bracket off. */
 int jat_prof_collect(jat_model* m, double* total_ms, int32_t* launches, double* flops, int32_t* variant);
 
+/* ---- DAC 44.1 kHz decoder: latent [B, 1024, T] -> audio [B, 1, T*512] ------------------------------------ */
+/* The reference decodes with the Descript Audio Codec (infer_test_v3m2.py:97-104, :408-437); the computation is
+ * transformers' DacDecoder.forward (models/dac/modeling_dac.py:407-441).  bf16 MFMA in both operand-dtype builds. */
+typedef struct jat_dac_decoder jat_dac_decoder;
+#define JAT_DAC_BF16X3 0   /* operands split bf16 hi + lo, three MFMA passes, fp32 accumulation (matches fp32) */
+#define JAT_DAC_BF16 1     /* one bf16 pass */
+typedef struct jat_dac_config {
+  int32_t latent_channels;   /* DacConfig.hidden_size: 1024 */
+  int32_t channels;          /* DacConfig.decoder_hidden_size: 1536 (every channels >> i a multiple of 32) */
+  int32_t n_blocks;          /* len(upsampling_ratios), 1..4 */
+  int32_t strides[4];        /* upsampling_ratios: 8, 8, 4, 2 (even) */
+} jat_dac_config;
+/* named: the decoder's folded (plain `weight`) fp32 parameters under transformers' DacDecoder names (modeling_dac.py:
+ * 416-433): conv1.{weight,bias}, block.{i}.snake1.alpha, block.{i}.conv_t1.{weight,bias},
+ * block.{i}.res_unit{1,2,3}.{snake1.alpha,conv1.weight,conv1.bias,snake2.alpha,conv2.weight,conv2.bias}, snake1.alpha,
+ * conv2.{weight,bias}.  Weights are re-laid out per tap / per phase and split into bf16 planes here; device memory for
+ * batches up to max_B x max_T frames is allocated here.  A missing or mis-sized key fails with its name. */
+int jat_dac_decoder_create(const jat_dac_config* cfg, const jat_tensor_ref* named, int32_t n, int32_t max_B,
+                           int32_t max_T, void* stream, jat_dac_decoder** out);
+void jat_dac_decoder_destroy(jat_dac_decoder* d);
+/* device bytes the handle holds (weights + activations for max_B x max_T) */
+int jat_dac_workspace_bytes(const jat_dac_decoder* d, size_t* bytes);
+/* DacDecoder.forward (modeling_dac.py:427-441): z fp32 [B, latent_channels, T] -> audio fp32 [B, 1, T * prod(strides)];
+ * 1 <= B <= max_B, 1 <= T <= max_T, precision JAT_DAC_*. */
+int jat_dac_decode(jat_dac_decoder* d, const float* z, float* audio, int32_t B, int32_t T, int32_t precision, void* stream);
+/* Per-kernel entry points (unit tests).  [host] fp32 torch-layout weight -> [N, taps, Cin] GEMM layout:
+ * kind 0: Conv1d weight [cout, cin, k] (taps = k, N = cout); kind 1: ConvTranspose1d weight [cin, cout, 2 s] with
+ * padding s / 2 (k_or_stride = s; polyphase, taps = 3, N = s * cout). */
+int jat_dac_pack_weight(int32_t kind, const float* w, int32_t cin, int32_t cout, int32_t k_or_stride, float* out);
+/* fp32 -> bf16 planes hi = bf16(x), lo = bf16(x - hi) */
+int jat_k_dac_split(const float* x, uint16_t* hi, uint16_t* lo, int64_t n, void* stream);
+/* One decoder convolution on channels-last operand planes a [B*T, cin] and packed weight planes w [N, taps, cin]:
+ *   taps 7, dil d:  Conv1d k7 padding 3d (modeling_dac.py:180,197) — with alpha: the snake epilogue;
+ *   taps 3, dil 1:  ConvTranspose1d polyphase (modeling_dac.py:244-250), N = s * cch, out rows [B, T*s, cch];
+ *   taps 1 + res:   residual-unit conv2 plus the fp32 residual (modeling_dac.py:198,208; out32 may equal res).
+ * Epilogue: v = acc + bias[n % cch] (+ res); out32 = v if non-null; o_hi/o_lo = planes of snake_alpha(v) if o_hi. */
+int jat_k_dac_conv(const uint16_t* a_hi, const uint16_t* a_lo, const uint16_t* w_hi, const uint16_t* w_lo,
+                   const float* bias, const float* res, float* out32, const float* alpha, uint16_t* o_hi, uint16_t* o_lo,
+                   int32_t B, int32_t T, int32_t cin, int32_t N, int32_t cch, int32_t taps, int32_t dil,
+                   int32_t precision, void* stream);
+/* Tail (modeling_dac.py:436-439): x fp32 [B*T, C] -> tanh(conv_k7(snake(x))) fp32 [B, 1, T]; w [7][C] (tap-major), C <= 96 */
+int jat_k_dac_tail(const float* x, const float* alpha, const float* w, const float* bias, float* out, int32_t B, int32_t T,
+                   int32_t C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,6 +31,11 @@ class JatConfig(C.Structure):
         "num_kv_heads", "bottleneck_dim", "mlp_hidden", "norm_mode")]
 
 
+class JatDacConfig(C.Structure):
+    _fields_ = [("latent_channels", C.c_int32), ("channels", C.c_int32), ("n_blocks", C.c_int32),
+                ("strides", C.c_int32 * 4)]
+
+
 class JatTensorRef(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("numel", C.c_int64)]
 
@@ -84,6 +89,14 @@ SIGNATURES = {
     "jat_trainer_optim": (C.c_int, [_VP, _F32, _F32, _F32, _F32, _F32, _F32, _F32, _I32, _VP, _VP]),
     "jat_prof_gemm_site": (C.c_int, [_VP, _I32, _I32]),
     "jat_prof_collect": (C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(_I32), C.POINTER(C.c_double), C.POINTER(_I32)]),
+    "jat_dac_decoder_create": (C.c_int, [C.c_void_p, C.POINTER(JatTensorRef), _I32, _I32, _I32, _VP, C.POINTER(_VP)]),
+    "jat_dac_decoder_destroy": (None, [_VP]),
+    "jat_dac_workspace_bytes": (C.c_int, [_VP, C.POINTER(_SZ)]),
+    "jat_dac_decode": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _VP]),
+    "jat_dac_pack_weight": (C.c_int, [_I32, _VP, _I32, _I32, _I32, _VP]),
+    "jat_k_dac_split": (C.c_int, [_VP, _VP, _VP, _I64, _VP]),
+    "jat_k_dac_conv": (C.c_int, [_VP] * 10 + [_I32] * 8 + [_VP]),
+    "jat_k_dac_tail": (C.c_int, [_VP] * 5 + [_I32] * 3 + [_VP]),
 }
 
 GRAD_HOOK = C.CFUNCTYPE(None, C.c_int64, C.c_int64, C.c_void_p)   # jat_trainer_set_grad_hook callback

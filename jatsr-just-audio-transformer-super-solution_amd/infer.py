@@ -4,9 +4,10 @@ Same flags (`--checkpoint --val-dir --stats-file --output-dir --steps --cfg-scal
 --input-file`), same chunk plan (16 s chunks = 1378 latent frames, 2 s = 172-frame linear crossfade, :340-404), same
 per-channel normalisation (:381-394).  Differences, all outside the hot path's semantics:
   * equal-length chunks are batched into one captured sampler launch instead of the reference's serial B=1 loop;
-  * the DAC decode + WAV writing of :411-437 is out of scope (the `descript-audio-codec` package and its weights are
-    not available offline): the generated / HR / LR latents are written as a `.pt` file in the
-    reference's latent container format, ready for `dac_codec.decode`;
+  * the generated / HR / LR latents are always written as a `.pt` file in the reference's latent container format;
+    with `--dac-weights PATH` (a DAC 44.1 kHz weight file: there is no download) they are also decoded on the GPU
+    (jatsr_amd.dac, csrc/dac.hip) and written as the reference's three 44.1 kHz WAV files (:408-437);
+    `--dac-precision` picks bf16x3 (default, fp32-accurate) or bf16;
   * `--seed` makes the initial noise reproducible (the reference draws it with torch.randn, :133).
 
     python -m jatsr_amd.infer --checkpoint ckpt.pt --input-file clip.pt --stats-file stats.json --cfg-scale 3.0
@@ -38,6 +39,10 @@ def build_parser():
     p.add_argument("--input-file", type=str, default=None, help="Specific input file; default: first file in val-dir")
     p.add_argument("--layernorm", action="store_true", help="checkpoint is a v3mod2 (LayerNorm, JaT_AudioSR_V2) model")
     p.add_argument("--seed", type=int, default=None, help="seed for the initial noise")
+    p.add_argument("--dac-weights", type=str, default=None,
+                   help="DAC 44.1 kHz weight file (.safetensors/.pt/.bin/.pth); decode to WAV when given")
+    p.add_argument("--dac-precision", type=str, default="bf16x3", choices=["bf16x3", "bf16"],
+                   help="DAC decoder arithmetic: bf16x3 (three-pass split, fp32-accurate) or bf16")
     return p
 
 
@@ -80,7 +85,23 @@ def run(args):
                          metadata={"source": os.path.basename(path), "steps": args.steps, "cfg_scale": args.cfg_scale,
                                    "frames": total, "seconds": dt})
     print(f"generated {gen.shape[-1]} frames in {dt:.2f} s -> {out_path}")
+    if args.dac_weights:
+        decode_to_wav(args, gen, hr, lr, total, stem, suffix, device)
     return out_path
+
+
+def decode_to_wav(args, gen, hr, lr, total, stem, suffix, device):
+    """DAC decode of the generated, HR and LR latents and the three WAV files of infer_test_v3m2.py:408-437."""
+    from .dac import load_dac_codec
+    codec = load_dac_codec(args.dac_weights, device=device, precision=args.dac_precision)
+    outs = [(f"{stem}_generated{suffix}.wav", gen[:1].float())]
+    if hr is not None:
+        outs.append((f"{stem}_hr_gt.wav", hr[None, :, :total].to(device)))
+    outs.append((f"{stem}_lr_input.wav", lr[None, :, :total].to(device)))
+    for name, z in outs:
+        audio = codec.decode(z)                      # [1, 1, frames * 512]
+        jio.write_wav_float32(os.path.join(args.output_dir, name), audio[0, 0], codec.sample_rate)
+    print(f"decoded {len(outs)} latents with DAC ({args.dac_precision}) -> {[n for n, _ in outs]}")
 
 
 def main(argv=None):

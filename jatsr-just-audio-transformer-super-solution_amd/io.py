@@ -78,3 +78,27 @@ def first_latent_file(val_dir):
     if not files:
         raise FileNotFoundError(f"No files found in {val_dir}")
     return os.path.join(val_dir, files[0])
+
+
+def write_wav_float32(path, samples, sample_rate=44100):
+    """Mono 32-bit IEEE-float WAV (format tag 3), what `torchaudio.save` writes for a float32 tensor
+    (infer_test_v3m2.py:425-436).  Stdlib only; `samples`: 1-D array-like or a [1, n] tensor."""
+    import array
+    import struct
+    if hasattr(samples, "detach"):
+        samples = samples.detach().to("cpu", torch.float32).reshape(-1).tolist()
+    data = array.array("f", samples)
+    if struct.pack("=f", 1.0) != struct.pack("<f", 1.0):
+        data.byteswap()
+    body = data.tobytes()
+    fmt = struct.pack("<HHIIHH", 3, 1, sample_rate, sample_rate * 4, 4, 32)
+    # WAVE_FORMAT_IEEE_FLOAT: fmt chunk with cbSize = 0 and a fact chunk (sample count), as libsndfile writes it
+    fmt += struct.pack("<H", 0)
+    fact = struct.pack("<4sII", b"fact", 4, len(data))
+    size = 4 + (8 + len(fmt)) + len(fact) + (8 + len(body))
+    with open(path, "wb") as f:
+        f.write(struct.pack("<4sI4s", b"RIFF", size, b"WAVE"))
+        f.write(struct.pack("<4sI", b"fmt ", len(fmt)) + fmt)
+        f.write(fact)
+        f.write(struct.pack("<4sI", b"data", len(body)) + body)
+    return path

@@ -186,3 +186,67 @@ CONFIGS = {
     "micro": dict(input_channels=32, cond_channels=32, patch_len=4, hidden_size=256, depth=2,
                   num_q_heads=4, num_kv_heads=2, bottleneck_dim=128, mlp_ratio=4.0),
 }
+
+
+# ---- DAC 44.1 kHz decoder (transformers DacDecoder, modeling_dac.py:407-441) -------------------------------------------
+DAC44K = {"latent_channels": 1024, "channels": 1536, "strides": (8, 8, 4, 2)}   # DacConfig(sampling_rate=44100)
+
+
+def dac_param_shapes(latent_channels: int = 1024, channels: int = 1536, strides=(8, 8, 4, 2)) -> "OrderedDict[str, tuple]":
+    """Folded (plain `weight`) decoder parameters under transformers' DacDecoder names, in registration order."""
+    s: "OrderedDict[str, tuple]" = OrderedDict()
+    s["conv1.weight"] = (channels, latent_channels, 7)
+    s["conv1.bias"] = (channels,)
+    for i, st in enumerate(strides):
+        cin, cout = channels >> i, channels >> (i + 1)
+        p = f"block.{i}."
+        s[p + "snake1.alpha"] = (1, cin, 1)
+        s[p + "conv_t1.weight"] = (cin, cout, 2 * st)
+        s[p + "conv_t1.bias"] = (cout,)
+        for u in (1, 2, 3):
+            r = f"{p}res_unit{u}."
+            s[r + "snake1.alpha"] = (1, cout, 1)
+            s[r + "conv1.weight"] = (cout, cout, 7)
+            s[r + "conv1.bias"] = (cout,)
+            s[r + "snake2.alpha"] = (1, cout, 1)
+            s[r + "conv2.weight"] = (cout, cout, 1)
+            s[r + "conv2.bias"] = (cout,)
+    cf = channels >> len(strides)
+    s["snake1.alpha"] = (1, cf, 1)
+    s["conv2.weight"] = (1, cf, 7)
+    s["conv2.bias"] = (1,)
+    return s
+
+
+def make_dac_param(name: str, shape, salt: int = 0) -> np.ndarray:
+    """Conv weights uniform with std 0.02 (transformers' DAC init), biases uniform +-0.01, snake alphas spread over
+    [0.5, 3] so that the per-channel alpha matters."""
+    u = uniform("dac." + name, shape, salt)
+    if name.endswith(".alpha"):
+        return (np.float32(1.75) + np.float32(1.25) * u).astype(np.float32)
+    if name.endswith(".weight"):
+        return (u * np.float32(0.02 * np.sqrt(3.0))).astype(np.float32)
+    if name.endswith(".bias"):
+        return (u * np.float32(0.01)).astype(np.float32)
+    raise KeyError(name)
+
+
+def make_dac_state_dict(salt: int = 0, threads: int = 8, **dims) -> "OrderedDict[str, np.ndarray]":
+    shapes = dac_param_shapes(**{**DAC44K, **dims})
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max(1, threads)) as ex:
+        vals = list(ex.map(lambda kv: make_dac_param(kv[0], kv[1], salt), shapes.items()))
+    return OrderedDict(zip(shapes.keys(), vals))
+
+
+def dac_flops(T: int, B: int = 1, latent_channels: int = 1024, channels: int = 1536, strides=(8, 8, 4, 2)) -> int:
+    """Algorithmic FLOPs (2 x MAC) of one decode: 1.608 GFLOP per latent frame for the 44.1 kHz model."""
+    f = 2 * 7 * latent_channels * channels
+    up = 1
+    for i, st in enumerate(strides):
+        cin, cout = channels >> i, channels >> (i + 1)
+        f += 2 * up * st * cout * cin * 2          # transposed conv: 2 taps per output
+        up *= st
+        f += 3 * 2 * up * (7 * cout * cout + cout * cout)
+    f += 2 * up * 7 * (channels >> len(strides))
+    return int(f) * T * B
