@@ -253,6 +253,54 @@ int jat_k_recon_loss(const float* pred, const float* target, float* dpred, float
 /* fp32 -> bf16 (round-to-nearest-even) */
 int jat_k_cast_bf16(const float* in, uint16_t* out, int64_t n, void* stream);
 
+/* ---- per-kernel entry points of the training step (the kernels jat_trainer_fwd_bwd / jat_trainer_optim launch) ----------
+ * Dropout sites are (seed, site, p): the mask of element e is the counter hash of jat_rng.h, as the trainer draws it with
+ * site = layer * 8 + kind.  p in [0, 1); p == 0 disables the site.  A shape the kernel does not take is JAT_E_INVALID;
+ * `work` is device scratch of at least the stated size (JAT_E_INVALID when smaller). */
+/* Training attention forward: o as jat_k_attention with dropout on the probabilities (element ((b*Hq + h)*N + i)*N + j),
+ * lse [B, Hq, N] fp32 = log2-domain log-sum-exp of the un-dropped scaled scores.  1 <= N <= 2048. */
+int jat_k_attention_train(const uint16_t* q, const uint16_t* k, const uint16_t* vt, uint16_t* o, float* lse, int32_t B,
+                          int32_t N, int32_t Hq, int32_t Hkv, int32_t Npad, uint64_t seed, int32_t site, float p, void* stream);
+/* Its backward: dqkv [B*N, (Hq + 2 Hkv)*64] = (dQ | dK | dV) with the inverse RoPE of rope_cos / rope_sin [2048, 32] (token
+ * position = row within the sample) applied to dQ and dK.  split_heads = 1: the query heads of a KV group go to separate
+ * blocks whose fp32 partials are reduced afterwards (the trainer's form); 0: one block per KV group.
+ * work: align256(B*Hq*N*4) + (split_heads ? B*Hq*N*128*4 : 0) bytes. */
+int jat_k_attention_bwd(const uint16_t* q, const uint16_t* k, const uint16_t* vt, const uint16_t* o, const uint16_t* dout,
+                        const float* lse, uint16_t* dqkv, const float* rope_cos, const float* rope_sin, int32_t B, int32_t N,
+                        int32_t Hq, int32_t Hkv, int32_t Npad, uint64_t seed, int32_t site, float p, int32_t split_heads,
+                        void* work, size_t work_bytes, void* stream);
+/* Backward of y = norm(x) (* w) * (1 + scale[b]) + shift[b] on x [B*ntok, D] (D = 256..2048 in steps of 256): dx (+)= dL/dx;
+ * dshift / dscale rows b at dmod_bstride; dw [D] summed over all rows.  w, scale, dshift, dscale, dw each nullable; mode 1
+ * (LayerNorm, no affine) takes no w / dw.  work: (B*ceil(ntok/16)*3*D + B*D)*4 bytes. */
+int jat_k_norm_bwd(const float* x, const uint16_t* dy, const float* w, const float* scale, int64_t mod_bstride, float* dx,
+                   int32_t accumulate, float* dshift, float* dscale, int64_t dmod_bstride, float* dw, int32_t B, int32_t D,
+                   int32_t ntok, int32_t mode, void* work, size_t work_bytes, void* stream);
+/* Backward of x_out = x_in + gate[b] * pm[b] * (m o y): dy = dx * gate * pm * m (16-bit), dgate[b] = sum_tok dx * y * pm * m;
+ * pm = DropPath draw of sample b (path site), m = element dropout of [B, ntok, D] (elem site).  work: B*ceil(ntok/16)*D*4 bytes. */
+int jat_k_gate_bwd(const float* dx, const uint16_t* y, const float* gate, int64_t gate_bstride, uint16_t* dy, float* dgate,
+                   int64_t dgate_bstride, int32_t B, int32_t D, int32_t ntok, uint64_t seed, int32_t path_site, float path_p,
+                   int32_t elem_site, float elem_p, void* work, size_t work_bytes, void* stream);
+/* The forward it differentiates: x_out [M, D] = x_in + gate[row / ntok] * pm * (m o y) (D % 8 == 0). */
+int jat_k_resid_gate(const float* x_in, const uint16_t* y, const float* gate, int64_t gate_bstride, float* x_out, int32_t M,
+                     int32_t D, int32_t ntok, uint64_t seed, int32_t path_site, float path_p, int32_t elem_site, float elem_p,
+                     void* stream);
+/* out = m o gelu_erf(in) and its backward in place: d = d * m * gelu'(pre); n % 8 == 0. */
+int jat_k_gelu(const uint16_t* in, uint16_t* out, int64_t n, uint64_t seed, int32_t site, float p, void* stream);
+int jat_k_gelu_bwd(const uint16_t* pre, uint16_t* d, int64_t n, uint64_t seed, int32_t site, float p, void* stream);
+/* clip_grad_norm_(max_grad_norm) of g / loss_scale + one AdamW step on p, m, v (the kernels of jat_trainer_optim, same
+ * semantics); grad_norm_out (device, nullable) = L2 norm of the SCALED g.  n % 4 == 0; work: 4104 bytes. */
+int jat_k_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                float weight_decay, float max_grad_norm, float loss_scale, int32_t step, float* grad_norm_out, void* work,
+                size_t work_bytes, void* stream);
+/* Small-batch Linear backward (adaLN modulation, t_embedder): dW [N, K] = dy[B, N]^T x'[B, K] with x' = silu(x) if silu_x,
+ * db [N] = column sums of dy (nullable); B <= 64, K % 4 == 0. */
+int jat_k_small_dw(const float* dy, int64_t ldy, const float* x, int64_t ldx, float* dW, float* db, int32_t B, int32_t N,
+                   int32_t K, int32_t silu_x, void* stream);
+/* dx [B, K] (+)= dy[B, N] W[N, K] (W 16-bit if w_is_bf16, else fp32), then times silu'(silu_pre) when silu_pre is given;
+ * B <= 32, K % 4 == 0; work: ceil(N / slab)*B*K*4 bytes, slab = 256 for N >= 16384, else 32. */
+int jat_k_small_dx(const float* dy, int64_t ldy, const void* W, int32_t w_is_bf16, float* dx, int32_t B, int32_t N, int32_t K,
+                   int32_t accumulate, const float* silu_pre, void* work, size_t work_bytes, void* stream);
+
 /* ---- measurement aid (bench.py roofline leg; no reference counterpart) ------------------------------------ */
 /* (state lives in the model handle: two models in one process do not share a bracket)
  * Bracket every GEMM launch of one call site (0 qkv, 1 out_proj, 2 MLP fc1, 3 MLP fc2, 4 other; -1 = off) with a

@@ -73,6 +73,17 @@ SIGNATURES = {
     "jat_k_attention": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP]),
     "jat_k_recon_loss": (C.c_int, [_VP, _VP, _VP, _VP, _I64, C.c_double, _F32, _VP, _SZ, _VP]),
     "jat_k_cast_bf16": (C.c_int, [_VP, _VP, _I64, _VP]),
+    "jat_k_attention_train": (C.c_int, [_VP] * 5 + [_I32] * 5 + [C.c_uint64, _I32, _F32, _VP]),
+    "jat_k_attention_bwd": (C.c_int, [_VP] * 9 + [_I32] * 5 + [C.c_uint64, _I32, _F32, _I32, _VP, _SZ, _VP]),
+    "jat_k_norm_bwd": (C.c_int, [_VP, _VP, _VP, _VP, _I64, _VP, _I32, _VP, _VP, _I64, _VP] + [_I32] * 4 + [_VP, _SZ, _VP]),
+    "jat_k_gate_bwd": (C.c_int, [_VP, _VP, _VP, _I64, _VP, _VP, _I64] + [_I32] * 3 + [C.c_uint64, _I32, _F32, _I32, _F32] +
+                       [_VP, _SZ, _VP]),
+    "jat_k_resid_gate": (C.c_int, [_VP, _VP, _VP, _I64, _VP] + [_I32] * 3 + [C.c_uint64, _I32, _F32, _I32, _F32, _VP]),
+    "jat_k_gelu": (C.c_int, [_VP, _VP, _I64, C.c_uint64, _I32, _F32, _VP]),
+    "jat_k_gelu_bwd": (C.c_int, [_VP, _VP, _I64, C.c_uint64, _I32, _F32, _VP]),
+    "jat_k_adamw": (C.c_int, [_VP, _VP, _VP, _VP, _I64] + [_F32] * 7 + [_I32, _VP, _VP, _SZ, _VP]),
+    "jat_k_small_dw": (C.c_int, [_VP, _I64, _VP, _I64, _VP, _VP] + [_I32] * 4 + [_VP]),
+    "jat_k_small_dx": (C.c_int, [_VP, _I64, _VP, _I32, _VP] + [_I32] * 4 + [_VP, _VP, _SZ, _VP]),
     "jat_k_latent_loss": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I32, _I32] + [C.c_double] * 7 + [_F32, _VP, _SZ, _VP]),
     "jat_trainer_create": (C.c_int, [_VP, C.POINTER(JatTensorRef), _I32, _VP, _VP, _VP, _VP, _I64, _I32, _I32, _VP,
                                      C.POINTER(_VP)]),

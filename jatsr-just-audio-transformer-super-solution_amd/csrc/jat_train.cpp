@@ -768,6 +768,158 @@ extern "C" int jat_k_latent_loss(const float* pred, const float* target, const f
   return JAT_OK;
 }
 
+// ---- per-kernel entry points of the training step (unit parity against fp64 references; include/jat_hip.h) ------------
+// Each validates what its launcher would reject (JAT_E_INVALID, never a launch that fails), takes its scratch from the
+// caller's `work` and calls the same launch_* the trainer calls.  Dropout sites are (seed, site, p) -> jat_drop_spec, as site().
+namespace {
+bool rate_ok(float p) { return p >= 0.f && p < 1.f; }
+bool al16(const void* p) { return ((uintptr_t)p & 15u) == 0; }
+}  // namespace
+
+extern "C" int jat_k_attention_train(const uint16_t* q, const uint16_t* k, const uint16_t* vt, uint16_t* o, float* lse, int32_t B,
+                                     int32_t N, int32_t Hq, int32_t Hkv, int32_t Npad, uint64_t seed, int32_t site, float p,
+                                     void* stream) {
+  if (!q || !k || !vt || !o || !lse) return fail(JAT_E_INVALID, "null argument");
+  if (B <= 0 || N <= 0 || N > MAX_LEN || Hkv <= 0 || Hq <= 0 || Hq % Hkv != 0 || Npad % 64 != 0 || Npad < N)
+    return fail(JAT_E_INVALID, "bad shape: B %d N %d (1..%d) Hq %d Hkv %d Npad %d", B, N, MAX_LEN, Hq, Hkv, Npad);
+  if (site < 0 || !rate_ok(p)) return fail(JAT_E_INVALID, "site must be >= 0 and p in [0, 1)");
+  AttnArgs a{};
+  a.q = q; a.k = k; a.vt = vt; a.o = o; a.ldq = (int64_t)Hq * 64; a.ldk = (int64_t)Hkv * 64; a.ldo = (int64_t)Hq * 64;
+  a.B = B; a.N = N; a.Hq = Hq; a.Hkv = Hkv; a.npad = Npad;
+  a.scale_log2e = 0.125f * 1.4426950408889634f;
+  a.lse = lse;
+  a.drop = jat_drop_spec(seed, (uint32_t)site, p);
+  KCHK(launch_attention(a, (hipStream_t)stream));
+  return JAT_OK;
+}
+
+extern "C" int jat_k_attention_bwd(const uint16_t* q, const uint16_t* k, const uint16_t* vt, const uint16_t* o, const uint16_t* dout,
+                                   const float* lse, uint16_t* dqkv, const float* rope_cos, const float* rope_sin, int32_t B,
+                                   int32_t N, int32_t Hq, int32_t Hkv, int32_t Npad, uint64_t seed, int32_t site, float p,
+                                   int32_t split_heads, void* work, size_t work_bytes, void* stream) {
+  if (!q || !k || !vt || !o || !dout || !lse || !dqkv || !rope_cos || !rope_sin || !work) return fail(JAT_E_INVALID, "null argument");
+  if (B <= 0 || N <= 0 || N > MAX_LEN || Hkv <= 0 || Hq <= 0 || Hq % Hkv != 0 || Npad % 64 != 0 || Npad < N)
+    return fail(JAT_E_INVALID, "bad shape: B %d N %d (1..%d) Hq %d Hkv %d Npad %d", B, N, MAX_LEN, Hq, Hkv, Npad);
+  if (site < 0 || !rate_ok(p)) return fail(JAT_E_INVALID, "site must be >= 0 and p in [0, 1)");
+  const size_t rows = (size_t)B * Hq * N, delta_b = align_up(rows * 4, 256);
+  const size_t need = delta_b + (split_heads ? rows * 128 * 4 : 0);
+  if (work_bytes < need) return fail(JAT_E_INVALID, "work needs %zu bytes", need);
+  float* delta = (float*)work;
+  float* dkv_part = split_heads ? (float*)((char*)work + delta_b) : nullptr;
+  KCHK(launch_attention_bwd(q, k, vt, o, dout, lse, delta, dqkv, rope_cos, rope_sin, B, N, Hq, Hkv, Npad,
+                            jat_drop_spec(seed, (uint32_t)site, p), dkv_part, (hipStream_t)stream));
+  return JAT_OK;
+}
+
+extern "C" int jat_k_norm_bwd(const float* x, const uint16_t* dy, const float* w, const float* scale, int64_t mod_bstride,
+                              float* dx, int32_t accumulate, float* dshift, float* dscale, int64_t dmod_bstride, float* dw,
+                              int32_t B, int32_t D, int32_t ntok, int32_t mode, void* work, size_t work_bytes, void* stream) {
+  if (!x || !dy || !dx || !work) return fail(JAT_E_INVALID, "null argument");
+  if (D % 256 != 0 || D <= 0 || D > 2048) return fail(JAT_E_INVALID, "D = %d: a multiple of 256 up to 2048", D);
+  if (B <= 0 || ntok <= 0) return fail(JAT_E_INVALID, "B and ntok must be positive");
+  if (mode != JAT_NORM_RMS_W && mode != JAT_NORM_LN_NOAFFINE) return fail(JAT_E_INVALID, "mode must be 0 (RMS) or 1 (LayerNorm)");
+  if (mode == JAT_NORM_LN_NOAFFINE && (w || dw)) return fail(JAT_E_INVALID, "the LayerNorm (mode 1) has no weight");
+  if (scale && (mod_bstride < 0 || mod_bstride % 4 != 0 || !al16(scale)))
+    return fail(JAT_E_INVALID, "scale rows must be 16-byte aligned (mod_bstride %% 4 == 0)");
+  if ((dshift || dscale) && dmod_bstride < D) return fail(JAT_E_INVALID, "dmod_bstride must be >= D");
+  if (!al16(x) || !al16(dx) || !al16(dy) || (w && !al16(w))) return fail(JAT_E_INVALID, "x, dy, dx and w must be 16-byte aligned");
+  const size_t part_f = (size_t)B * train_nchunk(ntok) * 3 * D, need = (part_f + (size_t)B * D) * 4;
+  if (work_bytes < need) return fail(JAT_E_INVALID, "work needs %zu bytes", need);
+  float* part = (float*)work;
+  KCHK(launch_norm_bwd(x, dy, w, scale, mod_bstride, dx, accumulate ? 1 : 0, part, part + part_f, dshift, dscale, dmod_bstride,
+                       dw, B, D, ntok, mode, (hipStream_t)stream));
+  return JAT_OK;
+}
+
+extern "C" int jat_k_gate_bwd(const float* dx, const uint16_t* y, const float* gate, int64_t gate_bstride, uint16_t* dy,
+                              float* dgate, int64_t dgate_bstride, int32_t B, int32_t D, int32_t ntok, uint64_t seed,
+                              int32_t path_site, float path_p, int32_t elem_site, float elem_p, void* work, size_t work_bytes,
+                              void* stream) {
+  if (!dx || !y || !gate || !dy || !dgate || !work) return fail(JAT_E_INVALID, "null argument");
+  if (B <= 0 || ntok <= 0 || D <= 0 || D % 4 != 0) return fail(JAT_E_INVALID, "B, ntok > 0 and D a positive multiple of 4");
+  if (gate_bstride < 0 || gate_bstride % 4 != 0 || dgate_bstride < D) return fail(JAT_E_INVALID, "bad gate strides");
+  if (!al16(dx) || !al16(gate) || ((uintptr_t)y & 7u) || ((uintptr_t)dy & 7u)) return fail(JAT_E_INVALID, "misaligned operand");
+  if (path_site < 0 || elem_site < 0 || !rate_ok(path_p) || !rate_ok(elem_p)) return fail(JAT_E_INVALID, "bad dropout site");
+  const size_t need = (size_t)B * train_nchunk(ntok) * D * 4;
+  if (work_bytes < need) return fail(JAT_E_INVALID, "work needs %zu bytes", need);
+  KCHK(launch_gate_bwd(dx, y, gate, gate_bstride, dy, (float*)work, dgate, dgate_bstride, B, D, ntok,
+                       jat_drop_spec(seed, (uint32_t)path_site, path_p), jat_drop_spec(seed, (uint32_t)elem_site, elem_p),
+                       (hipStream_t)stream));
+  return JAT_OK;
+}
+
+extern "C" int jat_k_resid_gate(const float* x_in, const uint16_t* y, const float* gate, int64_t gate_bstride, float* x_out,
+                                int32_t M, int32_t D, int32_t ntok, uint64_t seed, int32_t path_site, float path_p,
+                                int32_t elem_site, float elem_p, void* stream) {
+  if (!x_in || !y || !gate || !x_out) return fail(JAT_E_INVALID, "null argument");
+  if (M <= 0 || ntok <= 0 || D <= 0 || D % 8 != 0) return fail(JAT_E_INVALID, "M, ntok > 0 and D a positive multiple of 8");
+  if (gate_bstride < 0 || gate_bstride % 4 != 0) return fail(JAT_E_INVALID, "gate_bstride must be a multiple of 4");
+  if (!al16(x_in) || !al16(x_out) || !al16(gate) || !al16(y)) return fail(JAT_E_INVALID, "misaligned operand");
+  if (path_site < 0 || elem_site < 0 || !rate_ok(path_p) || !rate_ok(elem_p)) return fail(JAT_E_INVALID, "bad dropout site");
+  KCHK(launch_resid_gate(x_in, y, gate, gate_bstride, x_out, M, D, ntok, jat_drop_spec(seed, (uint32_t)path_site, path_p),
+                         jat_drop_spec(seed, (uint32_t)elem_site, elem_p), (hipStream_t)stream));
+  return JAT_OK;
+}
+
+extern "C" int jat_k_gelu(const uint16_t* in, uint16_t* out, int64_t n, uint64_t seed, int32_t site, float p, void* stream) {
+  if (!in || !out) return fail(JAT_E_INVALID, "null argument");
+  if (n <= 0 || n % 8 != 0 || !al16(in) || !al16(out)) return fail(JAT_E_INVALID, "n must be a positive multiple of 8, 16-B aligned");
+  if (site < 0 || !rate_ok(p)) return fail(JAT_E_INVALID, "site must be >= 0 and p in [0, 1)");
+  KCHK(launch_gelu_bf16(in, out, n, jat_drop_spec(seed, (uint32_t)site, p), (hipStream_t)stream));
+  return JAT_OK;
+}
+
+extern "C" int jat_k_gelu_bwd(const uint16_t* pre, uint16_t* d, int64_t n, uint64_t seed, int32_t site, float p, void* stream) {
+  if (!pre || !d) return fail(JAT_E_INVALID, "null argument");
+  if (n <= 0 || n % 8 != 0 || !al16(pre) || !al16(d)) return fail(JAT_E_INVALID, "n must be a positive multiple of 8, 16-B aligned");
+  if (site < 0 || !rate_ok(p)) return fail(JAT_E_INVALID, "site must be >= 0 and p in [0, 1)");
+  KCHK(launch_gelu_bwd(pre, d, n, jat_drop_spec(seed, (uint32_t)site, p), (hipStream_t)stream));
+  return JAT_OK;
+}
+
+extern "C" int jat_k_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                           float weight_decay, float max_grad_norm, float loss_scale, int32_t step, float* grad_norm_out,
+                           void* work, size_t work_bytes, void* stream) {
+  if (!p || !g || !m || !v || !work) return fail(JAT_E_INVALID, "null argument");
+  if (n <= 0 || n % 4 != 0 || !al16(p) || !al16(g) || !al16(m) || !al16(v))
+    return fail(JAT_E_INVALID, "n must be a positive multiple of 4, buffers 16-B aligned");
+  if (step < 1 || !(loss_scale > 0.f)) return fail(JAT_E_INVALID, "step must be >= 1 and loss_scale > 0");
+  const size_t need = ((size_t)train_red_blocks() + 2) * 4;
+  if (work_bytes < need) return fail(JAT_E_INVALID, "work needs %zu bytes", need);
+  hipStream_t s = (hipStream_t)stream;
+  float* part = (float*)work;
+  float* norm2 = part + train_red_blocks();
+  // as jat_trainer_optim chains them: sum of squares of the scaled gradients, then clip + AdamW
+  KCHK(launch_grad_sqsum(g, n, part, norm2, s));
+  KCHK(launch_adamw(p, (float*)g, m, v, n, norm2, 1.0f / loss_scale, max_grad_norm, lr, beta1, beta2, eps, weight_decay, step, s));
+  if (grad_norm_out) HIPCHK(hipMemcpyAsync(grad_norm_out, norm2 + 1, 4, hipMemcpyDeviceToDevice, s));
+  return JAT_OK;
+}
+
+extern "C" int jat_k_small_dw(const float* dy, int64_t ldy, const float* x, int64_t ldx, float* dW, float* db, int32_t B, int32_t N,
+                              int32_t K, int32_t silu_x, void* stream) {
+  if (!dy || !x || !dW) return fail(JAT_E_INVALID, "null argument");
+  if (B <= 0 || B > 64) return fail(JAT_E_INVALID, "B = %d: 1..64 rows", B);
+  if (N <= 0 || K <= 0 || K % 4 != 0 || ldy < N || ldx < K || ldx % 4 != 0)
+    return fail(JAT_E_INVALID, "N > 0, K a positive multiple of 4, ldy >= N, ldx >= K a multiple of 4");
+  if (!al16(x) || !al16(dW)) return fail(JAT_E_INVALID, "x and dW must be 16-byte aligned");
+  KCHK(launch_small_dw(dy, ldy, x, ldx, dW, db, B, N, K, silu_x ? 1 : 0, (hipStream_t)stream));
+  return JAT_OK;
+}
+
+extern "C" int jat_k_small_dx(const float* dy, int64_t ldy, const void* W, int32_t w_is_bf16, float* dx, int32_t B, int32_t N,
+                              int32_t K, int32_t accumulate, const float* silu_pre, void* work, size_t work_bytes, void* stream) {
+  if (!dy || !W || !dx || !work) return fail(JAT_E_INVALID, "null argument");
+  if (B <= 0 || B > 32) return fail(JAT_E_INVALID, "B = %d: 1..32 rows", B);
+  if (N <= 0 || K <= 0 || K % 4 != 0 || ldy < N) return fail(JAT_E_INVALID, "N > 0, K a positive multiple of 4, ldy >= N");
+  if (((uintptr_t)W & (w_is_bf16 ? 7u : 15u)) || !al16(work)) return fail(JAT_E_INVALID, "misaligned W or work");
+  const int slab = small_dx_slab(N);
+  const size_t need = (size_t)((N + slab - 1) / slab) * B * K * 4;
+  if (work_bytes < need) return fail(JAT_E_INVALID, "work needs %zu bytes", need);
+  KCHK(launch_small_dx(dy, ldy, W, w_is_bf16 ? 1 : 0, (float*)work, dx, B, N, K, accumulate ? 1 : 0, silu_pre, (hipStream_t)stream));
+  return JAT_OK;
+}
+
 // Re-derive every operand copy (bf16 weights, transposed copies, fp32 operand tensors) from the flat master buffer,
 // e.g. after the caller overwrote parameters (checkpoint resume, train_ddp_v3m2.py:443-500).
 extern "C" int jat_trainer_repack(jat_trainer* tr, void* stream) {

@@ -56,17 +56,25 @@ def drop_mult(seed, site, p, shape):
     3 MLP output [B,N,D], 4 DropPath(MLP) [B]."""
     if p <= 0:
         return np.ones(shape)
+    return drop_mult_range(seed, site, p, 0, int(np.prod(shape))).reshape(shape)
+
+
+def drop_mult_range(seed, site, p, start, count):
+    """The multipliers of elements start .. start + count - 1 of a site (flat element indices, may exceed 2^32): the same
+    values as drop_mult(...).ravel()[start:start + count] without enumerating the whole tensor."""
+    if p <= 0:
+        return np.ones(count)
     seed, site = int(seed), int(site)
     k0 = _hash32((seed & 0xFFFFFFFF) ^ ((site * 0x9e3779b9) & 0xFFFFFFFF))
     k1 = _hash32(((seed >> 32) + site * 0x85ebca6b + 1) & 0xFFFFFFFF)
     t = float(np.float32(p)) * 4294967296.0
     thresh = 4294967295 if t >= 4294967295.0 else int(t)
-    idx = np.arange(int(np.prod(shape)), dtype=np.uint64)
+    idx = np.arange(int(start), int(start) + int(count), dtype=np.uint64)
     lo, hi = idx & _M32, idx >> np.uint64(32)
     rot = ((hi << np.uint64(13)) | (hi >> np.uint64(19))) & _M32
     r = _hash32(lo ^ k0 ^ rot) ^ k1
     inv_keep = float(np.float32(1.0) / (np.float32(1.0) - np.float32(p)))
-    return np.where(r < np.uint64(thresh), 0.0, inv_keep).reshape(shape)
+    return np.where(r < np.uint64(thresh), 0.0, inv_keep)
 
 
 class DropPlan:

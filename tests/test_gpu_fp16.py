@@ -33,6 +33,7 @@ def test_fp16_library_is_what_the_env_selects():
 
 def test_fp16_kernels_and_forward_parity():
     _child(["tests/test_gpu_kernels.py"])
+    _child(["tests/test_gpu_train_kernels.py"])
     _child(["tests/test_gpu_model.py", "-k", "forward_vs_reference or sampler_vs_reference or benchmarked or fused"])
 
 

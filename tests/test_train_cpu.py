@@ -310,3 +310,31 @@ def test_train_oracle_v3mod2_step_matches_reference(name):
         ref_l2 = float(z["gl2_" + k])
         assert abs(np.linalg.norm(grads[k]) - ref_l2) <= 2e-4 * max(ref_l2, 1e-30), k   # the reference runs its FFT terms in fp32
         assert rel_l2(gsub(grads[k], meta), z["g_" + k]) <= 5e-4, k
+
+
+def _drop_mult_scalar(seed, site, p, idx):
+    """jat_rng.h jat_drop_spec + jat_drop_mult for one element, in plain Python integers (an independent transcription)."""
+    def h(x):
+        x &= 0xFFFFFFFF
+        x ^= x >> 16; x = (x * 0x7feb352d) & 0xFFFFFFFF
+        x ^= x >> 15; x = (x * 0x846ca68b) & 0xFFFFFFFF
+        return x ^ (x >> 16)
+    k0 = h((seed & 0xFFFFFFFF) ^ ((site * 0x9e3779b9) & 0xFFFFFFFF))
+    k1 = h((seed >> 32) + site * 0x85ebca6b + 1)
+    thresh = min(int(float(np.float32(p)) * 4294967296.0), 4294967295)
+    hi = idx >> 32
+    r = h((idx & 0xFFFFFFFF) ^ k0 ^ (((hi << 13) | (hi >> 19)) & 0xFFFFFFFF)) ^ k1
+    return 0.0 if r < thresh else float(np.float32(1.0) / (np.float32(1.0) - np.float32(p)))
+
+
+def test_drop_mult_range_matches_the_whole_tensor_form_and_the_64_bit_index():
+    """drop_mult_range (masks of a slice of a site, element indices past 2^32 included) is the whole-tensor mirror sliced."""
+    seed, site, p = 0x1234_5678_9ABC_DEF0, 3 * 8 + 0, 0.3
+    full = OT.drop_mult(seed, site, p, (3, 5, 7, 11)).ravel()
+    for start, count in [(0, full.size), (17, 100), (full.size - 9, 9)]:
+        assert np.array_equal(OT.drop_mult_range(seed, site, p, start, count), full[start:start + count])
+    assert np.array_equal(OT.drop_mult_range(seed, site, 0.0, 5, 4), np.ones(4))
+    start = (1 << 32) - 40                     # both sides of 2^32, where the rotated high half enters the hash
+    got = OT.drop_mult_range(seed, site, p, start, 80)
+    ref = np.array([_drop_mult_scalar(seed, site, p, start + i) for i in range(80)])
+    assert np.array_equal(got, ref) and 0 < (got == 0).sum() < 80
