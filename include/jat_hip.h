@@ -76,7 +76,7 @@ int jat_model_load_weights(jat_model* m, const jat_tensor_ref* named, int32_t n,
 int jat_model_workspace_bytes(const jat_model* m, int32_t B, int32_t T, size_t* out);
 /* Behaviour switches of this handle.  Their defaults come from the JAT_* environment variables, which are read ONCE, in
  * jat_model_create (INTEGRATION.md "Environment switches"); nothing on the enqueue path reads the environment.  Names:
- * "fuse_qkv_attn" (0 / 1 / 2), "qkv_split", "fuse_finish", "fold_norm" (0 / 1 / 2), "split_patch", "gemm_dbg", "fold_cap_mb".
+ * "fuse_qkv_attn" (0 / 1 / 2), "qkv_split", "fuse_finish", "fold_norm" (0 / 1 / 2), "split_patch", "patch_split", "fold_cap_mb".
  * Takes effect for forwards enqueued and samplers created afterwards. */
 int jat_model_set_switch(jat_model* m, const char* name, int32_t value);
 

@@ -340,43 +340,19 @@ __global__ void __launch_bounds__((WM * WN + (PIPE == 6 ? 4 : 0)) * 64, (WM * WN
     __builtin_amdgcn_s_barrier();
     if (grp == 1) __builtin_amdgcn_s_barrier();
     int cur = 0;
-    // optional timeline (diagnostic build path, taken only when dbg_out is set): cycles per slot phase
-    unsigned long long tl_load = 0, tl_b1 = 0, tl_mma = 0, tl_b2 = 0, ts0 = 0, ts1 = 0, ts2 = 0, ts3 = 0;
-    const bool tl = p.dbg_out != nullptr;
-#define JAT_STAMP(x)                                                                  \
-  if (tl) {                                                                           \
-    __builtin_amdgcn_sched_barrier(0);                                                \
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(x)::"memory");        \
-    __builtin_amdgcn_sched_barrier(0);                                                \
-  }
-    JAT_STAMP(ts0)
     for (int kt = 0; kt < nk; ++kt) {
       read_frags(a0, w0, cur, coff0);
       read_frags(a1, w1, cur, coff1);
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
-      JAT_STAMP(ts1)
       __builtin_amdgcn_s_barrier();
-      JAT_STAMP(ts2)
       __builtin_amdgcn_s_setprio(1);
       mma(a0, w0);
       mma(a1, w1);
       __builtin_amdgcn_s_setprio(0);
       __builtin_amdgcn_sched_barrier(0);
-      JAT_STAMP(ts3)
       __builtin_amdgcn_s_barrier();
-      if (tl) {
-        unsigned long long ts4;
-        JAT_STAMP(ts4)
-        tl_load += ts1 - ts0; tl_b1 += ts2 - ts1; tl_mma += ts3 - ts2; tl_b2 += ts4 - ts3;
-        ts0 = ts4;
-      }
       cur = cur == 2 ? 0 : cur + 1;
-    }
-#undef JAT_STAMP
-    if (tl && lane == 0) {
-      unsigned long long* o = p.dbg_out + ((size_t)blockIdx.x * NW + wave) * 4;
-      o[0] = tl_load; o[1] = tl_b1; o[2] = tl_mma; o[3] = tl_b2;
     }
     if (grp == 0) __builtin_amdgcn_s_barrier();
   } else if constexpr (PIPE == 8) {
@@ -494,7 +470,7 @@ __global__ void __launch_bounds__((WM * WN + (PIPE == 6 ? 4 : 0)) * 64, (WM * WN
     // fused QKV + attention: the v tile (j = TN - 1) with the operands swapped, D[token][feature]: a lane then holds 4 consecutive
     // KEYS of one feature, which is 8 contiguous bytes of the V^T operand image
 #define JAT_Q(I0, IC, J0, JC)                                                                                   \
-  if (!abl_mma) _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                                              \
+  _Pragma("unroll") for (int ks = 0; ks < 2; ++ks)                                                              \
   _Pragma("unroll") for (int i = 0; i < (IC); ++i)                                                              \
   _Pragma("unroll") for (int j = 0; j < (JC); ++j)                                                              \
     acc[(I0) + i][(J0) + j] = (QA && (J0) + j == TN - 1)                                                        \
@@ -523,38 +499,32 @@ __global__ void __launch_bounds__((WM * WN + (PIPE == 6 ? 4 : 0)) * 64, (WM * WN
     __builtin_amdgcn_s_barrier();
     if (grp == 1) __builtin_amdgcn_s_barrier();
     JAT_TL(1)
-#ifdef JAT_ABLATE   // timing ablations (wrong results; -DJAT_ABLATE builds only): dbg bit 1: no DMA after the prologue, bit 2: no fragment reads
-    const bool abl_dma = p.dbg & 2, abl_rd = p.dbg & 4, abl_mma = p.dbg & 8;   // after K-tile 0, bit 3: no MFMAs
-#else
-    constexpr bool abl_dma = false, abl_rd = false, abl_mma = false;
-#endif
     auto ktile = [&](int t, int st) {
-      const bool more2 = t + 2 < nk && !abl_dma;
-      const bool more1 = t >= 1 && t + 1 < nk && !abl_dma;
-      const bool rd = !abl_rd || t == 0;
+      const bool more2 = t + 2 < nk;
+      const bool more1 = t >= 1 && t + 1 < nk;
       if constexpr (SPLIT_M) {
         // P1 (A0, B0)
-        if (rd) rd_b(st, 0, TNa);
+        rd_b(st, 0, TNa);
         __builtin_amdgcn_sched_barrier(0);
-        if (rd) rd_a(st, 0, TMa);
+        rd_a(st, 0, TMa);
         if (more1) dma_b0(st ^ 1, t + 1);
         JAT_LOAD_END()
         JAT_Q(0, TMa, 0, TNa)
         JAT_MMA_END()
         // P2 (A0, B1)
-        if (rd) rd_b(st, TNa, TNb);
+        rd_b(st, TNa, TNb);
         if (more2) dma_a0(st, t + 2);
         JAT_LOAD_END()
         JAT_Q(0, TMa, TNa, TNb)
         JAT_MMA_END()
         // P3 (A1, B1)
-        if (rd) rd_a(st, TMa, TMb);
+        rd_a(st, TMa, TMb);
         if (more2) dma_b1(st, t + 2);
         JAT_LOAD_END()
         JAT_Q(TMa, TMb, TNa, TNb)
         JAT_MMA_END()
         // P4 (A1, B0)
-        if (rd) rd_b(st, 0, TNa);
+        rd_b(st, 0, TNa);
         if (more2) {
           dma_a1(st, t + 2);
           asm volatile("s_waitcnt vmcnt(%0)" ::"n"(CA0 + CB1 + CA1) : "memory");
@@ -566,15 +536,15 @@ __global__ void __launch_bounds__((WM * WN + (PIPE == 6 ? 4 : 0)) * 64, (WM * WN
         JAT_MMA_END()
       } else {
         // P1 (A, B0)
-        if (rd) rd_b(st, 0, TNa);
+        rd_b(st, 0, TNa);
         __builtin_amdgcn_sched_barrier(0);
-        if (rd) rd_a(st, 0, TMa);
+        rd_a(st, 0, TMa);
         if (more1) dma_b1(st ^ 1, t + 1);
         JAT_LOAD_END()
         JAT_Q(0, TMa, 0, TNa)
         JAT_MMA_END()
         // P2 (A, B1)
-        if (rd) rd_b(st, TNa, TNb);
+        rd_b(st, TNa, TNb);
         if (more2) {
           dma_a0(st, t + 2);
           dma_b0(st, t + 2);
@@ -651,7 +621,7 @@ __global__ void __launch_bounds__((WM * WN + (PIPE == 6 ? 4 : 0)) * 64, (WM * WN
       static_assert(NW * 32 * RS <= 2 * STAGE, "epilogue slab does not fit the staging buffers");
       __builtin_amdgcn_s_barrier();            // every wave is done reading the staging buffers
       JAT_TL(3)
-      if (p.dbg & 1) { JAT_TL_FLUSH() return; }
+      if (p.M <= 0) return;                    // see the coalesced epilogue
       char* wbuf = smem + wave * (32 * RS);
       const int mw0 = m0 + wm * TM * 16;
       float4 bb[TN];
@@ -713,10 +683,11 @@ __global__ void __launch_bounds__((WM * WN + (PIPE == 6 ? 4 : 0)) * 64, (WM * WN
             ho[e] = (unsigned)ha | ((unsigned)hb << 16);
             const float ra = x[2 * e] - jat_op2f(ha), rb = x[2 * e + 1] - jat_op2f(hb);
             lw2[e] = jat_pack2(ra, rb);
-            sq += x[2 * e] * x[2 * e] + x[2 * e + 1] * x[2 * e + 1];
+            // spelled out: which product -ffp-contract fuses otherwise depends on the code around it (the rounding must not)
+            sq += __builtin_fmaf(x[2 * e], x[2 * e], x[2 * e + 1] * x[2 * e + 1]);
           }
           const bool live = row < grows && m < p.M;
-          if (live && !(p.dbg & 128)) {
+          if (live) {
             *(uint4*)(p.fold_out + (int64_t)m * p.ldo + n) = uint4{ho[0], ho[1], ho[2], ho[3]};
             *(uint4*)(p.fold_lo + (int64_t)m * p.ldo + n) = uint4{lw2[0], lw2[1], lw2[2], lw2[3]};
           }
@@ -754,7 +725,9 @@ __global__ void __launch_bounds__((WM * WN + (PIPE == 6 ? 4 : 0)) * 64, (WM * WN
     static_assert(NW * 32 * RS <= 2 * STAGE, "epilogue slab does not fit the staging buffers");
     __builtin_amdgcn_s_barrier();             // every wave is done reading the staging buffers
     JAT_TL(3)
-    if (p.dbg & 1) { JAT_TL_FLUSH() return; }
+    // nothing to store for an empty M; the branch also keeps this epilogue's setup out of the K loop's registers (without it
+    // the 224 x 320 EPI_RESID tile spills inside its K loop)
+    if (p.M <= 0) return;
     char* wbuf = smem + wave * (32 * RS);
     const int mw0 = m0 + wm * TM * 16;
     float4 bb[TN];
@@ -813,7 +786,7 @@ __global__ void __launch_bounds__((WM * WN + (PIPE == 6 ? 4 : 0)) * 64, (WM * WN
           constexpr int g = decltype(gc)::value, t = decltype(tc)::value;
           constexpr int grows = (2 * g + 1 < TM) ? 32 : 16;
           const int m = mw0 + g * 32 + rowt[t];
-          if (rowt[t] < grows && m < p.M && !(p.dbg & 128))
+          if (rowt[t] < grows && m < p.M)
             *(u32x4*)((char*)p.out + ((int64_t)(mw0 + g * 32) * p.ldo + nw0) * 2 + goff[t]) = raw[t];
         };
         static_for<0, TN>([&](auto jc) __attribute__((always_inline)) { vwrite(std::integral_constant<int, 0>{}, jc); });
@@ -887,7 +860,7 @@ __global__ void __launch_bounds__((WM * WN + (PIPE == 6 ? 4 : 0)) * 64, (WM * WN
         const int m = mw0 + ig * 32 + row, n = nw0 + cc * EPC;
         const uint4 raw = *(const uint4*)(wbuf + (row < 32 ? row : 0) * RS + cc * 16);
         if (row >= grows) continue;
-        if (m < p.M && !(p.dbg & 128)) {
+        if (m < p.M) {
           if constexpr (EPI == EPI_RESID) {
             float4 x;
             x.x = xs[tt][0] + gs[tt][0] * __uint_as_float(raw.x); x.y = xs[tt][1] + gs[tt][1] * __uint_as_float(raw.y);
@@ -913,7 +886,6 @@ __global__ void __launch_bounds__((WM * WN + (PIPE == 6 ? 4 : 0)) * 64, (WM * WN
     constexpr int RS = TN * 32 + 16, CPR = TN * 2, NCH = 32 * CPR / 64;
     static_assert(NW * 32 * RS <= 2 * STAGE, "epilogue slab does not fit the staging buffers");
     __builtin_amdgcn_s_barrier();
-    if (p.dbg & 1) return;
     char* wbuf = smem + wave * (32 * RS);
     const int mw0 = m0 + wm * TM * 16;
     const int nqk = p.D + p.kvD;
@@ -974,7 +946,7 @@ __global__ void __launch_bounds__((WM * WN + (PIPE == 6 ? 4 : 0)) * 64, (WM * WN
             pk.y = (unsigned)*(const unsigned short*)(col + 2 * RS) | ((unsigned)*(const unsigned short*)(col + 3 * RS) << 16);
             pk.z = (unsigned)*(const unsigned short*)(col + 4 * RS) | ((unsigned)*(const unsigned short*)(col + 5 * RS) << 16);
             pk.w = (unsigned)*(const unsigned short*)(col + 6 * RS) | ((unsigned)*(const unsigned short*)(col + 7 * RS) << 16);
-            if (mg < p.M && !(p.dbg & 16)) {  // M % 8 == 0 on this path, so the 8 tokens are valid together
+            if (mg < p.M) {  // M % 8 == 0 on this path, so the 8 tokens are valid together
               const int b = mg / p.ntok, pos = mg - b * p.ntok, nv = nt + frow - nqk;
               *(uint4*)(p.vt_out + ((int64_t)(b * (p.kvD >> 6) + (nv >> 6)) * 64 + (nv & 63)) * p.npad + pos) = pk;
             }
@@ -1007,7 +979,6 @@ __global__ void __launch_bounds__((WM * WN + (PIPE == 6 ? 4 : 0)) * 64, (WM * WN
     static_assert(SV + 16384 <= 2 * STAGE, "operand images do not fit the staging buffers");
     __builtin_amdgcn_s_barrier();
     JAT_TL(3)
-    if (p.dbg & 64) { JAT_TL_FLUSH() return; }    // timing aid: K loop only
     // Column tiles of this wave (ctile): j < 5 the q tiles 5 wn + j, j = 5 its k tile, j = 6 its v tile (swapped operands).
     // RoPE angles: tile c covers the pair-interleaved features (16 c) % 64 ... of a head, i.e. frequencies 8 (c % 4) + 2 fg, +1;
     // c % 4 = (wn + j) % 4 for the q tiles and wn % 4 for the k tile: FOUR angle sets per row tile serve its six RoPE tiles
@@ -1061,7 +1032,6 @@ __global__ void __launch_bounds__((WM * WN + (PIPE == 6 ? 4 : 0)) * 64, (WM * WN
     JAT_TLX(0)
     __builtin_amdgcn_s_barrier();
     JAT_TLX(1)
-    if (p.dbg & 32) { JAT_TL_FLUSH() return; }    // timing aid: no attention phase
     const int q = wave * 16 + frow;                // this lane's query row (B-operand column)
     constexpr int G = 5;
     const int hbase = (n0 / 448) * G;
@@ -1166,7 +1136,6 @@ __global__ void __launch_bounds__((WM * WN + (PIPE == 6 ? 4 : 0)) * 64, (WM * WN
       const int nt = nw0 + j * 16;          // wave-uniform first column of this 16-wide MFMA tile
       const int n = nt + fg * 4;
       f32x4 v = acc[i][j] * rstd_d;
-      if ((p.dbg & 1) && v[0] != 12345.678f) continue;
       if constexpr (EPI == EPI_QKV_ROPE) {
         // Wq / Wk rows are packed pair-interleaved per head (position 2d <- feature d, 2d+1 <- feature d+32),
         // so the RoPE pair (d, d+32) (jat_audiosr_v3.py:87-108) sits in adjacent registers of one lane.
@@ -1732,7 +1701,6 @@ __global__ void __launch_bounds__(512, 1) gemm_kpair_kernel(const GemmArgs p) {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();                      // the exchange buffers are consumed: the slabs below may overwrite them
   JAT_TL(3)
-  if (p.dbg & 1) { JAT_TL_FLUSH() return; }
   // ---- split-residual epilogue (see gemm_bf16_kernel) on my half: row tiles [I0, I0 + NT) of the wave tile ---------------------
   constexpr int RS = TN * 64 + 16, CPR8 = TN * 2, NCH8 = TN;
   static_assert(NW * 32 * RS <= 3 * STAGE, "epilogue slabs fit the stages");
@@ -1814,10 +1782,14 @@ __global__ void __launch_bounds__(512, 1) gemm_kpair_kernel(const GemmArgs p) {
           ho[e] = (unsigned)ha | ((unsigned)hb << 16);
           const float ra = x[2 * e] - jat_op2f(ha), rb = x[2 * e + 1] - jat_op2f(hb);
           lw2[e] = jat_pack2(ra, rb);
-          sq += x[2 * e] * x[2 * e] + x[2 * e + 1] * x[2 * e + 1];
+          // spelled out (see gemm_bf16_kernel), as the contraction fell before: the split-residual form fuses x[2e+1]^2 after
+          // the first row group, every other form and group fuses x[2e]^2
+          const bool fuse_even = EPI != EPI_RESID || ig == 0;
+          sq += fuse_even ? __builtin_fmaf(x[2 * e], x[2 * e], x[2 * e + 1] * x[2 * e + 1])
+                          : __builtin_fmaf(x[2 * e + 1], x[2 * e + 1], x[2 * e] * x[2 * e]);
         }
         const bool live = row < grows;
-        if (live && !(p.dbg & 128)) {
+        if (live) {
           const unsigned off = (unsigned)(m * (int)p.ldo + n) * 2u;
           *(uint4*)((char*)p.fold_out + off) = uint4{ho[0], ho[1], ho[2], ho[3]};
           *(uint4*)((char*)p.fold_lo + off) = uint4{lw2[0], lw2[1], lw2[2], lw2[3]};
@@ -1870,7 +1842,7 @@ static hipError_t launch_kpair(const GemmArgs& a, hipStream_t s) {
 
 static bool gemm_persist_eligible(const GemmArgs& a, int epi) {
   return (epi == EPI_BF16 || epi == EPI_BF16_GELU) && a.M > 0 && a.M % 224 == 0 && a.N % 320 == 0 && a.K % 64 == 0 && a.ksplit <= 1 &&
-         a.dual_rows == 0 && !a.fold_out && (!a.rs_part || a.rs_np == 16) && a.ldo * 2 * 16 < (1ll << 31) && !(a.dbg & 129);
+         a.dual_rows == 0 && !a.fold_out && (!a.rs_part || a.rs_np == 16) && a.ldo * 2 * 16 < (1ll << 31);
 }
 template <int EPI>
 static hipError_t launch_persist(const GemmArgs& a, hipStream_t s) {

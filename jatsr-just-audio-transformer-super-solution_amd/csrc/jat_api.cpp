@@ -108,7 +108,7 @@ extern "C" int jat_model_create(const jat_config* c, jat_model** out) {
   auto env_int = [](const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; };
   m->sw.fuse_qkv_attn = env_int("JAT_FUSE_QKV_ATTN", 1); m->sw.qkv_split = env_int("JAT_QKV_SPLIT", 1);
   m->sw.fuse_finish = env_int("JAT_FUSE_FINISH", 1); m->sw.fold_norm = env_int("JAT_FOLD_NORM", 1);
-  m->sw.split_patch = env_int("JAT_SPLIT_PATCH", 1); m->sw.gemm_dbg = env_int("JAT_GEMM_DBG", 0);
+  m->sw.split_patch = env_int("JAT_SPLIT_PATCH", 1);
   m->sw.fold_cap_mb = env_int("JAT_FOLD_CAP_MB", 0); m->sw.patch_split = env_int("JAT_PATCH_SPLIT", 1);
   if (const char* v = getenv("JAT_GEMM_VARIANT"))
     for (int i = 0; i < 5; ++i) m->variants[i] = atoi(v);
@@ -125,7 +125,7 @@ extern "C" int jat_model_set_switch(jat_model* m, const char* name, int32_t valu
   if (!m || !name) return fail(JAT_E_INVALID, "null argument");
   const std::string n(name);
   int* slot = n == "fuse_qkv_attn" ? &m->sw.fuse_qkv_attn : n == "qkv_split" ? &m->sw.qkv_split : n == "fuse_finish" ? &m->sw.fuse_finish
-            : n == "fold_norm" ? &m->sw.fold_norm : n == "split_patch" ? &m->sw.split_patch : n == "gemm_dbg" ? &m->sw.gemm_dbg
+            : n == "fold_norm" ? &m->sw.fold_norm : n == "split_patch" ? &m->sw.split_patch
             : n == "fold_cap_mb" ? &m->sw.fold_cap_mb : n == "patch_split" ? &m->sw.patch_split : nullptr;
   if (!slot) return fail(JAT_E_INVALID, "unknown switch '%s'", name);
   *slot = value;
@@ -391,7 +391,6 @@ int jat_gemm(const jat_model* m, int site, const bf16_t* A, int64_t lda, const b
   if (N % kTileN(variant) != 0) variant = 20;  // 128 x 128, always valid
   if (a.fold_out) { a.fold_np = N / gemm_variant_wave_n(variant); m->last_fold_np = a.fold_np; }
   if (a.rs_part) a.rs_np = m->last_fold_np;
-  a.dbg = m->sw.gemm_dbg;   // profiling aid (0 in production)
   // measurement aid (bench.py roofline leg): bracket the launches of one call site with HIP events on the
   // launch stream.  Never active during graph capture (the bench enables it around eager forwards only).
   const bool timed = m->prof.site == site && m->prof.n < (int)m->prof.ev.size() / 2;
@@ -504,7 +503,6 @@ static int run_block(const jat_model* m, const Workspace& w, int l, int B, int n
     a.out = w.ao; a.ldo = D; a.ntok = ntok; a.rope_inv_freq = m->rope_invf;
     a.attn_scale_log2e = 0.125f * 1.4426950408889634f;
     if (f) { a.rs_part = w.part; a.rs_np = m->last_fold_np; a.bias = f->bq_g + (int64_t)l * Nqkv; }
-    a.dbg = m->sw.gemm_dbg;   // profiling aid (0 in production)
     KCHK(launch_qkv_attn(a, s));
   } else {
     GemmArgs e{};
@@ -1120,8 +1118,7 @@ extern "C" int jat_k_gemm(const uint16_t* A, const uint16_t* W, const float* bia
   a.A = A; a.W = W; a.lda = K; a.ldw = K; a.M = M; a.N = N; a.K = K;
   a.out = C; a.ldo = N; a.bias = bias; a.gate = gate; a.gate_bstride = gate_bstride;
   a.ntok = rows_per_batch > 0 ? rows_per_batch : 1;
-  if (const char* d = getenv("JAT_GEMM_DBG")) a.dbg = atoi(d);
-  if (const char* d = getenv("JAT_GEMM_TIMELINE")) a.dbg_out = (unsigned long long*)strtoull(d, nullptr, 0);  // tools/gemm_timeline.py
+  if (const char* d = getenv("JAT_GEMM_TIMELINE")) a.dbg_out = (unsigned long long*)strtoull(d, nullptr, 0);  // tools/tl_probe.py
   KCHK(launch_gemm(a, epilogue, variant, (hipStream_t)stream));
   return JAT_OK;
 }
@@ -1155,7 +1152,6 @@ extern "C" int jat_k_gemm_fold(const uint16_t* A, const uint16_t* W, const float
   a.fold_out = hi; a.fold_lo = lo; a.fold_part = part_out;
   if (hi) a.fold_np = N / gemm_variant_wave_n(variant);
   a.rs_part = part_in; a.rs_np = part_in_np;
-  if (const char* d = getenv("JAT_GEMM_DBG")) a.dbg = atoi(d);
   if (const char* d = getenv("JAT_GEMM_TIMELINE")) a.dbg_out = (unsigned long long*)strtoull(d, nullptr, 0);  // tools/tl_probe.py
   KCHK(launch_gemm(a, epilogue, variant, (hipStream_t)stream));
   return JAT_OK;
@@ -1170,7 +1166,6 @@ extern "C" int jat_k_qkv_attn(const uint16_t* A, const uint16_t* Wg, const float
   a.out = out; a.ldo = (int64_t)Hkv * 320; a.ntok = 128; a.rope_inv_freq = rope_inv_freq; a.bias = bias;
   a.attn_scale_log2e = 0.125f * 1.4426950408889634f;
   a.rs_part = part_in; a.rs_np = part_in_np;
-  if (const char* d = getenv("JAT_GEMM_DBG")) a.dbg = atoi(d);
   if (const char* d = getenv("JAT_GEMM_TIMELINE")) a.dbg_out = (unsigned long long*)strtoull(d, nullptr, 0);
   KCHK(launch_qkv_attn(a, (hipStream_t)stream));
   return JAT_OK;

@@ -39,7 +39,6 @@ struct GemmArgs {
   const float* rope_inv_freq;  // [32] fp32: 1/10000^(2i/64), for in-register sin/cos (coalesced epilogue)
   // EPI_UNPATCH
   int C_out, T_orig;
-  int dbg;  // profiling aid (bit0: suppress epilogue stores); 0 in production
   // ---- norm folding (sampler path; coalesced-epilogue variants only) ------------------------------------------
   // RMSNorm commutes with the matmul, and in the sampler every row shares the modulation (one t per step), so
   //   (x * rstd * w * (1 + scale) + shift) @ W^T  =  rstd[m] * (bf16(x) @ W'^T) + (shift @ W^T),   W' = W diag(w (1 + scale))
@@ -59,7 +58,7 @@ struct GemmArgs {
   // get gelu(acc + bias): the CFG cond / uncond halves share the z contribution of the first patch-embed Linear.
   const float* dual_add;
   int dual_rows;
-  unsigned long long* dbg_out;  // profiling aid (tools/gemm_timeline.py): per-wave cycle sums of the PIPE 6 slot phases
+  unsigned long long* dbg_out;  // -DJAT_TIMELINE build only (tools/tl_probe.py): per-wave whole-kernel s_memtime stamps
   // split-K (EPI_F32 only; the dW GEMMs of the training step whose M x N is too small to fill 256 CUs): grid.y = ksplit
   // blocks each contract K columns starting at blockIdx.y * K and write their partial to out + blockIdx.y * split_stride
   // (fp32 elements); the caller sums the partials in fixed order (launch_sum_partials).  0 / 1: off.

@@ -15,7 +15,6 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--shape", default="fc1", choices=["fc1", "fc2", "out", "qkvattn"])
 ap.add_argument("--variant", type=int, default=36)
 ap.add_argument("--M", type=int, default=7168)
-ap.add_argument("--dbg", type=int, default=0)
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 OP = torch.bfloat16
@@ -49,7 +48,6 @@ def run():
                                         L.ptr(lo), L.ptr(part_out), None, 0, a.variant, L.stream_ptr()))
 
 
-os.environ["JAT_GEMM_DBG"] = str(a.dbg)
 for _ in range(20):          # warm clocks and caches without the stamps' stores
     run()
 torch.cuda.synchronize()
@@ -64,7 +62,7 @@ seg = {"entry -> K loop start (prologue)": t[:, 1] - t[:, 0], "K loop": t[:, 2] 
        "epilogue": t[:, 4] - t[:, 3], "whole wave": t[:, 4] - t[:, 0]}
 real = (t[:, 6] - t[:, 5]) * 10.0       # ns
 clk = float(((t[:, 4] - t[:, 0]) / real).median())   # cycles per ns = GHz
-print(f"{a.shape} M={M} N={N} K={K} variant {a.variant} dbg={a.dbg}: {len(t)} waves of {nb} blocks, clock {clk:.2f} GHz")
+print(f"{a.shape} M={M} N={N} K={K} variant {a.variant}: {len(t)} waves of {nb} blocks, clock {clk:.2f} GHz")
 for k, v in seg.items():
     print(f"  {k:42s} median {float(v.median()):9.0f} cyc = {float(v.median()) / clk / 1e3:6.2f} us   (p10 {float(v.quantile(0.1)) / clk / 1e3:6.2f}, p90 {float(v.quantile(0.9)) / clk / 1e3:6.2f})")
 if epi == -1:
