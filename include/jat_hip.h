@@ -337,7 +337,8 @@ int jat_dac_workspace_bytes(const jat_dac_decoder* d, size_t* bytes);
 int jat_dac_decode(jat_dac_decoder* d, const float* z, float* audio, int32_t B, int32_t T, int32_t precision, void* stream);
 /* Per-kernel entry points (unit tests).  [host] fp32 torch-layout weight -> [N, taps, Cin] GEMM layout:
  * kind 0: Conv1d weight [cout, cin, k] (taps = k, N = cout); kind 1: ConvTranspose1d weight [cin, cout, 2 s] with
- * padding s / 2 (k_or_stride = s; polyphase, taps = 3, N = s * cout). */
+ * padding s / 2 (k_or_stride = s; polyphase, taps = 3, N = s * cout); kind 2: strided Conv1d weight [cout, cin, 2 s], stride s,
+ * padding s / 2, over super-rows of s input rows (taps = 3, N = cout, GEMM cin = s * cin; out [cout, 3, s * cin]). */
 int jat_dac_pack_weight(int32_t kind, const float* w, int32_t cin, int32_t cout, int32_t k_or_stride, float* out);
 /* fp32 -> bf16 planes hi = bf16(x), lo = bf16(x - hi) */
 int jat_k_dac_split(const float* x, uint16_t* hi, uint16_t* lo, int64_t n, void* stream);
@@ -353,6 +354,51 @@ int jat_k_dac_conv(const uint16_t* a_hi, const uint16_t* a_lo, const uint16_t* w
 /* Tail (modeling_dac.py:436-439): x fp32 [B*T, C] -> tanh(conv_k7(snake(x))) fp32 [B, 1, T]; w [7][C] (tap-major), C <= 96 */
 int jat_k_dac_tail(const float* x, const float* alpha, const float* w, const float* bias, float* out, int32_t B, int32_t T,
                    int32_t C, void* stream);
+
+/* ---- DAC 44.1 kHz encoder: audio [B, 1, T*512] -> latent z [B, 1024, T] + codes --------------------------------- */
+/* The reference encodes its training pairs with the Descript Audio Codec (prepare_dataset_v5.py:206-219,
+ * refine_dataset_lr_only.py:189-194: `z, _, _, _, _ = dac_model.encode(audio)`); the computation is transformers'
+ * DacEncoder.forward + DacResidualVectorQuantizer.forward in eval mode (models/dac/modeling_dac.py:103-173, 283-345,
+ * 444-475).  Convs in bf16 MFMA (JAT_DAC_* precision), the quantizer in fp32; the same bits in both operand-dtype builds. */
+typedef struct jat_dac_encoder jat_dac_encoder;
+#define JAT_DAC_MAX_CODEBOOKS 9
+typedef struct jat_dac_encoder_config {
+  int32_t channels;        /* DacConfig.encoder_hidden_size: 64 (a multiple of 32) */
+  int32_t hidden_size;     /* DacConfig.hidden_size: 1024 (the only size the quantizer kernel takes) */
+  int32_t n_blocks;        /* len(downsampling_ratios), 1..4; block i runs on channels << i */
+  int32_t strides[4];      /* downsampling_ratios: 2, 4, 8, 8 (even) */
+  int32_t n_codebooks;     /* 1..JAT_DAC_MAX_CODEBOOKS: 9 */
+  int32_t codebook_size;   /* 1024 */
+  int32_t codebook_dim;    /* 8 */
+} jat_dac_encoder_config;
+/* named: folded (plain `weight`) fp32 parameters under transformers' DacModel names: encoder.conv1.{weight,bias},
+ * encoder.block.{i}.res_unit{1,2,3}.{snake1.alpha,conv1.weight,conv1.bias,snake2.alpha,conv2.weight,conv2.bias},
+ * encoder.block.{i}.snake1.alpha, encoder.block.{i}.conv1.{weight,bias}, encoder.snake1.alpha, encoder.conv2.{weight,bias},
+ * quantizer.quantizers.{i}.{in_proj.weight,in_proj.bias,out_proj.weight,out_proj.bias,codebook.weight}.  A missing or
+ * mis-sized key fails with its name.  Device memory for batches up to max_B x max_T frames is allocated here. */
+int jat_dac_encoder_create(const jat_dac_encoder_config* cfg, const jat_tensor_ref* named, int32_t n, int32_t max_B,
+                           int32_t max_T, void* stream, jat_dac_encoder** out);
+void jat_dac_encoder_destroy(jat_dac_encoder* e);
+/* device bytes the handle holds (weights + activations for max_B x max_T) */
+int jat_dac_encoder_workspace_bytes(const jat_dac_encoder* e, size_t* bytes);
+/* audio fp32 [B, 1, T * prod(strides)] -> z fp32 [B, hidden, T] (sum of the first n_quantizers quantized codebooks),
+ * codes int32 [B, n_quantizers, T] (or null), latents fp32 [B, 8 n_quantizers, T] (in_proj outputs, or null), hidden fp32
+ * [B, hidden, T] (the encoder output before the quantizer, or null).  1 <= B <= max_B, 1 <= T <= max_T,
+ * 1 <= n_quantizers <= n_codebooks, precision JAT_DAC_* (convs only; the quantizer is fp32). */
+int jat_dac_encode(jat_dac_encoder* e, const float* audio, float* z, int32_t* codes, float* latents, float* hidden,
+                   int32_t B, int32_t T, int32_t n_quantizers, int32_t precision, void* stream);
+/* Encoder per-kernel entry points (unit tests); the strided convs run through jat_k_dac_conv (taps 3, dil 1, cin = s * Cin,
+ * T = output frames) with jat_dac_pack_weight kind 2.
+ * Head (modeling_dac.py:450): audio fp32 [B, L] -> conv1 = Conv1d(1, C, k7, pad 3) per sample; w [C, 1, 7]; out32 [B*L, C]
+ * and / or o_hi (+ o_lo, may be null) planes of snake_alpha(out); C a multiple of 32. */
+int jat_k_dac_head(const float* audio, const float* w, const float* bias, const float* alpha, float* out32, uint16_t* o_hi,
+                   uint16_t* o_lo, int32_t B, int32_t L, int32_t C, void* stream);
+/* Residual vector quantizer in fp32: hidden [B*T, 1024] channels-last; w_in [nq, 8, 1024], b_in [nq, 8], codebook
+ * [nq, 1024, 8] (un-normalized), w_out [nq, 1024, 8], b_out [nq, 1024]; outputs as jat_dac_encode (hidden_cm: hidden
+ * re-laid out as [B, 1024, T]).  hidden_size must be 1024. */
+int jat_k_dac_rvq(const float* hidden, const float* w_in, const float* b_in, const float* codebook, const float* w_out,
+                  const float* b_out, float* z, int32_t* codes, float* latents, float* hidden_cm, int32_t B, int32_t T,
+                  int32_t hidden_size, int32_t n_quantizers, void* stream);
 
 #ifdef __cplusplus
 }

@@ -36,6 +36,11 @@ class JatDacConfig(C.Structure):
                 ("strides", C.c_int32 * 4)]
 
 
+class JatDacEncoderConfig(C.Structure):
+    _fields_ = [("channels", C.c_int32), ("hidden_size", C.c_int32), ("n_blocks", C.c_int32), ("strides", C.c_int32 * 4),
+                ("n_codebooks", C.c_int32), ("codebook_size", C.c_int32), ("codebook_dim", C.c_int32)]
+
+
 class JatTensorRef(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("numel", C.c_int64)]
 
@@ -108,6 +113,12 @@ SIGNATURES = {
     "jat_k_dac_split": (C.c_int, [_VP, _VP, _VP, _I64, _VP]),
     "jat_k_dac_conv": (C.c_int, [_VP] * 10 + [_I32] * 8 + [_VP]),
     "jat_k_dac_tail": (C.c_int, [_VP] * 5 + [_I32] * 3 + [_VP]),
+    "jat_dac_encoder_create": (C.c_int, [C.c_void_p, C.POINTER(JatTensorRef), _I32, _I32, _I32, _VP, C.POINTER(_VP)]),
+    "jat_dac_encoder_destroy": (None, [_VP]),
+    "jat_dac_encoder_workspace_bytes": (C.c_int, [_VP, C.POINTER(_SZ)]),
+    "jat_dac_encode": (C.c_int, [_VP] * 6 + [_I32] * 4 + [_VP]),
+    "jat_k_dac_head": (C.c_int, [_VP] * 7 + [_I32] * 3 + [_VP]),
+    "jat_k_dac_rvq": (C.c_int, [_VP] * 10 + [_I32] * 4 + [_VP]),
 }
 
 GRAD_HOOK = C.CFUNCTYPE(None, C.c_int64, C.c_int64, C.c_void_p)   # jat_trainer_set_grad_hook callback

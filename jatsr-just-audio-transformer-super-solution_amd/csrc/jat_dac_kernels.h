@@ -23,3 +23,25 @@ hipError_t dac_launch_z_split(const float* z, uint16_t* hi, uint16_t* lo, int B,
 hipError_t dac_launch_split(const float* x, uint16_t* hi, uint16_t* lo, int64_t n, hipStream_t s);
 hipError_t dac_launch_tail(const float* x, const float* alpha, const float* w, const float* bias, float* out, int C, int T,
                            int64_t M, hipStream_t s);
+
+// Encoder (dac_enc.hip).  Head: conv1 = Conv1d(1, C, k7, pad 3) per sample on audio [B, L] (M = B * L rows); w torch
+// [C, 1, 7]; out32 [M, C] fp32 and/or o_hi/o_lo [M, C] planes of snake_alpha(out) (o_lo may be null: bf16 only).
+hipError_t dac_launch_head(const float* audio, const float* w, const float* bias, const float* alpha, float* out32,
+                           uint16_t* o_hi, uint16_t* o_lo, int C, int L, int64_t M, hipStream_t s);
+
+// Residual vector quantizer in fp32 (hidden size 1024, codebooks of 1024 x 8).
+struct DacRvqArgs {
+  const float* hidden;     // [M, 1024] channels-last (M = B * T)
+  const float* w_in;       // [nq, 8, 1024] in_proj weights
+  const float* b_in;       // [nq, 8]
+  const float* codebook;   // [nq, 1024, 8] un-normalized (normalized in LDS by the kernel)
+  const float* w_out;      // [nq, 1024, 8] out_proj weights
+  const float* b_out;      // [nq, 1024]
+  float* z;                // [B, 1024, T]
+  int32_t* codes;          // [B, nq, T] or null
+  float* latents;          // [B, 8 nq, T] in_proj outputs, or null
+  float* hidden_cm;        // [B, 1024, T] copy of hidden, or null
+  int64_t M;
+  int T, nq;
+};
+hipError_t dac_launch_rvq(const DacRvqArgs& p, hipStream_t s);

@@ -8,6 +8,8 @@ per-channel normalisation (:381-394).  Differences, all outside the hot path's s
     with `--dac-weights PATH` (a DAC 44.1 kHz weight file: there is no download) they are also decoded on the GPU
     (jatsr_amd.dac, csrc/dac.hip) and written as the reference's three 44.1 kHz WAV files (:408-437);
     `--dac-precision` picks bf16x3 (default, fp32-accurate) or bf16;
+  * `--input-audio PATH.wav` (44.1 kHz, with `--dac-weights`) starts from audio: the WAV is DAC-encoded on the GPU
+    (csrc/dac_enc.hip) and its latent is the LR input; there is no HR latent;
   * `--seed` makes the initial noise reproducible (the reference draws it with torch.randn, :133).
 
     python -m jatsr_amd.infer --checkpoint ckpt.pt --input-file clip.pt --stats-file stats.json --cfg-scale 3.0
@@ -43,20 +45,30 @@ def build_parser():
                    help="DAC 44.1 kHz weight file (.safetensors/.pt/.bin/.pth); decode to WAV when given")
     p.add_argument("--dac-precision", type=str, default="bf16x3", choices=["bf16x3", "bf16"],
                    help="DAC decoder arithmetic: bf16x3 (three-pass split, fp32-accurate) or bf16")
+    p.add_argument("--input-audio", type=str, default=None,
+                   help="44.1 kHz WAV to super-resolve: DAC-encoded on the GPU as the LR latent (needs --dac-weights; "
+                        "not with --input-file)")
     return p
 
 
 def run(args):
+    if args.input_audio and (args.input_file or not args.dac_weights):
+        raise SystemExit("--input-audio needs --dac-weights and cannot be combined with --input-file")
     device = torch.device(args.device)
     os.makedirs(args.output_dir, exist_ok=True)
     model = load_model(args.checkpoint, device=device, cls=JaT_AudioSR_V2 if args.layernorm else JaT_AudioSR_V3)
-    if args.input_file:
+    codec = None
+    if args.input_audio:
+        path = args.input_audio
+        codec, hr, lr = encode_audio(args, device)
+    elif args.input_file:
         path = args.input_file if os.path.exists(args.input_file) else os.path.join(args.val_dir, args.input_file)
         if not os.path.exists(path):
             raise FileNotFoundError(f"File not found: {path}")
     else:
         path = jio.first_latent_file(args.val_dir)
-    hr, lr = jio.load_latent_file(path)
+    if not args.input_audio:
+        hr, lr = jio.load_latent_file(path)
     C = model.input_channels
     stats = jio.load_stats(args.stats_file, channels=C, device=device)
 
@@ -86,14 +98,30 @@ def run(args):
                                    "frames": total, "seconds": dt})
     print(f"generated {gen.shape[-1]} frames in {dt:.2f} s -> {out_path}")
     if args.dac_weights:
-        decode_to_wav(args, gen, hr, lr, total, stem, suffix, device)
+        decode_to_wav(args, gen, hr, lr, total, stem, suffix, device, codec)
     return out_path
 
 
-def decode_to_wav(args, gen, hr, lr, total, stem, suffix, device):
+def encode_audio(args, device):
+    """--input-audio: the WAV's DAC latent (the reference's data preparation, prepare_dataset_v5.py:206-219) becomes the
+    LR latent; there is no HR latent.  -> (codec, None, lr fp32 [1024, T] on the CPU)."""
+    from .dac import load_dac_codec
+    x, sr = jio.read_wav(args.input_audio)
+    if sr != 44100:
+        raise SystemExit(f"{args.input_audio}: sample rate {sr} Hz; the DAC 44.1 kHz model needs 44100 Hz "
+                         "(resampling is not provided)")
+    codec = load_dac_codec(args.dac_weights, device=device, precision=args.dac_precision)
+    z = codec.encode(torch.from_numpy(x).to(device)[None, None])[0]
+    print(f"encoded {os.path.basename(args.input_audio)}: {x.shape[0]} samples -> {z.shape[-1]} frames "
+          f"(DAC {args.dac_precision})")
+    return codec, None, z[0].cpu()
+
+
+def decode_to_wav(args, gen, hr, lr, total, stem, suffix, device, codec=None):
     """DAC decode of the generated, HR and LR latents and the three WAV files of infer_test_v3m2.py:408-437."""
     from .dac import load_dac_codec
-    codec = load_dac_codec(args.dac_weights, device=device, precision=args.dac_precision)
+    if codec is None:
+        codec = load_dac_codec(args.dac_weights, device=device, precision=args.dac_precision)
     outs = [(f"{stem}_generated{suffix}.wav", gen[:1].float())]
     if hr is not None:
         outs.append((f"{stem}_hr_gt.wav", hr[None, :, :total].to(device)))

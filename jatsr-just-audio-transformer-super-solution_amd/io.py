@@ -102,3 +102,52 @@ def write_wav_float32(path, samples, sample_rate=44100):
         f.write(fact)
         f.write(struct.pack("<4sI", b"data", len(body)) + body)
     return path
+
+
+def read_wav(path):
+    """WAV file -> (float32 numpy [L], sample_rate).  Reads PCM 16 / 24 / 32-bit integer (format tag 1) and 32-bit IEEE
+    float (tag 3), also inside WAVE_FORMAT_EXTENSIBLE (tag 0xFFFE); integers are scaled by 2^-(bits-1).  Multi-channel
+    audio is averaged to mono, as the reference does (prepare_dataset_v5.py:130).  Stdlib + numpy only; a malformed or
+    unsupported file raises ValueError."""
+    import struct
+
+    import numpy as np
+    with open(path, "rb") as f:
+        raw = f.read()
+    if len(raw) < 12 or raw[:4] != b"RIFF" or raw[8:12] != b"WAVE":
+        raise ValueError(f"{path}: not a RIFF/WAVE file")
+    pos, fmt, data = 12, None, None
+    while pos + 8 <= len(raw):
+        cid, n = struct.unpack("<4sI", raw[pos:pos + 8])
+        body = raw[pos + 8:pos + 8 + n]
+        if len(body) < n:
+            raise ValueError(f"{path}: chunk {cid!r} is truncated")
+        if cid == b"fmt ":
+            if n < 16:
+                raise ValueError(f"{path}: fmt chunk of {n} bytes")
+            fmt = struct.unpack("<HHIIHH", body[:16])
+            if fmt[0] == 0xFFFE:
+                if n < 26:
+                    raise ValueError(f"{path}: WAVE_FORMAT_EXTENSIBLE fmt chunk of {n} bytes")
+                fmt = (struct.unpack("<H", body[24:26])[0],) + fmt[1:]   # the sub-format GUID's leading tag
+        elif cid == b"data":
+            data = body
+        pos += 8 + n + (n & 1)
+    if fmt is None or data is None:
+        raise ValueError(f"{path}: missing {'fmt' if fmt is None else 'data'} chunk")
+    tag, ch, sr, _, align, bits = fmt
+    if ch < 1 or sr < 1 or align != ch * bits // 8:
+        raise ValueError(f"{path}: inconsistent fmt chunk (channels {ch}, rate {sr}, block align {align}, bits {bits})")
+    usable = len(data) - len(data) % align
+    if tag == 3 and bits == 32:
+        x = np.frombuffer(data[:usable], "<f4").astype(np.float32)
+    elif tag == 1 and bits in (16, 32):
+        x = np.frombuffer(data[:usable], "<i2" if bits == 16 else "<i4").astype(np.float64) / 2.0 ** (bits - 1)
+    elif tag == 1 and bits == 24:
+        b = np.frombuffer(data[:usable], np.uint8).reshape(-1, 3).astype(np.int32)
+        v = b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)
+        x = (v - ((v & 0x800000) << 1)).astype(np.float64) / 2.0 ** 23
+    else:
+        raise ValueError(f"{path}: unsupported WAV format tag {tag} with {bits} bits")
+    x = x.reshape(-1, ch).mean(axis=1) if ch > 1 else x
+    return x.astype(np.float32), sr

@@ -250,3 +250,102 @@ def dac_flops(T: int, B: int = 1, latent_channels: int = 1024, channels: int = 1
         f += 3 * 2 * up * (7 * cout * cout + cout * cout)
     f += 2 * up * 7 * (channels >> len(strides))
     return int(f) * T * B
+
+
+# ---- DAC 44.1 kHz encoder + quantizer (transformers DacEncoder / DacResidualVectorQuantizer, modeling_dac.py:103-173,
+# 212-234, 283-345, 444-475) ---------------------------------------------------------------------------------------------
+DAC44K_ENC = {"channels": 64, "hidden_size": 1024, "strides": (2, 4, 8, 8), "n_codebooks": 9, "codebook_size": 1024,
+              "codebook_dim": 8}   # DacConfig(sampling_rate=44100): encoder_hidden_size, downsampling_ratios, ...
+
+
+def dac_encoder_param_shapes(channels: int = 64, hidden_size: int = 1024, strides=(2, 4, 8, 8), n_codebooks: int = 9,
+                             codebook_size: int = 1024, codebook_dim: int = 8) -> "OrderedDict[str, tuple]":
+    """Folded (plain `weight`) encoder and quantizer parameters under transformers' DacModel names, in registration
+    order."""
+    s: "OrderedDict[str, tuple]" = OrderedDict()
+    s["encoder.conv1.weight"] = (channels, 1, 7)
+    s["encoder.conv1.bias"] = (channels,)
+    for i, st in enumerate(strides):
+        c = channels << i
+        p = f"encoder.block.{i}."
+        for u in (1, 2, 3):
+            r = f"{p}res_unit{u}."
+            s[r + "snake1.alpha"] = (1, c, 1)
+            s[r + "conv1.weight"] = (c, c, 7)
+            s[r + "conv1.bias"] = (c,)
+            s[r + "snake2.alpha"] = (1, c, 1)
+            s[r + "conv2.weight"] = (c, c, 1)
+            s[r + "conv2.bias"] = (c,)
+        s[p + "snake1.alpha"] = (1, c, 1)
+        s[p + "conv1.weight"] = (2 * c, c, 2 * st)
+        s[p + "conv1.bias"] = (2 * c,)
+    cf = channels << len(strides)
+    s["encoder.snake1.alpha"] = (1, cf, 1)
+    s["encoder.conv2.weight"] = (hidden_size, cf, 3)
+    s["encoder.conv2.bias"] = (hidden_size,)
+    for i in range(n_codebooks):
+        q = f"quantizer.quantizers.{i}."
+        s[q + "in_proj.weight"] = (codebook_dim, hidden_size, 1)
+        s[q + "in_proj.bias"] = (codebook_dim,)
+        s[q + "out_proj.weight"] = (hidden_size, codebook_dim, 1)
+        s[q + "out_proj.bias"] = (hidden_size,)
+        s[q + "codebook.weight"] = (codebook_size, codebook_dim)
+    return s
+
+
+def make_dac_encoder_param(name: str, shape, salt: int = 0) -> np.ndarray:
+    """Conv weights uniform with std gain / sqrt(fan-in) (std 0.02 would shrink the signal ~10x per conv and leave the
+    snakes linear), gain 0.5 on the residual units' 1x1 convs so that the residual stream grows slowly; biases uniform
+    +-0.01; snake alphas over [0.5, 3] as for the decoder; codebook rows uniform with std 1."""
+    u = uniform("dac." + name, shape, salt)
+    if name.endswith(".alpha"):
+        return (np.float32(1.75) + np.float32(1.25) * u).astype(np.float32)
+    if name.endswith(".bias"):
+        return (u * np.float32(0.01)).astype(np.float32)
+    if name.endswith("codebook.weight"):
+        return (u * np.float32(np.sqrt(3.0))).astype(np.float32)
+    if name.endswith(".weight"):
+        fan_in = int(np.prod(shape[1:]))
+        gain = 0.5 if ".res_unit" in name and ".conv2." in name else 1.0
+        return (u * np.float32(gain * np.sqrt(3.0 / fan_in))).astype(np.float32)
+    raise KeyError(name)
+
+
+def make_dac_encoder_state_dict(salt: int = 0, threads: int = 8, **dims) -> "OrderedDict[str, np.ndarray]":
+    shapes = dac_encoder_param_shapes(**{**DAC44K_ENC, **dims})
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(max(1, threads)) as ex:
+        vals = list(ex.map(lambda kv: make_dac_encoder_param(kv[0], kv[1], salt), shapes.items()))
+    return OrderedDict(zip(shapes.keys(), vals))
+
+
+def make_dac_audio(B: int, L: int, salt: int = 0, sample_rate: int = 44100) -> np.ndarray:
+    """Recipe audio fp32 [B, 1, L]: per sample three tones (60 Hz - 6 kHz, different per sample) plus white noise and a
+    slow amplitude swell, scaled to peak 0.5."""
+    out = np.empty((B, 1, L), np.float32)
+    t = np.arange(L, dtype=np.float64) / sample_rate
+    for b in range(B):
+        u = uniform("dac_audio", (8,), salt * 1000 + b).astype(np.float64)
+        f = 60.0 * 100.0 ** ((u[:3] + 1) / 2)                    # log-uniform 60 Hz .. 6 kHz
+        ph = np.pi * u[3:6]
+        x = sum(a * np.sin(2 * np.pi * fi * t + p) for a, fi, p in zip((1.0, 0.6, 0.3), f, ph))
+        x = x * (1.2 + np.sin(2 * np.pi * (0.5 + u[6] + 1) * t))
+        x = x + (0.15 + 0.1 * u[7]) * gaussian("dac_audio_noise", (L,), salt * 1000 + b).astype(np.float64)
+        out[b, 0] = (0.5 * x / np.abs(x).max()).astype(np.float32)
+    return out
+
+
+def dac_encoder_flops(T: int, B: int = 1, n_quantizers: int = 9, channels: int = 64, hidden_size: int = 1024,
+                      strides=(2, 4, 8, 8), codebook_size: int = 1024, codebook_dim: int = 8, **_) -> int:
+    """Algorithmic FLOPs (2 x MAC) of one encode: convs 0.711 GFLOP and the quantizer 0.44 MFLOP per latent frame for the
+    44.1 kHz model (the strided convs count their 2s taps, not the 3s of the super-row GEMM)."""
+    rows = int(np.prod(strides))   # input rows per latent frame
+    f = 2 * rows * 7 * channels
+    for i, st in enumerate(strides):
+        c = channels << i
+        f += 3 * 2 * rows * (7 * c * c + c * c)
+        rows //= st
+        f += 2 * rows * 2 * st * c * 2 * c
+    f += 2 * rows * 3 * (channels << len(strides)) * hidden_size
+    f += n_quantizers * 2 * (hidden_size * codebook_dim + codebook_size * codebook_dim + codebook_dim * hidden_size)
+    return int(f) * T * B
