@@ -7,14 +7,20 @@ metric string is quoted on; it fits one GPU).  value = output latent frames per 
 N_gpus * B * T * steps / wall (weak scaling: every rank samples its own B=28 batch; the path has no
 data-path collective).  Inputs are resident in HBM before the timed region starts.
 
-Extra objects on the same JSON line:
+A plain run sets up, warms up, times the steps, writes --dump-outputs and prints the result line: nothing else.
+--full adds, on rank 0 after the timed steps, extra objects on the same JSON line (each a measurement of its own;
+together they take minutes):
+  forward      — single DiT forward (configs[1]) frames/s and its fraction of the bf16 MFMA peak.
+  single_chunk — B=1 sampler runs of one 1378- and one 512-frame chunk (one GPU; --no-single-chunk skips it).
+  long_sequence — one T=4096 file in chunks (configs[4]; one GPU; --no-long skips it).
   roofline     — the dominant kernel (MLP fc1 bf16 MFMA GEMM, M=2B*N_tok, N=5120, K=1280, GELU epilogue):
                  algorithmic FLOPs per launch / average launch duration measured live with HIP events.
+  train_step   — bf16 training steps (configs[3] dims) and the fp16 V2 trainer in a child process (one GPU; --no-train).
   cpu_baseline — the numpy oracle (port of the reference's fp32 CPU forward) timed on this host's cores on a
-                 bounded sample, converted to the same unit.
-  forward      — single DiT forward (configs[1]) frames/s and its fraction of the bf16 MFMA peak.
+                 bounded sample, converted to the same unit (one GPU; --no-cpu-baseline skips it).
 
-    python bench.py                                    # 1 GPU, defaults
+    python bench.py                                    # 1 GPU, defaults: the headline line only
+    python bench.py --full                             # + the legs above
     python bench.py --gpus 8 [--scaling strong]        # starts 8 ranks itself (torch.distributed.run child, one per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W          # the driver's own launch: used as is
@@ -210,6 +216,9 @@ def main():
     ap.add_argument("--dry-run", action="store_true", help="CPU/gloo rehearsal of the launcher and timing contract (tests)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (rank 0; <= 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the forward, single-chunk, long-sequence, roofline, training and "
+                         "CPU-baseline legs (rank 0; minutes); a plain run prints the headline line only")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
@@ -427,7 +436,7 @@ def main():
         "setup_s": setup_s,
     }
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # ---- single forward (BASELINE configs[1]): B=28, T=512, per-sample t ---------------------------
         x_t = torch.from_numpy(recipe.gaussian("x_t", (B, C_lat, T), 77)).to(dev)
         tvec = torch.linspace(0.02, 0.98, B, device=dev)
@@ -654,6 +663,7 @@ def main():
                 "forward_gflops": fwd_flops_B / c_s / 1e9,
                 "sampler_from_forward_rate": fwd_fps / per_run,
                 "reference_torch_cpu_survey": REFERENCE_TORCH_CPU_SURVEY}
+    if rank == 0:
         print(json.dumps(result))
     if dist is not None:
         dist.barrier()

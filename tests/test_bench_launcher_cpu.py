@@ -34,6 +34,12 @@ def test_bench_dry_run_single_rank():
     assert r["n_gpus"] == 1 and r["ranks_seen"] == 1
 
 
+def test_bench_full_option_keeps_the_contract():
+    """--full (the extra legs after the headline, GPU path only) is accepted and leaves the one-line timing contract as it is."""
+    r = _run(["--gpus", "2", "--full"])
+    assert r["n_gpus"] == 2 and r["ranks_seen"] == 2 and r["steps"] == 3 and r["warmup"] == 1 and r["value"] > 0
+
+
 @pytest.mark.parametrize("mode", ["train", "long"])
 def test_bench_launcher_other_modes_world2(mode):
     """`--mode train` (configs[3]: the gradient exchange of jatsr_amd.dist.exchange_sum_, slice by slice, summed right on both
