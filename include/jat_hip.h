@@ -400,6 +400,40 @@ int jat_k_dac_rvq(const float* hidden, const float* w_in, const float* b_in, con
                   const float* b_out, float* z, int32_t* codes, float* latents, float* hidden_cm, int32_t B, int32_t T,
                   int32_t hidden_size, int32_t n_quantizers, void* stream);
 
+/* ---- sample-rate converter: audio [B, L] -> [B, ceil(n L / o)] ------------------------------------------------ */
+/* The reference resamples its training audio with torchaudio (prepare_dataset_v5.py:198,203: AF.resample); the
+ * computation is torchaudio.functional.resample with resampling_method "sinc_interp_hann" (functional.py,
+ * _get_sinc_resample_kernel + _apply_sinc_resample_kernel).  With g = gcd(orig, new), o = orig / g, n = new / g,
+ * base = min(o, n) * rolloff, width = ceil(lowpass_filter_width * o / base) and K = 2 width + o taps per phase:
+ *   t       = clamp((-p / n + (k - width) / o) * base, -lpw, +lpw)                       p in [0, n), k in [0, K)
+ *   h[p][k] = (t == 0 ? 1 : sin(pi t) / (pi t)) * cos(pi t / lpw / 2)^2 * (base / o)     (fp64, stored as fp32)
+ *   y[f n + p] = sum_k h[p][k] * x[f o + k - width]   (x = 0 outside [0, L)),   L_out = ceil(n L / o)
+ * fp32 in both operand-dtype builds; every output is one ascending sum over k: the same bits from run to run and for
+ * a row alone or in a batch.  orig == new is a copy. */
+typedef struct jat_resampler jat_resampler;
+/* [host, no GPU needed] the dimensions and, when table is non-null, the tap table h as [n][K] fp32 [host].  o, n, width
+ * and K must be non-null.  Fails on orig or new_ < 1, lowpass_filter_width < 1, rolloff outside (0, 1], or a table of more
+ * than 2^26 entries (nearly coprime rates). */
+int jat_resample_table(int32_t orig, int32_t new_, int32_t lowpass_filter_width, double rolloff, float* table, int32_t* o,
+                       int32_t* n, int32_t* width, int32_t* K);
+/* Builds the table, uploads it on `stream` and waits for the upload; the same argument checks as the table call. */
+int jat_resampler_create(int32_t orig, int32_t new_, int32_t lowpass_filter_width, double rolloff, void* stream,
+                         jat_resampler** out);
+void jat_resampler_destroy(jat_resampler* r);
+/* [host] L_out = ceil(n L / o); fails when L_out or L + K does not fit in 31 bits. */
+int jat_resample_out_length(const jat_resampler* r, int64_t L, int64_t* L_out);
+/* x fp32 [B, L] -> y fp32 [B, L_out], both dense; 1 <= B <= 65535; L = 0 does nothing. */
+int jat_resample(jat_resampler* r, const float* x, float* y, int32_t B, int64_t L, void* stream);
+
+/* ---- per-channel latent statistics (prepare_dataset_v5.py:251-253, recalculate_stats.py:60-110) -------------------- */
+/* sum[c] += sum_{b,t} v, sq_sum[c] += sum_{b,t} v^2 with v = z[b, c, t] rounded to fp16 (what the latent files store), in
+ * fp64: z fp32 [B, C, T], sum and sq_sum fp64 [C] device buffers the caller owns and zeroes, so that many files fold into
+ * one running total.  Two stages (JAT_STATS_SLICES partial sums per channel in `work`, then one thread per channel adds
+ * them in order), no atomics: the same bits from run to run.  work: at least C * JAT_STATS_SLICES * 16 bytes. */
+#define JAT_STATS_SLICES 16
+int jat_channel_stats(const float* z, int32_t B, int32_t C, int32_t T, double* sum, double* sq_sum, void* work,
+                      size_t work_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

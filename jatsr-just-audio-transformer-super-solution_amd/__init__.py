@@ -16,6 +16,8 @@ _LAZY = {
     "sample_long": "sampler", "Sampler": "sampler", "channel_affine": "sampler",
     "load_latent_file": "io", "save_latent_file": "io", "load_stats": "io",
     "DacDecoder": "dac", "DacEncoder": "dac", "load_dac_codec": "dac",
+    "resample": "resample", "simulate_lr": "resample", "channel_stats": "resample",
+    "prepare_audio": "prepare", "chunk_bounds": "prepare",
     "Trainer": "train", "u_shaped_timestep_sampling": "train", "get_lr": "train", "GradScaler": "train",
 }
 __all__ = ["recipe"] + sorted(_LAZY)

@@ -119,6 +119,12 @@ SIGNATURES = {
     "jat_dac_encode": (C.c_int, [_VP] * 6 + [_I32] * 4 + [_VP]),
     "jat_k_dac_head": (C.c_int, [_VP] * 7 + [_I32] * 3 + [_VP]),
     "jat_k_dac_rvq": (C.c_int, [_VP] * 10 + [_I32] * 4 + [_VP]),
+    "jat_resample_table": (C.c_int, [_I32, _I32, _I32, C.c_double, _VP] + [C.POINTER(_I32)] * 4),
+    "jat_resampler_create": (C.c_int, [_I32, _I32, _I32, C.c_double, _VP, C.POINTER(_VP)]),
+    "jat_resampler_destroy": (None, [_VP]),
+    "jat_resample_out_length": (C.c_int, [_VP, _I64, C.POINTER(_I64)]),
+    "jat_resample": (C.c_int, [_VP, _VP, _VP, _I32, _I64, _VP]),
+    "jat_channel_stats": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _VP, _SZ, _VP]),
 }
 
 GRAD_HOOK = C.CFUNCTYPE(None, C.c_int64, C.c_int64, C.c_void_p)   # jat_trainer_set_grad_hook callback

@@ -48,12 +48,19 @@ def build_parser():
     p.add_argument("--input-audio", type=str, default=None,
                    help="44.1 kHz WAV to super-resolve: DAC-encoded on the GPU as the LR latent (needs --dac-weights; "
                         "not with --input-file)")
+    p.add_argument("--resample", action="store_true",
+                   help="with --input-audio: convert a WAV of any sample rate to 44.1 kHz on the GPU before the encode")
+    p.add_argument("--simulate-lr", type=int, nargs="?", const=16000, default=None, metavar="LOW_SR",
+                   help="with --input-audio: the WAV is the HR recording; its LR latent (through LOW_SR, default 16000) "
+                        "is the sampler's input, made as the training data is (implies --resample)")
     return p
 
 
 def run(args):
     if args.input_audio and (args.input_file or not args.dac_weights):
         raise SystemExit("--input-audio needs --dac-weights and cannot be combined with --input-file")
+    if (args.resample or args.simulate_lr is not None) and not args.input_audio:
+        raise SystemExit("--resample and --simulate-lr need --input-audio")
     device = torch.device(args.device)
     os.makedirs(args.output_dir, exist_ok=True)
     model = load_model(args.checkpoint, device=device, cls=JaT_AudioSR_V2 if args.layernorm else JaT_AudioSR_V3)
@@ -104,14 +111,30 @@ def run(args):
 
 def encode_audio(args, device):
     """--input-audio: the WAV's DAC latent (the reference's data preparation, prepare_dataset_v5.py:206-219) becomes the
-    LR latent; there is no HR latent.  -> (codec, None, lr fp32 [1024, T] on the CPU)."""
+    LR latent; there is no HR latent.  -> (codec, None, lr fp32 [1024, T] on the CPU).  With --resample a WAV of another
+    rate is converted to 44.1 kHz first; with --simulate-lr the WAV is the HR recording and both latents come from
+    prepare_audio -> (codec, hr, lr)."""
     from .dac import load_dac_codec
     x, sr = jio.read_wav(args.input_audio)
-    if sr != 44100:
+    if args.simulate_lr is not None:
+        from .prepare import prepare_audio
+        codec = load_dac_codec(args.dac_weights, device=device, precision=args.dac_precision)
+        res = prepare_audio(x, sr, codec, low_sr=args.simulate_lr, device=device)
+        if res is None:
+            raise SystemExit(f"{args.input_audio}: shorter than 1 s")
+        print(f"prepared {os.path.basename(args.input_audio)}: {x.shape[0]} samples at {sr} Hz -> {res['count']} frames "
+              f"(HR and LR through {args.simulate_lr} Hz, DAC {args.dac_precision})")
+        return codec, res["hr_latent"].cpu(), res["lr_latent"].cpu()
+    if sr != 44100 and not args.resample:
         raise SystemExit(f"{args.input_audio}: sample rate {sr} Hz; the DAC 44.1 kHz model needs 44100 Hz "
-                         "(resampling is not provided)")
+                         "(resampling is not provided unless --resample is given)")
     codec = load_dac_codec(args.dac_weights, device=device, precision=args.dac_precision)
-    z = codec.encode(torch.from_numpy(x).to(device)[None, None])[0]
+    audio = torch.from_numpy(x).to(device)[None]
+    if sr != 44100:
+        from .resample import resample
+        audio = resample(audio, sr, 44100)
+        print(f"resampled {os.path.basename(args.input_audio)}: {sr} Hz -> 44100 Hz, {audio.shape[-1]} samples")
+    z = codec.encode(audio[None])[0]
     print(f"encoded {os.path.basename(args.input_audio)}: {x.shape[0]} samples -> {z.shape[-1]} frames "
           f"(DAC {args.dac_precision})")
     return codec, None, z[0].cpu()

@@ -1,0 +1,238 @@
+"""Audio -> HR / LR latent pairs and per-channel statistics: the MI355X counterpart of the reference's data preparation
+(prepare_dataset_v5.py:120-264) and of its separated statistics (recalculate_stats.py:103-124).
+
+Per file, in the reference's order: mono, divided by its peak only where the peak exceeds 1 (:130-132); 8 s chunks = 7 s valid
+plus 0.5 s on each side (:143-168); resample to 48 kHz (:198); LR simulation 48 -> 16 -> 48 kHz (:203-205); both to
+44.1 kHz and through the DAC encoder (:207-219); the overlap frames trimmed (:221-232); concatenated and cut to the file's
+frame count (:239-245); per-channel sum and sum of squares in fp64 (:251-253).  All arithmetic on audio and latents runs on
+the GPU (csrc/resample.hip, csrc/dac_enc.hip).  Differences:
+  * one process on one GPU (no worker pool, no file sharding); WAV files only;
+  * the 48 -> 44.1 kHz step is the same windowed-sinc kernel with width 24 / rolloff 0.945, a same-family approximation of
+    the reference's audiotools (julius) call there;
+  * the statistics are kept separately for HR and LR (2048 channels: HR first, then LR), over the fp16-rounded values that
+    the latent files hold;
+  * the encoder runs in the codec's precision (bf16x3 by default), not under fp16 autocast;
+  * consecutive chunks are batched only where their lengths are equal (the reference pads a batch to its first chunk).
+
+    python -m jatsr_amd.prepare --source-dir wavs --output-dir data --dac-weights dac.pth
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import math
+import os
+import random
+
+HIGH_SR = 48000
+CHUNK_SECONDS, OVERLAP_SECONDS, MIN_SECONDS = 7.0, 0.5, 1.0
+
+
+def chunk_bounds(total_samples: int, sr: int, chunk: float = CHUNK_SECONDS, overlap: float = OVERLAP_SECONDS):
+    """The reference's chunk list (prepare_dataset_v5.py:143-168) with its int() truncations:
+    [(idx_start, idx_end, pad_left, pad_right)]; [] for a file shorter than 1 s (:137-139).  Pure host code."""
+    duration = total_samples / sr
+    if duration < MIN_SECONDS:
+        return []
+    out = []
+    for i in range(math.ceil(duration / chunk)):
+        t_start = i * chunk - overlap
+        t_end = t_start + chunk + (2 * overlap)
+        a, b = int(t_start * sr), int(t_end * sr)
+        pad_left = pad_right = 0
+        if a < 0:
+            pad_left, a = -a, 0
+        if b > total_samples:
+            pad_right, b = b - total_samples, total_samples
+        out.append((a, b, pad_left, pad_right))
+    return out
+
+
+class _Clock:
+    """Device-event brackets of the three stages, only when the caller asks for timings."""
+
+    def __init__(self, sink):
+        self.sink = sink
+
+    def run(self, name, fn):
+        if self.sink is None:
+            return fn()
+        import torch
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        e1.synchronize()
+        self.sink[name] = self.sink.get(name, 0.0) + e0.elapsed_time(e1)
+        return out
+
+
+def to_codec_rate(x, codec):
+    """48 kHz audio -> the codec's 44.1 kHz (the `signal.resample(dac_model.sample_rate)` of prepare_dataset_v5.py:211)."""
+    from .resample import CODEC_LOWPASS_WIDTH, CODEC_ROLLOFF, resample
+    return resample(x, HIGH_SR, codec.sample_rate, CODEC_LOWPASS_WIDTH, CODEC_ROLLOFF)
+
+
+def prepare_audio(audio, sr: int, codec, low_sr: int = 16000, batch: int = 8, device="cuda", timings: dict | None = None):
+    """One recording -> dict(hr_latent fp32 [1024, T], lr_latent, sum fp64 [2048], sq_sum, count, metadata), tensors on the
+    GPU; None for a recording shorter than 1 s.  `audio`: [L] or [channels, L], array or tensor; `codec`: a DacCodec with an
+    encoder.  sum / sq_sum: HR channels first, then LR, over the values rounded to fp16; count: T (frames of each)."""
+    import torch
+
+    from . import _lib as L
+    from .resample import channel_stats, resample, simulate_lr
+    L.require_gpu()
+    if int(sr) != sr or sr < 1 or int(low_sr) != low_sr or low_sr < 1:
+        raise ValueError(f"prepare_audio: sample rates must be positive integers, got {sr!r}, {low_sr!r}")
+    if batch < 1:
+        raise ValueError(f"prepare_audio: batch {batch} must be >= 1")
+    sr, low_sr = int(sr), int(low_sr)
+    x = torch.as_tensor(audio)
+    if not x.is_cuda:
+        x = x.to(device)
+    x = x.to(torch.float32)
+    if x.dim() == 2:
+        x = x.mean(dim=0)                                   # :130
+    if x.dim() != 1:
+        raise ValueError(f"prepare_audio: audio must be [L] or [channels, L], got {tuple(x.shape)}")
+    total = x.shape[0]
+    duration = total / sr
+    bounds = chunk_bounds(total, sr)
+    if not bounds:
+        return None
+    peak = float(x.abs().max())
+    if peak > 1.0:                                          # :131-132
+        x = x / peak
+    chunks = [torch.nn.functional.pad(x[a:b], (pl, pr)) if pl or pr else x[a:b] for a, b, pl, pr in bounds]
+    clock = _Clock(timings)
+    hr_parts, lr_parts = [], []
+    hop48 = trim = valid = None
+    i = 0
+    while i < len(chunks):
+        j = i + 1
+        while j < len(chunks) and j - i < batch and chunks[j].shape[0] == chunks[i].shape[0]:
+            j += 1
+        raw = torch.stack(chunks[i:j])
+        i = j
+
+        def both(raw=raw):
+            hr = resample(raw, sr, HIGH_SR) if sr != HIGH_SR else raw                    # :197-200
+            lr = simulate_lr(hr, HIGH_SR, low_sr)                                         # :203-205
+            return hr, to_codec_rate(hr, codec), to_codec_rate(lr, codec)
+        hr48, hr44, lr44 = clock.run("resample", both)
+        z_hr, z_lr = clock.run("encode", lambda: (codec.encode(hr44[:, None])[0], codec.encode(lr44[:, None])[0]))
+        if hop48 is None:                                                                 # :222-227
+            hop48 = hr48.shape[-1] / z_hr.shape[-1]
+            trim = int(int(OVERLAP_SECONDS * HIGH_SR) / hop48)
+            valid = int(int(CHUNK_SECONDS * HIGH_SR) / hop48)
+        hr_parts.extend(z_hr[..., trim:trim + valid])                                     # :230-235
+        lr_parts.extend(z_lr[..., trim:trim + valid])
+    frames = int(int(duration * HIGH_SR) / hop48)                                         # :242-245
+    hr = torch.cat(hr_parts, dim=-1)[..., :frames].contiguous()
+    lr = torch.cat(lr_parts, dim=-1)[..., :frames].contiguous()
+    C = hr.shape[0]
+    s = torch.zeros(2 * C, dtype=torch.float64, device=hr.device)
+    q = torch.zeros(2 * C, dtype=torch.float64, device=hr.device)
+
+    def stats():
+        channel_stats(hr, s[:C], q[:C])
+        channel_stats(lr, s[C:], q[C:])
+    clock.run("stats", stats)
+    return {"hr_latent": hr, "lr_latent": lr, "sum": s, "sq_sum": q, "count": hr.shape[-1],
+            "metadata": {"duration": duration, "sr": sr, "chunks": len(chunks), "frames": hr.shape[-1],
+                         "hop_48k": hop48, "trim_frames": trim, "valid_frames": valid}}
+
+
+def final_stats(sum_, sq_sum, count, channels: int = 1024) -> dict:
+    """Running totals (HR first, then LR) -> hr_mean / hr_std / lr_mean / lr_std lists with std = sqrt(clamp(var, 1e-6))
+    (recalculate_stats.py:103-121)."""
+    import torch
+    mean = sum_.double().cpu() / float(count)
+    var = sq_sum.double().cpu() / float(count) - mean ** 2
+    std = torch.sqrt(torch.clamp(var, min=1e-6))
+    return {"hr_mean": mean[:channels].float().tolist(), "hr_std": std[:channels].float().tolist(),
+            "lr_mean": mean[channels:].float().tolist(), "lr_std": std[channels:].float().tolist(),
+            "hr_total_frames": int(count), "lr_total_frames": int(count),
+            "note": "HR and LR statistics are separated"}
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description="WAV folders -> HR/LR DAC latent pairs and normalisation statistics on MI355X")
+    p.add_argument("--source-dir", action="append", required=True, help="folder of *.wav files (searched recursively); repeatable")
+    p.add_argument("--output-dir", required=True, help="receives train/, val/, running_stats.pt, global_stats_separated.json")
+    p.add_argument("--dac-weights", required=True, help="DAC 44.1 kHz weight file with encoder and quantizer weights")
+    p.add_argument("--val-fraction", type=float, default=0.05, help="share of the files that goes to val/")
+    p.add_argument("--seed", type=int, default=42, help="seed of the train / val shuffle")
+    p.add_argument("--low-sr", type=int, default=16000, help="sample rate of the simulated low-resolution audio")
+    p.add_argument("--dac-precision", default="bf16x3", choices=["bf16x3", "bf16"], help="DAC encoder arithmetic")
+    p.add_argument("--batch", type=int, default=8, help="chunks per resampler / encoder call")
+    p.add_argument("--device", default="cuda", help="an AMD GPU; there is no CPU path")
+    return p
+
+
+def find_wavs(dirs):
+    files = []
+    for d in dirs:
+        for dp, _, names in sorted(os.walk(d)):
+            files.extend(os.path.join(dp, f) for f in sorted(names) if f.lower().endswith(".wav"))
+    return files
+
+
+def run(args):
+    import torch
+
+    from . import io as jio
+    from .dac import load_dac_codec
+    files = find_wavs(args.source_dir)
+    random.Random(args.seed).shuffle(files)                 # :301-305
+    split = int(len(files) * (1 - args.val_fraction))
+    tasks = [(f, "train") for f in files[:split]] + [(f, "val") for f in files[split:]]
+    for sub in ("train", "val"):
+        os.makedirs(os.path.join(args.output_dir, sub), exist_ok=True)
+    stats_path = os.path.join(args.output_dir, "running_stats.pt")
+    if os.path.exists(stats_path):
+        st = torch.load(stats_path, map_location="cpu", weights_only=False)
+        total_sum, total_sq, total_count = st["sum"].double(), st["sq_sum"].double(), int(st["count"])
+    else:
+        total_sum = total_sq = None
+        total_count = 0
+    codec = None
+    report = {"written": [], "skipped": [], "existing": []}
+    for path, sub in tasks:
+        stem = os.path.splitext(os.path.basename(path))[0]
+        out_path = os.path.join(args.output_dir, sub, f"{stem}.pt")
+        # a file added to the sources later can move others across the split: what either folder holds already stays there
+        if any(os.path.exists(os.path.join(args.output_dir, d, f"{stem}.pt")) for d in ("train", "val")):
+            report["existing"].append(path)
+            continue
+        if codec is None:
+            codec = load_dac_codec(args.dac_weights, device=args.device, precision=args.dac_precision)
+        x, sr = jio.read_wav(path)
+        res = prepare_audio(x, sr, codec, low_sr=args.low_sr, batch=args.batch, device=args.device)
+        if res is None:
+            print(f"skipped {path}: shorter than {MIN_SECONDS:g} s")
+            report["skipped"].append(path)
+            continue
+        jio.save_latent_file(out_path, hr_latent=res["hr_latent"], lr_latent=res["lr_latent"],
+                             metadata={"name": stem, "path": path, "duration": res["metadata"]["duration"], "sr": sr})
+        s, q = res["sum"].cpu(), res["sq_sum"].cpu()
+        total_sum = s if total_sum is None else total_sum + s
+        total_sq = q if total_sq is None else total_sq + q
+        total_count += res["count"]
+        torch.save({"sum": total_sum, "sq_sum": total_sq, "count": total_count}, stats_path)
+        report["written"].append(out_path)
+        print(f"{path} -> {out_path}: {res['count']} frames")
+    if total_count > 0:
+        with open(os.path.join(args.output_dir, "global_stats_separated.json"), "w") as f:
+            json.dump(final_stats(total_sum, total_sq, total_count, total_sum.numel() // 2), f, indent=4)
+    print(f"prepared {len(report['written'])} file(s), skipped {len(report['skipped'])}, "
+          f"{len(report['existing'])} already present; {total_count} frames in the statistics")
+    return report
+
+
+def main(argv=None):
+    return run(build_parser().parse_args(argv))
+
+
+if __name__ == "__main__":
+    main()
