@@ -434,6 +434,40 @@ int jat_resample(jat_resampler* r, const float* x, float* y, int32_t B, int64_t 
 int jat_channel_stats(const float* z, int32_t B, int32_t C, int32_t T, double* sum, double* sq_sum, void* work,
                       size_t work_bytes, void* stream);
 
+/* ---- audio-quality metrics: log-spectral distance and mel-spectrogram losses -------------------------------------- */
+/* What the reference's calculate_metrics.py computes with librosa >= 0.10, on mono fp32 audio [B, L] pairs (pred, gt):
+ *   STFT   periodic Hann w[i] = 0.5 - 0.5 cos(2 pi i / n_fft), win_length = n_fft, center=True with n_fft / 2 zeros a side,
+ *          frames = 1 + L / hop, bins = 1 + n_fft / 2,  X[k, f] = sum_i w[i] x_pad[f hop + i] e^{-2 pi i k i / n_fft}
+ *   LSD    d = log10 max(|X_pred|, 1e-8) - log10 max(|X_gt|, 1e-8),  lsd_frames[f] = sqrt(mean_k d[k, f]^2),
+ *          lsd_db = 20 mean_f lsd_frames[f]                                                  (calculate_metrics.py:23-62)
+ *   mel    S = M |X|^2, M = librosa.filters.mel (Slaney scale, fmin 0, fmax sr / 2, norm "slaney"),
+ *          dB = max(10 log10 max(1e-10, S) - 10 log10 max(1e-10, max S), -80), the maximum over one signal's whole
+ *          spectrogram;  mel_l1 = mean |a - b|,  mel_l2 = sqrt(mean (a - b)^2)                              (:64-101)
+ * One pass transforms pred + i gt per frame in LDS and reduces in place (no spectrogram reaches memory), a second sums in
+ * fp64.  fp32 in both operand-dtype builds, no atomics: the same bits from run to run and for a row alone or in a batch. */
+typedef struct jat_audio_metrics jat_audio_metrics;
+/* [host, no GPU needed] the filterbank as [n_mels][1 + n_fft / 2] fp32 (computed in fp64), when out is non-null.  Fails on
+ * sr < 1, n_fft not a power of two in 64..4096, n_mels < 0 or above the bin count. */
+int jat_mel_filterbank(int32_t sr, int32_t n_fft, int32_t n_mels, float* out);
+/* [host] frames = 1 + L / hop; fails on L < 1 or hop < 1 */
+int jat_stft_frames(int64_t L, int32_t hop, int64_t* frames);
+/* Builds window, twiddles and the sparse filterbank, uploads them on `stream` and waits.  n_mels = 0: no mel bands (STFT
+ * and LSD only).  The same argument checks as jat_mel_filterbank, and hop >= 1. */
+int jat_audio_metrics_create(int32_t sr, int32_t n_fft, int32_t hop, int32_t n_mels, void* stream, jat_audio_metrics** out);
+void jat_audio_metrics_destroy(jat_audio_metrics* h);
+/* Device bytes jat_audio_metrics_run needs for B rows of L samples.  Fails on L < 1, B outside 1..65535, or frames * bins
+ * or L + n_fft beyond 31 bits. */
+int jat_audio_metrics_workspace_bytes(const jat_audio_metrics* h, int32_t B, int64_t L, size_t* bytes);
+/* pred, gt fp32 [B, L] (device) -> out fp64 [B, 3] (device): lsd_db (0 unless want_lsd), mel_l1, mel_l2 (0 when the handle
+ * has no mel bands).  Optional device outputs: lsd_frames fp32 [B, frames] (needs want_lsd); pred_db and gt_db fp32
+ * [B, n_mels, frames] (both or neither).  JAT_E_STATE when work_bytes is below jat_audio_metrics_workspace_bytes. */
+int jat_audio_metrics_run(jat_audio_metrics* h, const float* pred, const float* gt, int32_t B, int64_t L, int32_t want_lsd,
+                          double* out, float* lsd_frames, float* pred_db, float* gt_db, void* work, size_t work_bytes,
+                          void* stream);
+/* The transform alone, through the same kernel: x fp32 [B, L] -> X complex64 [B, bins, frames].  With y (and Y) a second
+ * signal rides in the imaginary part of the same transforms; y and Y are null together. */
+int jat_stft(jat_audio_metrics* h, const float* x, const float* y, int32_t B, int64_t L, void* X, void* Y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

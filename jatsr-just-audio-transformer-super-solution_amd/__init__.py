@@ -18,6 +18,8 @@ _LAZY = {
     "DacDecoder": "dac", "DacEncoder": "dac", "load_dac_codec": "dac",
     "resample": "resample", "simulate_lr": "resample", "channel_stats": "resample",
     "prepare_audio": "prepare", "chunk_bounds": "prepare",
+    "stft": "metrics", "mel_filterbank": "metrics", "calculate_lsd": "metrics", "calculate_mel_loss": "metrics",
+    "calculate_multi_scale_mel_loss": "metrics", "evaluate": "metrics", "load_audio": "metrics",
     "Trainer": "train", "u_shaped_timestep_sampling": "train", "get_lr": "train", "GradScaler": "train",
 }
 __all__ = ["recipe"] + sorted(_LAZY)

@@ -125,6 +125,13 @@ SIGNATURES = {
     "jat_resample_out_length": (C.c_int, [_VP, _I64, C.POINTER(_I64)]),
     "jat_resample": (C.c_int, [_VP, _VP, _VP, _I32, _I64, _VP]),
     "jat_channel_stats": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _VP, _SZ, _VP]),
+    "jat_mel_filterbank": (C.c_int, [_I32, _I32, _I32, _VP]),
+    "jat_stft_frames": (C.c_int, [_I64, _I32, C.POINTER(_I64)]),
+    "jat_audio_metrics_create": (C.c_int, [_I32, _I32, _I32, _I32, _VP, C.POINTER(_VP)]),
+    "jat_audio_metrics_destroy": (None, [_VP]),
+    "jat_audio_metrics_workspace_bytes": (C.c_int, [_VP, _I32, _I64, C.POINTER(_SZ)]),
+    "jat_audio_metrics_run": (C.c_int, [_VP, _VP, _VP, _I32, _I64, _I32, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "jat_stft": (C.c_int, [_VP, _VP, _VP, _I32, _I64, _VP, _VP, _VP]),
 }
 
 GRAD_HOOK = C.CFUNCTYPE(None, C.c_int64, C.c_int64, C.c_void_p)   # jat_trainer_set_grad_hook callback

@@ -10,7 +10,10 @@ per-channel normalisation (:381-394).  Differences, all outside the hot path's s
     `--dac-precision` picks bf16x3 (default, fp32-accurate) or bf16;
   * `--input-audio PATH.wav` (44.1 kHz, with `--dac-weights`) starts from audio: the WAV is DAC-encoded on the GPU
     (csrc/dac_enc.hip) and its latent is the LR input; there is no HR latent;
-  * `--seed` makes the initial noise reproducible (the reference draws it with torch.randn, :133).
+  * `--seed` makes the initial noise reproducible (the reference draws it with torch.randn, :133);
+  * `--metrics` (with `--dac-weights`, where an HR ground truth exists: `--simulate-lr`, or a latent file with `hr_latent`)
+    evaluates the decoded generated / HR / LR audio as the reference's calculate_metrics.py does (jatsr_amd.metrics) and
+    writes `{stem}_metrics.json` (with the `_cfgX` suffix of the generated files, if any) next to the WAVs.
 
     python -m jatsr_amd.infer --checkpoint ckpt.pt --input-file clip.pt --stats-file stats.json --cfg-scale 3.0
 """
@@ -53,6 +56,9 @@ def build_parser():
     p.add_argument("--simulate-lr", type=int, nargs="?", const=16000, default=None, metavar="LOW_SR",
                    help="with --input-audio: the WAV is the HR recording; its LR latent (through LOW_SR, default 16000) "
                         "is the sampler's input, made as the training data is (implies --resample)")
+    p.add_argument("--metrics", action="store_true",
+                   help="LSD and mel losses of the decoded generated and LR audio against the HR ground truth, written as "
+                        "{stem}_metrics.json (needs --dac-weights and a ground truth: --simulate-lr or a latent file with hr_latent)")
     return p
 
 
@@ -61,6 +67,8 @@ def run(args):
         raise SystemExit("--input-audio needs --dac-weights and cannot be combined with --input-file")
     if (args.resample or args.simulate_lr is not None) and not args.input_audio:
         raise SystemExit("--resample and --simulate-lr need --input-audio")
+    if args.metrics and (not args.dac_weights or (args.input_audio and args.simulate_lr is None)):
+        raise SystemExit("--metrics needs --dac-weights and an HR ground truth (--simulate-lr, or a latent file with hr_latent)")
     device = torch.device(args.device)
     os.makedirs(args.output_dir, exist_ok=True)
     model = load_model(args.checkpoint, device=device, cls=JaT_AudioSR_V2 if args.layernorm else JaT_AudioSR_V3)
@@ -76,6 +84,8 @@ def run(args):
         path = jio.first_latent_file(args.val_dir)
     if not args.input_audio:
         hr, lr = jio.load_latent_file(path)
+    if args.metrics and hr is None:
+        raise SystemExit(f"--metrics: {path} holds no hr_latent, so there is no ground truth to compare with")
     C = model.input_channels
     stats = jio.load_stats(args.stats_file, channels=C, device=device)
 
@@ -149,10 +159,24 @@ def decode_to_wav(args, gen, hr, lr, total, stem, suffix, device, codec=None):
     if hr is not None:
         outs.append((f"{stem}_hr_gt.wav", hr[None, :, :total].to(device)))
     outs.append((f"{stem}_lr_input.wav", lr[None, :, :total].to(device)))
+    decoded = []
     for name, z in outs:
         audio = codec.decode(z)                      # [1, 1, frames * 512]
         jio.write_wav_float32(os.path.join(args.output_dir, name), audio[0, 0], codec.sample_rate)
+        if args.metrics:
+            decoded.append(audio[0, 0].float().contiguous())
     print(f"decoded {len(outs)} latents with DAC ({args.dac_precision}) -> {[n for n, _ in outs]}")
+    if args.metrics:
+        import json
+
+        from . import metrics
+        generated, hr_gt, lr_input = decoded
+        rep = metrics.evaluate(generated, hr_gt, lr_input, sr=codec.sample_rate)
+        print(metrics.format_report(rep))
+        out = os.path.join(args.output_dir, f"{stem}_metrics{suffix}.json")
+        with open(out, "w") as f:
+            json.dump(rep, f, indent=2)
+        print(f"metrics -> {out}")
 
 
 def main(argv=None):

@@ -81,20 +81,27 @@ def first_latent_file(val_dir):
 
 
 def write_wav_float32(path, samples, sample_rate=44100):
-    """Mono 32-bit IEEE-float WAV (format tag 3), what `torchaudio.save` writes for a float32 tensor
-    (infer_test_v3m2.py:425-436).  Stdlib only; `samples`: 1-D array-like or a [1, n] tensor."""
+    """32-bit IEEE-float WAV (format tag 3), what `torchaudio.save` writes for a float32 tensor
+    (infer_test_v3m2.py:425-436).  Stdlib only; `samples`: 1-D array-like or a [1, n] tensor (mono), or a [channels, n]
+    tensor or array (interleaved on disk)."""
     import array
     import struct
+    channels = 1
+    if getattr(samples, "ndim", 1) == 2 and samples.shape[0] > 1:
+        channels = int(samples.shape[0])
+        samples = samples.T                                   # [n, channels]: frames of interleaved samples
     if hasattr(samples, "detach"):
         samples = samples.detach().to("cpu", torch.float32).reshape(-1).tolist()
+    elif channels > 1:
+        samples = samples.reshape(-1).tolist()
     data = array.array("f", samples)
     if struct.pack("=f", 1.0) != struct.pack("<f", 1.0):
         data.byteswap()
     body = data.tobytes()
-    fmt = struct.pack("<HHIIHH", 3, 1, sample_rate, sample_rate * 4, 4, 32)
+    fmt = struct.pack("<HHIIHH", 3, channels, sample_rate, sample_rate * 4 * channels, 4 * channels, 32)
     # WAVE_FORMAT_IEEE_FLOAT: fmt chunk with cbSize = 0 and a fact chunk (sample count), as libsndfile writes it
     fmt += struct.pack("<H", 0)
-    fact = struct.pack("<4sII", b"fact", 4, len(data))
+    fact = struct.pack("<4sII", b"fact", 4, len(data) // channels)
     size = 4 + (8 + len(fmt)) + len(fact) + (8 + len(body))
     with open(path, "wb") as f:
         f.write(struct.pack("<4sI4s", b"RIFF", size, b"WAVE"))
@@ -104,11 +111,11 @@ def write_wav_float32(path, samples, sample_rate=44100):
     return path
 
 
-def read_wav(path):
+def read_wav(path, mono=True):
     """WAV file -> (float32 numpy [L], sample_rate).  Reads PCM 16 / 24 / 32-bit integer (format tag 1) and 32-bit IEEE
     float (tag 3), also inside WAVE_FORMAT_EXTENSIBLE (tag 0xFFFE); integers are scaled by 2^-(bits-1).  Multi-channel
-    audio is averaged to mono, as the reference does (prepare_dataset_v5.py:130).  Stdlib + numpy only; a malformed or
-    unsupported file raises ValueError."""
+    audio is averaged to mono, as the reference does (prepare_dataset_v5.py:130), unless mono=False, which keeps the
+    channels: [channels, L].  Stdlib + numpy only; a malformed or unsupported file raises ValueError."""
     import struct
 
     import numpy as np
@@ -149,5 +156,7 @@ def read_wav(path):
         x = (v - ((v & 0x800000) << 1)).astype(np.float64) / 2.0 ** 23
     else:
         raise ValueError(f"{path}: unsupported WAV format tag {tag} with {bits} bits")
+    if not mono:
+        return np.ascontiguousarray(x.reshape(-1, ch).T).astype(np.float32), sr
     x = x.reshape(-1, ch).mean(axis=1) if ch > 1 else x
     return x.astype(np.float32), sr
