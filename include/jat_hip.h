@@ -200,8 +200,8 @@ int jat_k_norm_modulate(const float* x, const float* w, const float* shift, cons
                         int64_t mod_bstride, uint16_t* y_bf16, int32_t M, int32_t D, int32_t rows_per_batch,
                         int32_t norm_mode, void* stream);
 /* C[M,N] (+bias) = A_bf16[M,K] * W_bf16[N,K]^T ; epilogue: 0 = fp32 out, 1 = bf16 out, 2 = bf16 GELU(erf),
- * 3 = fp32 out += gate[b]*(acc+bias) (gate [B, N] with stride gate_bstride).  variant selects the tile
- * configuration (0 = default). */
+ * 3 = fp32 out += gate[b]*(acc+bias) (gate [B, N] with stride gate_bstride).  variant: the id of a live tile variant
+ * (csrc/gemm_variants.h; there is no default: retired and unknown ids, 0 among them, are rejected). */
 int jat_k_gemm(const uint16_t* A, const uint16_t* W, const float* bias, void* C, int32_t M, int32_t N,
                int32_t K, int32_t epilogue, const float* gate, int64_t gate_bstride, int32_t rows_per_batch,
                int32_t variant, void* stream);
@@ -212,7 +212,7 @@ int jat_k_gemm(const uint16_t* A, const uint16_t* W, const float* bias, void* C,
  *     x_new^2 in fixed order.  C is not touched.
  *   consumer (part_in != NULL; any epilogue): accumulator row m scaled by rsqrt(sum_j part_in[m][j] / K + 1e-6) before the
  *     bias; part_in_np in {4, 8, 16}.
- * Variants with the coalesced epilogue only (>= 18). */
+ * Variants with the coalesced epilogue only (CE != 0 in csrc/gemm_variants.h: every live one but 10). */
 int jat_k_gemm_fold(const uint16_t* A, const uint16_t* W, const float* bias, void* C, int32_t M, int32_t N, int32_t K,
                     int32_t epilogue, const float* gate, int64_t gate_bstride, int32_t rows_per_batch, uint16_t* hi,
                     uint16_t* lo, float* part_out, const float* part_in, int32_t part_in_np, int32_t variant, void* stream);
@@ -230,6 +230,12 @@ int jat_k_qkv_attn(const uint16_t* A, const uint16_t* Wg, const float* bias, uin
                    const float* rope_inv_freq, const float* part_in, int32_t part_in_np, void* stream);
 /* columns per wave tile of a GEMM tile variant (the slot width of part_out); 0 for an unknown variant */
 int jat_k_gemm_wave_n(int32_t variant);
+/* The tile variant and the K-slice count (1 = none) the forward of `m` launches for a GEMM [M, N, K] at a call site: 0 qkv,
+ * 1 out_proj, 2 fc1, 3 fc2, 4 everything else.  The split-K plans apply where N is the width the site has in the model (qkv:
+ * D + 2 kvD; out_proj, fc2: D; 4 with N = bottleneck_dim: the first patch-embed Linear); any other N is planned as a plain GEMM.
+ * folding != 0: as in a sampler bucket that runs with folded norms.  Host arithmetic only: needs no weights and no GPU. */
+int jat_k_gemm_plan(const jat_model* m, int32_t site, int32_t M, int32_t N, int32_t K, int32_t folding, int32_t* variant,
+                    int32_t* ksplit);
 /* Weight gradient of y = x W^T + b from token-major operands: dW[out,in] = dY[tokens,out]^T X[tokens,in] (fp32), db[out] =
  * column sums of dY (db may be NULL).  out and in multiples of 128; ksplit >= 1 slices of the token axis summed in order
  * (0 = the count that fills the chip, at most 16); work: 256 + (ksplit > 1 ? ksplit*out*in*4 : 0) + 32*out*4 bytes.  (The backward of every nn.Linear of

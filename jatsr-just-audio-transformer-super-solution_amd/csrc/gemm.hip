@@ -27,8 +27,10 @@
 // M may be ragged (rows clamped on load, masked on store); N % BN == 0 and K % 64 == 0 are required.
 #include "jat_kernels.h"
 #include "jat_dtype.h"
+#include "gemm_variants.h"
 
 #include <type_traits>
+#include <utility>
 
 typedef jat_opx8 bf16x8;   // 8 operand elements (bf16, or fp16 in the -DJAT_FP16 build): one MFMA fragment
 typedef __attribute__((ext_vector_type(4))) float f32x4;
@@ -1900,70 +1902,43 @@ static hipError_t launch_epi(const GemmArgs& a, int epi, hipStream_t s) {
   return hipErrorInvalidValue;
 }
 
-// variant table: {BM, BN} per id (for the host-side chooser) and the dispatch below must stay in sync
-// Variant ids are stable across rounds (profiles and DESIGN.md cite them); retired ids have a {0, 0} tile and are rejected.
-static const int kVariantTile[][2] = {
-    {0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0},   // 0-9: retired (PIPE 0 / 1)
-    {128, 64},                                                                          // 10: PIPE 1, the always-valid fallback (N % 64)
-    {0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0}, {0, 0},                             // 11-17: retired (PIPE 2 without the coalesced epilogue, PIPE 3)
-    {128, 160}, {0, 0}, {128, 128}, {256, 256},      // 18, 20, 21: PIPE 2 + coalesced epilogue (19 retired)
-    {0, 0}, {0, 0}, {0, 0},                          // 22-24: retired (PIPE 4 / 5)
-    {256, 160}, {256, 128},                          // 25-26: PIPE 6 (8 MFMA waves + 4 DMA waves)
-    {64, 160}, {64, 128},                            // 27-28: small-M tiles (PIPE 2 + coalesced epilogue)
-    {0, 0}, {0, 0},                                  // 29-30: retired (PIPE 7)
-    {224, 320}, {256, 160}, {256, 256}, {128, 448},  // 31-34: PIPE 8 (quadrant ping-pong, 2 LDS stages) + coalesced epilogue
-    {224, 256},                                      // 35: PIPE 8
-    {224, 320},                                      // 36: the tile of 31 with the software-pipelined bf16 / GELU epilogue (CE == 2)
-    {0, 0},                                          // 37: retired (pipelined split-residual epilogue: slower, profiles/r03)
-    {224, 320},                                      // 38: persistent two-tile form of 36 (gemm_persist_kernel); falls back to 36
-    {256, 160},                                      // 39: k-step-pair 224 x 160 tile for the split-residual producers (gemm_kpair_kernel);
-                                                     //     falls back to 32 (whose tile this entry reports)
-};
-static const int kVariantWaveN[] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 32, 0, 0, 0, 0, 0, 0, 0,
-                                    80, 0, 64, 64, 0, 0, 0, 80, 64, 80, 64, 0, 0, 80, 80, 64, 112, 64, 80, 0, 80, 80};
-int gemm_variant_wave_n(int variant) { return kVariantWaveN[variant]; }
-bool gemm_variant_coalesced(int variant) { return variant >= 18; }
-int gemm_num_variants() { return (int)(sizeof(kVariantTile) / sizeof(kVariantTile[0])); }
-
 hipError_t launch_qkv_attn(const GemmArgs& a, hipStream_t s) {
   if (a.ntok != 128 || a.N % 448 != 0 || a.M % 128 != 0) return hipErrorInvalidValue;
   return launch_one<2, 4, 4, 7, 8, 0, EPI_QKV_ATTN>(a, s);
 }
-void gemm_variant_tile(int variant, int* bm, int* bn) {
-  *bm = kVariantTile[variant][0];
-  *bn = kVariantTile[variant][1];
-}
 
-bool gemm_variant_exists(int variant) {
-  return variant >= 0 && variant < gemm_num_variants() && kVariantTile[variant][0] != 0;
+// row I of the variant table (gemm_variants.h) as template arguments: the table is the dispatch
+template <int I>
+static hipError_t launch_row(const GemmArgs& a, int epi, hipStream_t s) {
+  constexpr GemmVariant v = kGemmVariants[I];
+  static_assert(v.fallback >= 0 || v.blocks_per_cu == ((v.WM * v.WN == 4 && v.TM * v.TN <= 20) ? 2 : 1),
+                "blocks_per_cu must be what the launch bounds of gemm_bf16_kernel allow");
+  if constexpr (v.fallback >= 0) {
+    constexpr const GemmVariant* f = gemm_variant(v.fallback);
+    static_assert(f && f->fallback < 0 && f->WM == v.WM && f->WN == v.WN && f->TM == v.TM && f->TN == v.TN && f->PIPE == v.PIPE && f->CE == v.CE,
+                  "a variant with a kernel of its own carries the row of its (live, final) fallback");
+  }
+  return launch_epi<v.WM, v.WN, v.TM, v.TN, v.PIPE, v.CE>(a, epi, s);
+}
+template <int... I>
+static hipError_t launch_rows(int id, const GemmArgs& a, int epi, hipStream_t s, std::integer_sequence<int, I...>) {
+  hipError_t e = hipErrorInvalidValue;
+  (void)((kGemmVariants[I].id == id && ((e = launch_row<I>(a, epi, s)), true)) || ...);
+  return e;
 }
 
 hipError_t launch_gemm(const GemmArgs& a, int epi, int variant, hipStream_t s) {
-  if (!gemm_variant_exists(variant)) return hipErrorInvalidValue;
-  if (a.N % kVariantTile[variant][1] != 0) variant = (a.N % 128 == 0) ? 20 : 10;  // always-valid fallbacks
-  switch (variant) {
-    case 10: return launch_epi<2, 2, 4, 2, 1>(a, epi, s);
-    case 18: return launch_epi<2, 2, 4, 5, 2, 1>(a, epi, s);
-    case 20: return launch_epi<2, 2, 4, 4, 2, 1>(a, epi, s);
-    case 21: return launch_epi<2, 4, 8, 4, 2, 1>(a, epi, s);
-    case 25: return launch_epi<4, 2, 4, 5, 6, 1>(a, epi, s);
-    case 26: return launch_epi<4, 2, 4, 4, 6, 1>(a, epi, s);
-    case 27: return launch_epi<2, 2, 2, 5, 2, 1>(a, epi, s);
-    case 28: return launch_epi<2, 2, 2, 4, 2, 1>(a, epi, s);
-    case 31: return launch_epi<2, 4, 7, 5, 8, 1>(a, epi, s);
-    case 39:
-      if (gemm_kpair_part_eligible(a, epi)) return launch_kpair<EPI_F32, 0, true>(a, s);
-      if (gemm_kpair_eligible(a, epi))
-        return epi != EPI_RESID ? launch_kpair<EPI_F32, 0>(a, s) : a.K >= 4096 ? launch_kpair<EPI_RESID, 1>(a, s) : launch_kpair<EPI_RESID, 0>(a, s);
-      [[fallthrough]];
-    case 32: return launch_epi<4, 2, 4, 5, 8, 1>(a, epi, s);
-    case 33: return launch_epi<2, 4, 8, 4, 8, 1>(a, epi, s);
-    case 34: return launch_epi<2, 4, 4, 7, 8, 1>(a, epi, s);
-    case 35: return launch_epi<2, 4, 7, 4, 8, 1>(a, epi, s);
-    case 38:
-      if (gemm_persist_eligible(a, epi)) return epi == EPI_BF16 ? launch_persist<EPI_BF16>(a, s) : launch_persist<EPI_BF16_GELU>(a, s);
-      [[fallthrough]];
-    case 36: return launch_epi<2, 4, 7, 5, 8, 2>(a, epi, s);
+  const GemmVariant* v = gemm_variant(variant);
+  if (!v) return hipErrorInvalidValue;   // retired or unknown id
+  if (a.N % v->bn() != 0) v = gemm_variant(a.N % 128 == 0 ? V_128x128 : V_LAST_RESORT);  // always-valid fallbacks
+  // the two variants with kernels of their own take what those kernels are written for; the rest goes to their fallback,
+  // whose row they carry
+  if (v->id == V_KPAIR) {
+    if (gemm_kpair_part_eligible(a, epi)) return launch_kpair<EPI_F32, 0, true>(a, s);
+    if (gemm_kpair_eligible(a, epi))
+      return epi != EPI_RESID ? launch_kpair<EPI_F32, 0>(a, s) : a.K >= 4096 ? launch_kpair<EPI_RESID, 1>(a, s) : launch_kpair<EPI_RESID, 0>(a, s);
   }
-  return hipErrorInvalidValue;
+  if (v->id == V_PERSIST && gemm_persist_eligible(a, epi))
+    return epi == EPI_BF16 ? launch_persist<EPI_BF16>(a, s) : launch_persist<EPI_BF16_GELU>(a, s);
+  return launch_rows(v->fallback >= 0 ? v->fallback : v->id, a, epi, s, std::make_integer_sequence<int, kNumGemmVariants>{});
 }

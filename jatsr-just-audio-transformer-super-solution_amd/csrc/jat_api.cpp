@@ -16,6 +16,8 @@
 
 #include "jat_internal.h"
 #include "jat_dtype.h"
+#include "gemm_plan.h"
+#include "gemm_variants.h"
 
 static thread_local char g_err[512] = "";
 int jat_fail(int code, const char* fmt, ...) {
@@ -30,17 +32,12 @@ int jat_fail(int code, const char* fmt, ...) {
 struct Workspace {
   bf16_t *a_patch, *h_patch, *xn, *xlo, *q, *k, *vt, *ao, *hm, *t_silu;
   float *x, *mod, *e_sin, *t_h, *t_emb, *part;
-  float* kpart;   // split-K partials of the fc2 GEMM when M is too small to fill the chip (nullptr for large M)
+  float* kpart;   // split-K partials when M is too small to fill the chip (nullptr for large M: split_ws_slices, gemm_plan.h)
   const int* lens = nullptr;   // sampler: per-batch-row key counts (tokens) for the attention kernel, or nullptr
   const int* tvalid = nullptr; // sampler: valid frames per source row (patchify reads zeros beyond them), or nullptr
   int npad;
   size_t vt_bytes, total;
 };
-
-// Small-M inference (the reference's own B = 1 chunk loop gives M = 690 rows with CFG; a file's short last chunk M = 240):
-// the K = 5120 fc2 GEMM has a few dozen tiles x 80 K-steps — split K over otherwise idle CUs, finish in fixed order.
-static constexpr int kSplitMaxRows = 2304, kSplitMax = 8;
-static constexpr int kSplitWsRows = 4096;   // split-K partial workspace exists up to here (un-folded buckets: see resid_split)
 
 static Workspace carve(const jat_model* m, int B, int ntok, char* base) {
   Workspace w;
@@ -69,7 +66,7 @@ static Workspace carve(const jat_model* m, int B, int ntok, char* base) {
   w.t_emb = (float*)take((size_t)B * m->D * 4);
   w.t_silu = (bf16_t*)take((size_t)B * m->D * 2);
   w.part = (float*)take(M * 32 * 4);  // row partial sums of x^2 (norm folding), <= 32 wave column tiles
-  w.kpart = M <= kSplitWsRows ? (float*)take((size_t)(M <= kSplitMaxRows ? kSplitMax : 2) * M * (m->D + 2 * m->kvD) * 4) : nullptr;   // widest user: the QKV GEMM
+  w.kpart = split_ws_slices(M) ? (float*)take((size_t)split_ws_slices(M) * M * (m->D + 2 * m->kvD) * 4) : nullptr;   // widest user: the QKV GEMM
   w.total = off;
   return w;
 }
@@ -325,87 +322,31 @@ extern "C" int jat_model_workspace_bytes(const jat_model* m, int32_t B, int32_t 
 // forward pieces
 // ---------------------------------------------------------------------------------------------------------
 
-// Tile choice by shape (gemm.hip variant table; measured on MI355X, profiles/r01/gemm_variants.md).  What
-// decides is how the tile count quantises onto 256 CUs (one 8-wave block or two 4-wave blocks per CU) and how
-// many bytes are staged per MFMA: 256x160 with DMA waves (variant 25; 224 tiles at M=7168, N=1280: one round) >
-// 128x160 > 256x256 > 128x128.
-static int pick_variant(int M, int N, int nbatch = 1) {
-  // score = in-tile efficiency factor x tile-quantisation efficiency on the slots the variant occupies
-  // (256 CUs x 1 eight/twelve-wave block, or x 2 four-wave blocks); factors calibrated on the measured block GEMMs
-  // at M = 7168 and M = 3584 (profiles/r01/gemm_variants_*.log).  Multi-round 1-block-per-CU variants pay 15 %:
-  // their prologue/epilogue is not overlapped by a co-resident block.
-  struct Cand { int id, bm, bn, slots; double f; };
-  // 31-35: quadrant ping-pong (PIPE 8), one 8-wave block per CU; calibrated on profiles/r02/gemm_variants_*.log
-  static const Cand cands[] = {
-      {20, 128, 128, 512, 0.95}, {18, 128, 160, 512, 0.95}, {25, 256, 160, 256, 1.00},
-      {26, 256, 128, 256, 0.90}, {21, 256, 256, 256, 1.00}, {27, 64, 160, 512, 0.60}, {28, 64, 128, 512, 0.62},
-      {31, 224, 320, 256, 1.12}, {32, 256, 160, 256, 1.01}, {33, 256, 256, 256, 1.06},
-      {35, 224, 256, 256, 1.06},
-  };
-  int best = 20;
-  double best_score = -1.0;
-  for (const Cand& c : cands) {
-    if (N % c.bn != 0) continue;
-    const long t = (long)((M + c.bm - 1) / c.bm) * (N / c.bn) * nbatch;
-    const long rounds = (t + c.slots - 1) / c.slots;
-    double score = c.f * (double)t / (double)(rounds * c.slots);
-    // multi-round penalty: the 12-wave DMA-wave variants (25, 26) pay their un-overlapped prologue/epilogue per round;
-    // the 8-wave tiles (21, 31-35) less so (M = 9660, N = 5120: 110 us vs 124 us for 128x160, tools/gemm_shapes_bench.py)
-    if (c.slots == 256 && rounds > 1 && (c.id == 25 || c.id == 26)) score *= 0.85;
-    // padding waste of a ragged last row tile counts against big tiles
-    score *= (double)M / (double)(((M + c.bm - 1) / c.bm) * c.bm);
-    if (score > best_score) { best_score = score; best = c.id; }
-  }
-  // a half-size batch's QKV GEMM (M = 3584, N = 1792): 392 tiles of 128 x 128 fill 77 % of the 512 four-wave slots; 196 tiles of
-  // 256 x 128 with the DMA-wave pipeline are one block on 196 CUs and measured faster (forward 5.530 -> 5.455 ms,
-  // profiles/r03/forward_B28_out_qkv_tile_sweep.log).  Only where those tiles make one nearly full round.
-  if (best == 20 && nbatch == 1 && N % 128 == 0) {
-    const long t26 = (long)((M + 255) / 256) * (N / 128);
-    if (t26 >= 192 && t26 <= 256 && M % 256 == 0) best = 26;
-  }
-  // 36: the tile of 31 with the software-pipelined bf16 / GELU epilogue (JAT_EPI_PIPE=0 keeps the plain one: A/B)
-  static const int epi_pipe = getenv("JAT_EPI_PIPE") ? atoi(getenv("JAT_EPI_PIPE")) : 1;
-  if (epi_pipe && best == 31) best = 36;
-  // 39: the k-step-pair 224 x 160 tile for the N = 1280 class when it fills more of the chip than 256 x 160 (M = 7168: 256 tiles
-  // against 224); launch_gemm falls back to 32 for anything but the split-residual producer epilogues.  JAT_KPAIR=0: A/B
-  static const int kpair = getenv("JAT_KPAIR") ? atoi(getenv("JAT_KPAIR")) : 1;
-  if (kpair && best == 32 && nbatch == 1 && M % 224 == 0 && N % 160 == 0) {
-    auto eff = [](long t) { return (double)t / (double)(((t + 255) / 256) * 256); };
-    if (eff((long)(M / 224) * (N / 160)) > eff((long)((M + 255) / 256) * (N / 160))) best = 39;
-  }
-  // 38: the persistent two-tile form of 36 (launch_gemm falls back to 36 for shapes / epilogues it does not take); JAT_PERSIST=0: A/B
-  static const int persist = getenv("JAT_PERSIST") ? atoi(getenv("JAT_PERSIST")) : 1;
-  if (persist && best == 36 && M % 224 == 0 && (long)(M / 224) * (N / 320) * nbatch > 256) best = 38;
-  return best;
-}
-
-static int kTileN(int variant) { int bm, bn; gemm_variant_tile(variant, &bm, &bn); return bn; }
-
+// plan == nullptr: a plain GEMM of the call site (plan_gemm), in extra.ksplit slices if the caller set them up itself (the
+// training step's dW GEMMs); else what one of the per-decision functions of gemm_plan.h returned
 int jat_gemm(const jat_model* m, int site, const bf16_t* A, int64_t lda, const bf16_t* W, int64_t ldw, int M, int N,
-             int K, int epi, GemmArgs extra, hipStream_t s) {
+             int K, int epi, GemmArgs extra, hipStream_t s, const GemmPlan* plan) {
   GemmArgs a = extra;
   a.A = A; a.lda = lda; a.W = W; a.ldw = ldw; a.M = M; a.N = N; a.K = K;
-  if (a.ksplit > 1) a.K = K / a.ksplit;   // per-slice depth; the kernel shifts A / W / out by blockIdx.y
-  int variant = m->variants[site] >= 0 ? m->variants[site] : a.variant_hint > 0 ? a.variant_hint : pick_variant(M, N, a.ksplit > 1 ? a.ksplit : 1);
-  if ((a.fold_out || a.rs_part) && !gemm_variant_coalesced(variant)) variant = 20;  // folding lives in the CE epilogues
-  if (N % kTileN(variant) != 0) variant = 20;  // 128 x 128, always valid
-  if (a.fold_out) { a.fold_np = N / gemm_variant_wave_n(variant); m->last_fold_np = a.fold_np; }
+  const GemmPlan p = plan ? *plan : plan_gemm(m, site, M, N, a.ksplit, a.fold_out || a.rs_part);
+  if (p.ksplit > 1) { a.ksplit = p.ksplit; a.K = K / p.ksplit; }   // per-slice depth; the kernel shifts A / W / out by blockIdx.y
+  const GemmVariant* t = gemm_variant(p.variant);   // nullptr (a pinned id that is not live): launch_gemm rejects it
+  if (a.fold_out) { a.fold_np = t ? N / t->wave_n() : 0; m->last_fold_np = a.fold_np; }
   if (a.rs_part) a.rs_np = m->last_fold_np;
   // measurement aid (bench.py roofline leg): bracket the launches of one call site with HIP events on the
   // launch stream.  Never active during graph capture (the bench enables it around eager forwards only).
   const bool timed = m->prof.site == site && m->prof.n < (int)m->prof.ev.size() / 2;
   if (timed) { m->prof.stream = s; (void)hipEventRecord(m->prof.ev[2 * m->prof.n], s); }
-  hipError_t e = launch_gemm(a, epi, variant, s);
+  hipError_t e = launch_gemm(a, epi, p.variant, s);
   if (timed) {
     (void)hipEventRecord(m->prof.ev[2 * m->prof.n + 1], s);
     m->prof.flops += 2.0 * M * N * K;
-    m->prof.variant = variant;
+    m->prof.variant = p.variant;
     ++m->prof.n;
   }
   if (e != hipSuccess) return fail(JAT_E_HIP, "gemm launch (M=%d N=%d K=%d epi=%d): %s", M, N, K, epi, hipGetErrorString(e));
   return JAT_OK;
 }
-#define gemm jat_gemm
 
 // t [B] -> t_emb [B,D] fp32 (+ bf16 silu(t_emb))  (t_embedder, jat_audiosr_v3.py:364-369)
 static int time_path(const jat_model* m, const Workspace& w, const float* t, int B, hipStream_t s) {
@@ -418,7 +359,7 @@ static int time_path(const jat_model* m, const Workspace& w, const float* t, int
 static int adaln_path(const jat_model* m, const bf16_t* t_silu, float* mod, int B, int l0, int nl, hipStream_t s) {
   GemmArgs e{};
   e.out = mod; e.ldo = (int64_t)nl * 6 * m->D; e.bias = m->bada + (int64_t)l0 * 6 * m->D; e.ntok = 1;
-  return gemm(m, G_OTHER, t_silu, m->D, m->wada + (int64_t)l0 * 6 * m->D * m->D, m->D, B, nl * 6 * m->D, m->D, EPI_F32, e, s);
+  return jat_gemm(m, G_OTHER, t_silu, m->D, m->wada + (int64_t)l0 * 6 * m->D * m->D, m->D, B, nl * 6 * m->D, m->D, EPI_F32, e, s);
 }
 
 // Norm folding (sampler path, RMSNorm only): this step's slice of the FoldTable (jat_internal.h); layer offsets are applied
@@ -428,68 +369,59 @@ struct Fold {
   const float *bq_g, *bq_i, *bf;
 };
 
-// K-slices for a gated-residual GEMM [M, D] = A[M, K] W^T whose tiles do not fill the chip (small-M inference), 1 = none
-static int resid_split(const jat_model* m, const Workspace& w, int site, int M, int K, bool folding, int* variant = nullptr) {
-  if (variant) *variant = -1;
-  if (!w.kpart || folding || K < 1024 || m->variants[site] >= 0) return 1;
-  auto slices = [&](int v, int cap) {
-    int bm, bn;
-    gemm_variant_tile(v, &bm, &bn);
-    const int tiles = ((M + bm - 1) / bm) * (m->D / bn), slots = (v == 18 || v == 20 || v == 27 || v == 28) ? 512 : 256;
-    int split = slots / tiles < cap ? slots / tiles : cap;
-    while (split > 1 && ((K / 64) % split != 0 || K / split < 256)) --split;   // >= 4 K-tiles per slice
-    return split > 1 ? split : 1;
-  };
-  // Which tile the slices are cut for: 64 x 128 tiles (what pick_variant takes un-split) are bound by the per-CU L2->LDS rate
-  // (24 KB per K-tile and block, two blocks per CU); 128 x 128 tiles move 2/3 of the bytes per flop and, cut into more slices,
-  // give as many blocks.  Measured per 50-step run (B = 2 / 4 / 8): fc2 133.0 -> 130.3, 169.0 -> 154.5, 253.6 -> 220.1 ms (B = 1:
-  // neutral); out_proj only pays from M = 2048 (B = 8: 219.7 -> 212.8 ms).
-  if (M <= kSplitMaxRows) return slices((K >= 4096 || M >= 1536) ? 20 : pick_variant(M, m->D), kSplitMax);
-  // a mid-size un-folded bucket (a T = 4096 file: M = 2760): the 64 x 128 tiles that fill the chip un-split are bound by the
-  // per-CU L2->LDS rate (24 KB per K-tile and block, two blocks per CU); for the long-K fc2 two slices of 128 x 128 tiles
-  // (the same 440 blocks, 2/3 of the bytes per flop) + the finishing pass are faster: 70 -> 45 us
-  // A half-size batch (configs[1]'s single forward, M = 3584): the 224 x 160 k-step-pair tile makes 128 tiles — two K slices
-  // put one on every CU (tile bytes per flop: 0.011 against 0.022 for the 64 x 160 tiles that fill the chip un-split); the
-  // finishing pass also applies the norm that follows, which saves the separate norm launch.  JAT_KPAIR_SPLIT=0: A/B
-  static const int kpair_split = getenv("JAT_KPAIR_SPLIT") ? atoi(getenv("JAT_KPAIR_SPLIT")) : 1;
-  if (kpair_split && variant && M % 224 == 0 && m->D % 160 == 0) {
-    const int tiles = (M / 224) * (m->D / 160);
-    int split = tiles <= 128 ? 256 / tiles : 1;
-    if (split > 2) split = 2;                      // the workspace of this bucket holds two slices (carve)
-    while (split > 1 && ((K / 64) % split != 0 || K / split < 512)) --split;
-    // only where the slices fill the chip (M = 3136 ... 3584: 224 ... 256 blocks); below that the 128 x 128 slices stay (measured
-    // at M = 3584 only: profiles/r03/forward_B28_kernel_table_kpair_split.txt)
-    if (split > 1 && tiles * split >= 224 && (K >= 4096 || kpair_split >= 2)) { *variant = 39; return split; }
-  }
-  return K >= 4096 ? slices(20, 2) : 1;
+static constexpr float kAttnScaleLog2e = 0.125f * 1.4426950408889634f;   // (1 / sqrt(64)) * log2(e)
+static GemmArgs qkv_rope_args(const jat_model* m, const Workspace& w, int ntok) {
+  GemmArgs e{};
+  e.out = w.q; e.k_out = w.k; e.vt_out = w.vt; e.D = m->D; e.kvD = m->kvD; e.npad = w.npad; e.ntok = ntok;
+  e.rope_cos = m->rope_cos; e.rope_sin = m->rope_sin; e.rope_inv_freq = m->rope_invf;
+  return e;
+}
+static AttnArgs attn_args(const jat_model* m, const Workspace& w, int B, int ntok) {
+  AttnArgs a{};
+  a.q = w.q; a.k = w.k; a.vt = w.vt; a.o = w.ao; a.ldq = m->D; a.ldk = m->kvD; a.ldo = m->D;
+  a.B = B; a.N = ntok; a.Hq = m->Hq; a.Hkv = m->Hkv; a.npad = w.npad;
+  a.scale_log2e = kAttnScaleLog2e; a.lens = w.lens;
+  return a;
 }
 
-// K-slices for the QKV GEMM of a small bucket (M <= kSplitMaxRows, un-folded, separate attention kernel): its 56 tiles at one
-// chunk leave 200 CUs without weights to pull; the slices are summed, rotated and laid out by splitk_qkv_finish_kernel
-static int qkv_split(const jat_model* m, const Workspace& w, int M, int K, bool folding) {
-  if (!m->sw.qkv_split || m->D % 64 != 0 || m->kvD % 64 != 0 || !w.kpart || folding || M > kSplitMaxRows || m->variants[G_QKV] >= 0) return 1;
-  const int N = m->D + 2 * m->kvD;
-  int bm, bn;
-  const int v = pick_variant(M, N);
-  gemm_variant_tile(v, &bm, &bn);
-  if (N % bn != 0) return 1;
-  const int tiles = ((M + bm - 1) / bm) * (N / bn), slots = (v == 18 || v == 20 || v == 27 || v == 28) ? 512 : 256;
-  int split = slots / tiles < kSplitMax ? slots / tiles : kSplitMax;
-  while (split > 1 && ((K / 64) % split != 0 || K / split < 256)) --split;
-  return split > 1 ? split : 1;
+// The norm that consumes a block's output (norm1 of the next block, or the final norm: shift == nullptr) can ride in the
+// finishing pass of a split-K fc2 (small-M buckets); likewise norm2 in that of out_proj.
+struct NextNorm { const float *w, *shift, *scale; };
+
+// Gated-residual GEMM w.x += gate * (A[M, K] W^T + bias) of out_proj (G_OUT) and fc2 (G_FC2): one launch with the EPI_RESID
+// epilogue, or K slices + a finishing pass that also applies the norm `next` into w.xn where it can (*norm_done reports it)
+static int resid_gemm(const jat_model* m, const Workspace& w, int site, const bf16_t* A, const bf16_t* W, int K, const float* bias,
+                      const float* gate, int64_t bstride, int M, int ntok, bool folding, const NextNorm* next, bool* norm_done,
+                      hipStream_t s) {
+  const int D = m->D;
+  *norm_done = false;
+  const GemmPlan plan = plan_resid(m, site, M, K, folding, w.kpart != nullptr);
+  if (plan.ksplit == 1) {
+    GemmArgs e{};
+    e.out = w.x; e.ldo = D; e.bias = bias; e.gate = gate; e.gate_bstride = bstride; e.ntok = ntok;
+    if (folding) { e.fold_out = w.xn; e.fold_lo = w.xlo; e.fold_part = w.part; }   // feeds the norm that follows
+    return jat_gemm(m, site, A, K, W, K, M, D, K, EPI_RESID, e, s, &plan);
+  }
+  GemmArgs p{};
+  p.out = w.kpart; p.ldo = D; p.ntok = ntok; p.split_stride = (int64_t)M * D;
+  JCHK(jat_gemm(m, site, A, K, W, K, M, D, K, EPI_F32, p, s, &plan));
+  if (next && !folding && m->sw.fuse_finish && splitk_resid_norm_supported(D)) {   // slice sum + gate + residual + norm in one launch
+    KCHK(launch_splitk_resid_norm(w.kpart, plan.ksplit, (int64_t)M * D, bias, gate, bstride, w.x, next->w, next->shift, next->scale,
+                                  bstride, w.xn, M, D, ntok, m->cfg.norm_mode, s));
+    *norm_done = true;
+  } else {
+    KCHK(launch_splitk_resid_finish(w.kpart, plan.ksplit, (int64_t)M * D, bias, gate, bstride, ntok, w.x, M, D, s));
+  }
+  return JAT_OK;
 }
 
 // one DiTBlock_GQA on the residual stream w.x  (jat_audiosr_v3.py:284-308); mod_l = this layer's 6D row of batch 0
-// The norm that consumes a block's output (norm1 of the next block, or the final norm: shift == nullptr) can ride in the
-// finishing pass of a split-K fc2 (small-M buckets): `next` describes it, *next_done reports that w.xn already holds it.
-struct NextNorm { const float *w, *shift, *scale; };
+// `next`: the norm that reads this block's output, *next_done reports that w.xn already holds it.
 static int run_block(const jat_model* m, const Workspace& w, int l, int B, int ntok, const float* mod_l,
                      int64_t bstride, hipStream_t s, const Fold* f = nullptr, bool xn_ready = false,
                      const NextNorm* next = nullptr, bool* next_done = nullptr) {
   const int D = m->D, M = B * ntok, Nqkv = D + 2 * m->kvD;
   const LayerW& L = m->layers[l];
-  if (next_done) *next_done = false;
-  const bool can_fuse = m->sw.fuse_finish && splitk_resid_norm_supported(D);
   if (!f && !xn_ready) KCHK(launch_norm_modulate(w.x, L.norm1, mod_l + 0 * D, mod_l + 1 * D, bstride, w.xn, M, D, ntok, m->cfg.norm_mode, s));
   const int fuse_env = m->sw.fuse_qkv_attn;   // per-handle switch (jat_model_set_switch): tests A/B the two paths on one model
   // one block per (sample, KV group): worth it only when B * Hkv blocks fill the 256 CUs (measured: +1.8 % at
@@ -501,84 +433,56 @@ static int run_block(const jat_model* m, const Workspace& w, int l, int B, int n
     GemmArgs a{};
     a.A = w.xn; a.lda = D; a.W = f ? f->wqkv_g + (int64_t)l * Nqkv * D : L.wqkv_g; a.ldw = D; a.M = M; a.N = m->Hkv * 448; a.K = D;
     a.out = w.ao; a.ldo = D; a.ntok = ntok; a.rope_inv_freq = m->rope_invf;
-    a.attn_scale_log2e = 0.125f * 1.4426950408889634f;
+    a.attn_scale_log2e = kAttnScaleLog2e;
     if (f) { a.rs_part = w.part; a.rs_np = m->last_fold_np; a.bias = f->bq_g + (int64_t)l * Nqkv; }
     KCHK(launch_qkv_attn(a, s));
   } else {
-    GemmArgs e{};
-    e.out = w.q; e.k_out = w.k; e.vt_out = w.vt; e.D = D; e.kvD = m->kvD; e.npad = w.npad; e.ntok = ntok;
-    e.rope_cos = m->rope_cos; e.rope_sin = m->rope_sin; e.rope_inv_freq = m->rope_invf;
-    if (f) { e.rs_part = w.part; e.bias = f->bq_i + (int64_t)l * Nqkv; }
-    const int qs = qkv_split(m, w, M, D, f != nullptr);
-    if (qs > 1) {
+    const GemmPlan plan = plan_qkv(m, M, D, f != nullptr, w.kpart != nullptr);
+    if (plan.ksplit > 1) {
       GemmArgs p{};
-      p.out = w.kpart; p.ldo = Nqkv; p.ntok = ntok; p.ksplit = qs; p.split_stride = (int64_t)M * Nqkv;
-      JCHK(gemm(m, G_QKV, w.xn, D, L.wqkv, D, M, Nqkv, D, EPI_F32, p, s));
-      KCHK(launch_splitk_qkv_finish(w.kpart, qs, (int64_t)M * Nqkv, m->rope_cos, m->rope_sin, w.q, w.k, w.vt, M, D, m->kvD, ntok,
-                                    w.npad, s));
+      p.out = w.kpart; p.ldo = Nqkv; p.ntok = ntok; p.split_stride = (int64_t)M * Nqkv;
+      JCHK(jat_gemm(m, G_QKV, w.xn, D, L.wqkv, D, M, Nqkv, D, EPI_F32, p, s, &plan));
+      KCHK(launch_splitk_qkv_finish(w.kpart, plan.ksplit, (int64_t)M * Nqkv, m->rope_cos, m->rope_sin, w.q, w.k, w.vt, M, D, m->kvD,
+                                    ntok, w.npad, s));
     } else {
-      JCHK(gemm(m, G_QKV, w.xn, D, f ? f->wqkv_i + (int64_t)l * Nqkv * D : L.wqkv, D, M, Nqkv, D, EPI_QKV_ROPE, e, s));
+      GemmArgs e = qkv_rope_args(m, w, ntok);
+      if (f) { e.rs_part = w.part; e.bias = f->bq_i + (int64_t)l * Nqkv; }
+      JCHK(jat_gemm(m, G_QKV, w.xn, D, f ? f->wqkv_i + (int64_t)l * Nqkv * D : L.wqkv, D, M, Nqkv, D, EPI_QKV_ROPE, e, s, &plan));
     }
+    KCHK(launch_attention(attn_args(m, w, B, ntok), s));
   }
-  if (!fused_attn) {
-    AttnArgs a{};
-    a.q = w.q; a.k = w.k; a.vt = w.vt; a.o = w.ao; a.ldq = D; a.ldk = m->kvD; a.ldo = D;
-    a.B = B; a.N = ntok; a.Hq = m->Hq; a.Hkv = m->Hkv; a.npad = w.npad;
-    a.scale_log2e = 0.125f * 1.4426950408889634f;
-    a.lens = w.lens;
-    KCHK(launch_attention(a, s));
-  }
-  bool norm2_done = false;
-  {
-    GemmArgs e{};
-    e.out = w.x; e.ldo = D; e.gate = mod_l + 2 * D; e.gate_bstride = bstride; e.ntok = ntok;
-    if (f) { e.fold_out = w.xn; e.fold_lo = w.xlo; e.fold_part = w.part; }
-    int sv = -1;
-    const int split = resid_split(m, w, G_OUT, M, D, f != nullptr, &sv);
-    if (split > 1) {
-      GemmArgs p{};
-      p.out = w.kpart; p.ldo = D; p.ntok = ntok; p.ksplit = split; p.split_stride = (int64_t)M * D; p.variant_hint = sv;
-      JCHK(gemm(m, G_OUT, w.ao, D, L.wo, D, M, D, D, EPI_F32, p, s));
-      if (can_fuse && !f) {   // slice sum + gate + residual + norm2 in one launch
-        KCHK(launch_splitk_resid_norm(w.kpart, split, (int64_t)M * D, nullptr, mod_l + 2 * D, bstride, w.x, L.norm2, mod_l + 3 * D,
-                                      mod_l + 4 * D, bstride, w.xn, M, D, ntok, m->cfg.norm_mode, s));
-        norm2_done = true;
-      } else {
-        KCHK(launch_splitk_resid_finish(w.kpart, split, (int64_t)M * D, nullptr, mod_l + 2 * D, bstride, ntok, w.x, M, D, s));
-      }
-    } else {
-      JCHK(gemm(m, G_OUT, w.ao, D, L.wo, D, M, D, D, EPI_RESID, e, s));
-    }
-  }
+  const NextNorm norm2{L.norm2, mod_l + 3 * D, mod_l + 4 * D};
+  bool norm2_done = false, done = false;
+  JCHK(resid_gemm(m, w, G_OUT, w.ao, L.wo, D, nullptr, mod_l + 2 * D, bstride, M, ntok, f != nullptr, &norm2, &norm2_done, s));
   if (!f && !norm2_done) KCHK(launch_norm_modulate(w.x, L.norm2, mod_l + 3 * D, mod_l + 4 * D, bstride, w.xn, M, D, ntok, m->cfg.norm_mode, s));
   {
     GemmArgs e{};
     e.out = w.hm; e.ldo = m->mlp; e.bias = L.b1; e.ntok = ntok;
     if (f) { e.rs_part = w.part; e.bias = f->bf + (int64_t)l * m->mlp; }
-    JCHK(gemm(m, G_FC1, w.xn, D, f ? f->w1 + (int64_t)l * m->mlp * D : L.w1, D, M, m->mlp, D, EPI_BF16_GELU, e, s));
+    JCHK(jat_gemm(m, G_FC1, w.xn, D, f ? f->w1 + (int64_t)l * m->mlp * D : L.w1, D, M, m->mlp, D, EPI_BF16_GELU, e, s));
   }
-  {
-    GemmArgs e{};
-    e.out = w.x; e.ldo = D; e.bias = L.b2; e.gate = mod_l + 5 * D; e.gate_bstride = bstride; e.ntok = ntok;
-    if (f) { e.fold_out = w.xn; e.fold_lo = w.xlo; e.fold_part = w.part; }   // feeds the next layer's norm1, or the final norm
-    int sv = -1;
-    const int split = resid_split(m, w, G_FC2, M, m->mlp, f != nullptr, &sv);
-    if (split > 1) {
-      GemmArgs p{};
-      p.out = w.kpart; p.ldo = D; p.ntok = ntok; p.ksplit = split; p.split_stride = (int64_t)M * D; p.variant_hint = sv;
-      JCHK(gemm(m, G_FC2, w.hm, m->mlp, L.w2, m->mlp, M, D, m->mlp, EPI_F32, p, s));
-      if (can_fuse && !f && next) {   // + the norm that reads this block's output
-        KCHK(launch_splitk_resid_norm(w.kpart, split, (int64_t)M * D, L.b2, mod_l + 5 * D, bstride, w.x, next->w, next->shift,
-                                      next->scale, bstride, w.xn, M, D, ntok, m->cfg.norm_mode, s));
-        if (next_done) *next_done = true;
-      } else {
-        KCHK(launch_splitk_resid_finish(w.kpart, split, (int64_t)M * D, L.b2, mod_l + 5 * D, bstride, ntok, w.x, M, D, s));
-      }
-    } else {
-      JCHK(gemm(m, G_FC2, w.hm, m->mlp, L.w2, m->mlp, M, D, m->mlp, EPI_RESID, e, s));
-    }
-  }
+  JCHK(resid_gemm(m, w, G_FC2, w.hm, L.w2, m->mlp, L.b2, mod_l + 5 * D, bstride, M, ntok, f != nullptr, next, &done, s));
+  if (next_done) *next_done = done;
   return JAT_OK;
+}
+
+// First patch-embed Linear + GELU: w.h_patch = gelu(w.a_patch[rows, K] W1[:, :K]^T + b1).  pc != nullptr (CFG sampler): the
+// rows are the z half shared by cond and uncond; rows r get + pc[r] inside the GELU, rows r + `rows` do not.
+// In one launch, or as K slices (plan_patch) whose partials live in the MLP hidden buffer, idle until block 0's fc1.
+static int patch_linear1(const jat_model* m, const Workspace& w, int rows, int K, const float* pc, int ntok, hipStream_t s) {
+  const GemmPlan plan = plan_patch(m, rows, K);
+  GemmArgs e{};
+  e.ldo = m->bott; e.ntok = ntok;
+  if (plan.ksplit > 1) {
+    e.out = w.hm; e.split_stride = (int64_t)rows * m->bott;
+    JCHK(jat_gemm(m, G_OTHER, w.a_patch, K, m->pe_w1, m->Kp, rows, m->bott, K, EPI_F32, e, s, &plan));
+    KCHK(launch_splitk_gelu_finish((const float*)w.hm, plan.ksplit, (int64_t)rows * m->bott, m->pe_b1, pc, pc ? rows : 0, w.h_patch,
+                                   m->bott, rows, m->bott, s));
+    return JAT_OK;
+  }
+  e.out = w.h_patch; e.bias = m->pe_b1;
+  if (pc) { e.dual_add = pc; e.dual_rows = rows; }
+  return jat_gemm(m, G_OTHER, w.a_patch, K, m->pe_w1, m->Kp, rows, m->bott, K, EPI_BF16_GELU, e, s, &plan);
 }
 
 // Whole forward over B batch rows.  x_t rows are read modulo B_src and the condition is zero from batch row
@@ -600,57 +504,21 @@ static int forward_impl(const jat_model* m, const Workspace& w, const float* x_t
   // sampler zeroes its private buffer once at creation (mod != nullptr path) and only the generic entry point,
   // whose workspace belongs to the caller, clears it per call.
   if (t) HIPCHK(hipMemsetAsync(w.vt, 0, w.vt_bytes, s));
-  // The first patch-embed Linear is narrow and deep ([rows, 4096 or 8192] x [512, .]^T: 64 x 128 tiles make at most one 4-wave
-  // block per CU at the bench's batch, each walking 64-128 K-tiles): K slices put two blocks on every CU, the finishing pass
-  // adds bias and GELU (same expression as the epilogue).  The partials live in the MLP hidden buffer, idle until block 0's fc1.
-  auto patch_split = [&](int rows, int K) {
-    if (!m->sw.patch_split || m->variants[G_OTHER] >= 0 || m->bott % 128 != 0) return 1;
-    const int tiles = ((rows + 63) / 64) * (m->bott / 128);
-    // measured (profiles/r03/patch_embed_split_ab.log): pays for the single forward (K = 8192: 5.45 -> 5.41 ms) and for one chunk
-    // (24 tiles: 133.4 -> 131.9 ms), not for the sampler's half-depth form at the bench's batch (224 tiles, K = 4096: 353.1 vs 353.6 ms)
-    if (tiles > 128 && K < 8192) return 1;
-    int split = 512 / tiles, cap = m->mlp / (2 * m->bott);   // partial slices must fit w.hm: split * bott * 4 <= mlp * 2 bytes per row
-    if (cap > 4) cap = 4;
-    if (split > cap) split = cap;
-    while (split > 1 && ((K / 64) % split != 0 || K / split < 1024)) --split;
-    return split > 1 ? split : 1;
-  };
   if (pc) {
     // CFG sampler: the first patch-embed Linear is linear in [z ; cond], the z part is the same for the cond and
     // uncond halves and the cond part (pc = patch(lr) @ W1[:, cond]^T, fp32) does not change over the 50 steps:
     // h_cond = gelu(S_z + pc + b1), h_uncond = gelu(S_z + b1) from ONE quarter-size GEMM (M/2 rows, K/2 deep).
-    const int Mh = M / 2, Kz = m->P * m->Cin;
     KCHK(launch_patchify(x_t, nullptr, w.a_patch, B_src, B_src, B_src, m->Cin, 0, T, ntok, s, w.tvalid));
-    const int ps = patch_split(Mh, Kz);
-    if (ps > 1) {
-      GemmArgs e{};
-      e.out = w.hm; e.ldo = m->bott; e.ntok = ntok; e.ksplit = ps; e.split_stride = (int64_t)Mh * m->bott;
-      JCHK(gemm(m, G_OTHER, w.a_patch, Kz, m->pe_w1, m->Kp, Mh, m->bott, Kz, EPI_F32, e, s));
-      KCHK(launch_splitk_gelu_finish((const float*)w.hm, ps, (int64_t)Mh * m->bott, m->pe_b1, pc, Mh, w.h_patch, m->bott, Mh, m->bott, s));
-    } else {
-      GemmArgs e{};
-      e.out = w.h_patch; e.ldo = m->bott; e.bias = m->pe_b1; e.ntok = ntok; e.dual_add = pc; e.dual_rows = Mh;
-      JCHK(gemm(m, G_OTHER, w.a_patch, Kz, m->pe_w1, m->Kp, Mh, m->bott, Kz, EPI_BF16_GELU, e, s));
-    }
+    JCHK(patch_linear1(m, w, M / 2, m->P * m->Cin, pc, ntok, s));
   } else {
     KCHK(launch_patchify(x_t, x_cond, w.a_patch, B, B_src, cond_zero_from, m->Cin, m->Cc, T, ntok, s, w.tvalid));
-    const int ps = patch_split(M, m->Kp);
-    if (ps > 1) {
-      GemmArgs e{};
-      e.out = w.hm; e.ldo = m->bott; e.ntok = ntok; e.ksplit = ps; e.split_stride = (int64_t)M * m->bott;
-      JCHK(gemm(m, G_OTHER, w.a_patch, m->Kp, m->pe_w1, m->Kp, M, m->bott, m->Kp, EPI_F32, e, s));
-      KCHK(launch_splitk_gelu_finish((const float*)w.hm, ps, (int64_t)M * m->bott, m->pe_b1, nullptr, 0, w.h_patch, m->bott, M, m->bott, s));
-    } else {
-      GemmArgs e{};
-      e.out = w.h_patch; e.ldo = m->bott; e.bias = m->pe_b1; e.ntok = ntok;
-      JCHK(gemm(m, G_OTHER, w.a_patch, m->Kp, m->pe_w1, m->Kp, M, m->bott, m->Kp, EPI_BF16_GELU, e, s));
-    }
+    JCHK(patch_linear1(m, w, M, m->Kp, nullptr, ntok, s));
   }
   {
     GemmArgs e{};
     e.out = w.x; e.ldo = D; e.bias = m->pe_b2; e.ntok = ntok;
     if (f) { e.fold_out = w.xn; e.fold_lo = w.xlo; e.fold_part = w.part; }
-    JCHK(gemm(m, G_OTHER, w.h_patch, m->bott, m->pe_w2, m->bott, M, D, m->bott, EPI_F32, e, s));
+    JCHK(jat_gemm(m, G_OTHER, w.h_patch, m->bott, m->pe_w2, m->bott, M, D, m->bott, EPI_F32, e, s));
   }
   bool xn_ready = false;
   for (int l = 0; l < m->depth; ++l) {
@@ -666,7 +534,7 @@ static int forward_impl(const jat_model* m, const Workspace& w, const float* x_t
     GemmArgs e{};
     e.out = x_pred; e.bias = m->bfinal; e.ntok = ntok; e.C_out = m->Cin; e.T_orig = T;
     if (f) e.rs_part = w.part;
-    JCHK(gemm(m, G_OTHER, w.xn, D, f ? f->wfinal : m->wfinal, D, M, m->Fout, D, EPI_UNPATCH, e, s));
+    JCHK(jat_gemm(m, G_OTHER, w.xn, D, f ? f->wfinal : m->wfinal, D, M, m->Fout, D, EPI_UNPATCH, e, s));
   }
   return JAT_OK;
 }
@@ -726,23 +594,12 @@ extern "C" int jat_attn_forward(jat_model* m, int32_t layer, const float* x, flo
   const LayerW& L = m->layers[layer];
   HIPCHK(hipMemsetAsync(w.vt, 0, w.vt_bytes, s));
   KCHK(launch_norm_modulate(x, nullptr, nullptr, nullptr, 0, w.xn, M, D, N, 2, s));  // plain bf16 cast
-  {
-    GemmArgs e{};
-    e.out = w.q; e.k_out = w.k; e.vt_out = w.vt; e.D = D; e.kvD = m->kvD; e.npad = w.npad; e.ntok = N;
-    e.rope_cos = m->rope_cos; e.rope_sin = m->rope_sin; e.rope_inv_freq = m->rope_invf;
-    JCHK(gemm(m, G_QKV, w.xn, D, L.wqkv, D, M, D + 2 * m->kvD, D, EPI_QKV_ROPE, e, s));
-  }
-  {
-    AttnArgs a{};
-    a.q = w.q; a.k = w.k; a.vt = w.vt; a.o = w.ao; a.ldq = D; a.ldk = m->kvD; a.ldo = D;
-    a.B = B; a.N = N; a.Hq = m->Hq; a.Hkv = m->Hkv; a.npad = w.npad;
-    a.scale_log2e = 0.125f * 1.4426950408889634f;
-    KCHK(launch_attention(a, s));
-  }
+  JCHK(jat_gemm(m, G_QKV, w.xn, D, L.wqkv, D, M, D + 2 * m->kvD, D, EPI_QKV_ROPE, qkv_rope_args(m, w, N), s));
+  KCHK(launch_attention(attn_args(m, w, B, N), s));
   {
     GemmArgs e{};
     e.out = y; e.ldo = D; e.ntok = N;
-    JCHK(gemm(m, G_OUT, w.ao, D, L.wo, D, M, D, D, EPI_F32, e, s));
+    JCHK(jat_gemm(m, G_OUT, w.ao, D, L.wo, D, M, D, D, EPI_F32, e, s));
   }
   return JAT_OK;
 }
@@ -789,7 +646,7 @@ static int sampler_cond_part(jat_sampler* sp, hipStream_t s) {
   KCHK(launch_patchify(sp->lr, nullptr, sp->w.a_patch, sp->B, sp->B, sp->B, m->Cc, 0, sp->T, ntok, s, sp->w.tvalid));
   GemmArgs e{};
   e.out = sp->pc; e.ldo = m->bott; e.ntok = ntok;
-  return gemm(m, G_OTHER, sp->w.a_patch, Kc, m->pe_w1 + (int64_t)m->P * m->Cin, m->Kp, sp->B * ntok, m->bott, Kc, EPI_F32, e, s);
+  return jat_gemm(m, G_OTHER, sp->w.a_patch, Kc, m->pe_w1 + (int64_t)m->P * m->Cin, m->Kp, sp->B * ntok, m->bott, Kc, EPI_F32, e, s);
 }
 
 static int sampler_steps(jat_sampler* sp, hipStream_t s) {
@@ -885,13 +742,13 @@ static int build_fold_table_impl(jat_model* m, FoldTable& ft, int steps, const f
       KCHK(launch_gather_cast_rows(mod + (int64_t)l * 6 * D, mrow, sh_bf16, steps, D, s));
       GemmArgs e{};
       e.out = bq + (int64_t)l * Nqkv; e.ldo = (int64_t)depth * Nqkv; e.ntok = 1;
-      JCHK(gemm(m, G_OTHER, sh_bf16, D, group_major ? L.wqkv_g : L.wqkv, D, steps, Nqkv, D, EPI_F32, e, s));
+      JCHK(jat_gemm(m, G_OTHER, sh_bf16, D, group_major ? L.wqkv_g : L.wqkv, D, steps, Nqkv, D, EPI_F32, e, s));
     }
     if (need_w1) {
       KCHK(launch_gather_cast_rows(mod + (int64_t)l * 6 * D + 3 * D, mrow, sh_bf16, steps, D, s));
       GemmArgs e{};
       e.out = ft.bf + (int64_t)l * mlp; e.ldo = (int64_t)depth * mlp; e.bias = L.b1; e.ntok = 1;
-      JCHK(gemm(m, G_OTHER, sh_bf16, D, L.w1, D, steps, mlp, D, EPI_F32, e, s));
+      JCHK(jat_gemm(m, G_OTHER, sh_bf16, D, L.w1, D, steps, mlp, D, EPI_F32, e, s));
     }
   }
   return JAT_OK;
@@ -931,20 +788,9 @@ extern "C" int jat_sampler_create(jat_model* m, int32_t B, int32_t T, int32_t st
   const size_t o_z = take(lat), o_lr = take(lat), o_xp = take((size_t)sp->Bf * m->Cin * T * 4);
   const size_t o_tab = take((size_t)steps * row * 4), o_ts = take((size_t)steps * 4), o_ws = take(ws_bytes);
   // Norm folding (default on for RMSNorm models; JAT_FOLD_NORM=0 keeps the norm kernels): decided per sampler.
-  const int fold_env = m->sw.fold_norm;
-  {  // the consumer side reads the row partials lane-linear: needs 4, 8 or 16 slots per row; the three producers of the
-     // residual stream (patch embed, out_proj, fc2: all [M, D]) must agree on the slot count
-    const int M = sp->Bf * ntok;
-    auto var = [&](int site) { return m->variants[site] >= 0 ? m->variants[site] : pick_variant(M, m->D); };
-    const int np = m->D / gemm_variant_wave_n(var(G_OUT));
-    sp->folded = fold_env > 0 && m->cfg.norm_mode == JAT_NORM_RMS_W && m->fold_src_ok && (np == 4 || np == 8 || np == 16) &&
-                 gemm_variant_coalesced(var(G_OUT)) && gemm_variant_coalesced(var(G_FC2)) && gemm_variant_coalesced(var(G_OTHER)) &&
-                 gemm_variant_wave_n(var(G_OUT)) == gemm_variant_wave_n(var(G_FC2)) &&
-                 gemm_variant_wave_n(var(G_OUT)) == gemm_variant_wave_n(var(G_OTHER)) &&
-                 (M > kSplitMaxRows || fold_env >= 2);   // small-M buckets finish fc2 / out_proj with split-K instead (2: force, tests)
-    const int fuse_env = m->sw.fuse_qkv_attn;
-    sp->fused_attn = fuse_env && m->Hq / m->Hkv == 5 && !m->group_copy_stale && ntok == 128 && (sp->Bf * m->Hkv >= 192 || fuse_env == 2);
-  }
+  sp->folded = plan_fold_norms(m, sp->Bf * ntok);
+  const int fuse_env = m->sw.fuse_qkv_attn;
+  sp->fused_attn = fuse_env && m->Hq / m->Hkv == 5 && !m->group_copy_stale && ntok == 128 && (sp->Bf * m->Hkv >= 192 || fuse_env == 2);
   const size_t o_sh = take((size_t)steps * m->D * 2);
   const size_t o_lens = take((size_t)sp->Bf * 4), o_frames = take((size_t)B * 4);
   const size_t o_pc = take((size_t)B * ntok * m->bott * 4);
@@ -1110,6 +956,11 @@ extern "C" int jat_k_norm_modulate(const float* x, const float* w, const float* 
   KCHK(launch_norm_modulate(x, w, shift, scale, mod_bstride, y, M, D, rows_per_batch, norm_mode, (hipStream_t)stream));
   return JAT_OK;
 }
+// -DJAT_TIMELINE build (tools/tl_probe.py): JAT_GEMM_TIMELINE = device address the GEMM kernels write their stamps to
+static unsigned long long* timeline_out() {
+  const char* d = getenv("JAT_GEMM_TIMELINE");
+  return d ? (unsigned long long*)strtoull(d, nullptr, 0) : nullptr;
+}
 extern "C" int jat_k_gemm(const uint16_t* A, const uint16_t* W, const float* bias, void* C, int32_t M, int32_t N,
                           int32_t K, int32_t epilogue, const float* gate, int64_t gate_bstride, int32_t rows_per_batch,
                           int32_t variant, void* stream) {
@@ -1118,30 +969,44 @@ extern "C" int jat_k_gemm(const uint16_t* A, const uint16_t* W, const float* bia
   a.A = A; a.W = W; a.lda = K; a.ldw = K; a.M = M; a.N = N; a.K = K;
   a.out = C; a.ldo = N; a.bias = bias; a.gate = gate; a.gate_bstride = gate_bstride;
   a.ntok = rows_per_batch > 0 ? rows_per_batch : 1;
-  if (const char* d = getenv("JAT_GEMM_TIMELINE")) a.dbg_out = (unsigned long long*)strtoull(d, nullptr, 0);  // tools/tl_probe.py
+  a.dbg_out = timeline_out();
   KCHK(launch_gemm(a, epilogue, variant, (hipStream_t)stream));
   return JAT_OK;
 }
 // split-K slices of C = A W^T: parts[z][M][N] fp32 = the sum over K columns [z K/ksplit, (z+1) K/ksplit); the caller (or the
 // finishing passes of elementwise.hip) adds the slices in order.  The un-folded forward's fc2 / out_proj use it when their
-// tiles leave CUs idle (resid_split); variant 39 = the 224 x 160 k-step-pair tile (M % 224 == 0, N % 160 == 0).
+// tiles leave CUs idle (plan_resid); variant 39 = the 224 x 160 k-step-pair tile (M % 224 == 0, N % 160 == 0).
 extern "C" int jat_k_gemm_splitk(const uint16_t* A, const uint16_t* W, float* parts, int32_t M, int32_t N, int32_t K,
                                  int32_t ksplit, int32_t variant, void* stream) {
   if (!A || !W || !parts || M <= 0 || N <= 0 || ksplit < 2 || K % (64 * ksplit) != 0) return fail(JAT_E_INVALID, "bad argument");
-  if (!gemm_variant_exists(variant)) return fail(JAT_E_INVALID, "unknown variant");
+  if (!gemm_variant(variant)) return fail(JAT_E_INVALID, "unknown variant");
   GemmArgs a{};
   a.A = A; a.W = W; a.lda = K; a.ldw = K; a.M = M; a.N = N; a.K = K / ksplit;
   a.out = parts; a.ldo = N; a.ntok = 1; a.ksplit = ksplit; a.split_stride = (int64_t)M * N;
   KCHK(launch_gemm(a, EPI_F32, variant, (hipStream_t)stream));
   return JAT_OK;
 }
-extern "C" int jat_k_gemm_wave_n(int32_t variant) { return gemm_variant_exists(variant) ? gemm_variant_wave_n(variant) : 0; }
+extern "C" int jat_k_gemm_wave_n(int32_t variant) { return gemm_variant(variant) ? gemm_variant(variant)->wave_n() : 0; }
+// what the forward launches for a GEMM [M, N, K] at a call site (pinned by tests/golden/gemm_plan.json): the per-decision plans
+// where N is the width the site has in the model, a plain GEMM otherwise
+extern "C" int jat_k_gemm_plan(const jat_model* m, int32_t site, int32_t M, int32_t N, int32_t K, int32_t folding, int32_t* variant,
+                               int32_t* ksplit) {
+  if (!m || !variant || !ksplit || site < 0 || site > G_OTHER || M <= 0 || N <= 0 || K <= 0 || K % 64 != 0) return fail(JAT_E_INVALID, "bad argument");
+  const bool f = folding != 0, ws = split_ws_slices(M) > 0;
+  const GemmPlan p = site == G_QKV && N == m->D + 2 * m->kvD         ? plan_qkv(m, M, K, f, ws)
+                     : (site == G_OUT || site == G_FC2) && N == m->D ? plan_resid(m, site, M, K, f, ws)
+                     : site == G_OTHER && N == m->bott               ? plan_patch(m, M, K)
+                                                                     : plan_gemm(m, site, M, N, 1, f);
+  *variant = p.variant; *ksplit = p.ksplit;
+  return JAT_OK;
+}
 extern "C" int jat_k_gemm_fold(const uint16_t* A, const uint16_t* W, const float* bias, void* C, int32_t M, int32_t N, int32_t K,
                                int32_t epilogue, const float* gate, int64_t gate_bstride, int32_t rows_per_batch, uint16_t* hi,
                                uint16_t* lo, float* part_out, const float* part_in, int32_t part_in_np, int32_t variant,
                                void* stream) {
   if (epilogue < 0 || epilogue > EPI_RESID) return fail(JAT_E_INVALID, "epilogue must be 0..3");
-  if (!gemm_variant_exists(variant) || !gemm_variant_coalesced(variant)) return fail(JAT_E_INVALID, "needs a coalesced-epilogue variant");
+  const GemmVariant* t = gemm_variant(variant);
+  if (!t || !t->coalesced()) return fail(JAT_E_INVALID, "needs a coalesced-epilogue variant");
   if (hi && (epilogue != EPI_F32 && epilogue != EPI_RESID)) return fail(JAT_E_INVALID, "producer epilogue must be 0 or 3");
   if (hi && (!lo || !part_out)) return fail(JAT_E_INVALID, "producer needs hi, lo and part_out");
   if (part_in && part_in_np != 4 && part_in_np != 8 && part_in_np != 16) return fail(JAT_E_INVALID, "part_in_np must be 4, 8 or 16");
@@ -1150,9 +1015,9 @@ extern "C" int jat_k_gemm_fold(const uint16_t* A, const uint16_t* W, const float
   a.out = C; a.ldo = N; a.bias = bias; a.gate = gate; a.gate_bstride = gate_bstride;
   a.ntok = rows_per_batch > 0 ? rows_per_batch : 1;
   a.fold_out = hi; a.fold_lo = lo; a.fold_part = part_out;
-  if (hi) a.fold_np = N / gemm_variant_wave_n(variant);
+  if (hi) a.fold_np = N / t->wave_n();
   a.rs_part = part_in; a.rs_np = part_in_np;
-  if (const char* d = getenv("JAT_GEMM_TIMELINE")) a.dbg_out = (unsigned long long*)strtoull(d, nullptr, 0);  // tools/tl_probe.py
+  a.dbg_out = timeline_out();
   KCHK(launch_gemm(a, epilogue, variant, (hipStream_t)stream));
   return JAT_OK;
 }
@@ -1164,9 +1029,9 @@ extern "C" int jat_k_qkv_attn(const uint16_t* A, const uint16_t* Wg, const float
   GemmArgs a{};
   a.A = A; a.lda = K; a.W = Wg; a.ldw = K; a.M = M; a.N = Hkv * 448; a.K = K;
   a.out = out; a.ldo = (int64_t)Hkv * 320; a.ntok = 128; a.rope_inv_freq = rope_inv_freq; a.bias = bias;
-  a.attn_scale_log2e = 0.125f * 1.4426950408889634f;
+  a.attn_scale_log2e = kAttnScaleLog2e;
   a.rs_part = part_in; a.rs_np = part_in_np;
-  if (const char* d = getenv("JAT_GEMM_TIMELINE")) a.dbg_out = (unsigned long long*)strtoull(d, nullptr, 0);
+  a.dbg_out = timeline_out();
   KCHK(launch_qkv_attn(a, (hipStream_t)stream));
   return JAT_OK;
 }
@@ -1193,7 +1058,7 @@ extern "C" int jat_k_attention(const uint16_t* q, const uint16_t* k, const uint1
   AttnArgs a{};
   a.q = q; a.k = k; a.vt = vt; a.o = o; a.ldq = (int64_t)Hq * 64; a.ldk = (int64_t)Hkv * 64; a.ldo = (int64_t)Hq * 64;
   a.B = B; a.N = N; a.Hq = Hq; a.Hkv = Hkv; a.npad = Npad;
-  a.scale_log2e = 0.125f * 1.4426950408889634f;
+  a.scale_log2e = kAttnScaleLog2e;
   KCHK(launch_attention(a, (hipStream_t)stream));
   return JAT_OK;
 }

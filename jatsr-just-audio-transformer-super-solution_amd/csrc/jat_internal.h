@@ -84,8 +84,8 @@ struct jat_model {
   bf16_t *pe_w1, *pe_w2, *wada, *wfinal;
   float *pe_b1, *pe_b2, *te_w1, *te_b1, *te_w2, *te_b2, *bada, *final_norm, *bfinal, *rope_cos, *rope_sin, *rope_invf;
   std::vector<LayerW> layers;
-  // GEMM tile/pipeline variant per call site: qkv, out_proj, fc1, fc2, everything else (gemm.hip table)
-  int variants[5] = {-1, -1, -1, -1, -1};  // -1: choose by shape (pick_variant)
+  // GEMM tile/pipeline variant per call site: qkv, out_proj, fc1, fc2, everything else (gemm_variants.h)
+  int variants[5] = {-1, -1, -1, -1, -1};  // -1: choose by shape (gemm_plan.h)
   mutable int last_fold_np = 0;            // partial-sum slots per row written by the latest folding producer
   float* wfinal32 = nullptr;               // fp32 copy of final_layer.1.weight (fold source)
   bool fold_src_ok = false;                // fp32 copies match the packed weights (false after a training re-pack)
@@ -95,8 +95,10 @@ struct jat_model {
 };
 enum { G_QKV = 0, G_OUT = 1, G_FC1 = 2, G_FC2 = 3, G_OTHER = 4 };
 
-// C[M,N] = A[M,K] W[N,K]^T through the variant chooser / profiling bracket of jat_api.cpp
+// C[M,N] = A[M,K] W[N,K]^T through the planner (gemm_plan.h; plan == nullptr: a plain GEMM of the call site) and the profiling
+// bracket of jat_api.cpp
+struct GemmPlan;
 int jat_gemm(const jat_model* m, int site, const bf16_t* A, int64_t lda, const bf16_t* W, int64_t ldw, int M, int N, int K,
-             int epi, GemmArgs extra, hipStream_t s);
+             int epi, GemmArgs extra, hipStream_t s, const GemmPlan* plan = nullptr);
 // (re)pack the bf16 / fp32 device copies of the model from named fp32 tensors; sync_tables: also (re)build the RoPE tables
 int jat_pack_weights(jat_model* m, const jat_tensor_ref* named, int32_t n, hipStream_t s, bool build_tables);

@@ -64,19 +64,14 @@ struct GemmArgs {
   // (fp32 elements); the caller sums the partials in fixed order (launch_sum_partials).  0 / 1: off.
   int ksplit;
   int64_t split_stride;
-  int variant_hint;   // host side only (jat_gemm): > 0 = the tile variant the caller's split plan was made for
+  int variant_hint;   // unused (the plan travels beside the arguments: jat_gemm); kept so that the kernels' argument block keeps its size
 };
 
-// variant: index into the tile/pipeline table of gemm.hip (gemm_variant_tile gives its BM x BN)
+// variant: an id of the tile variant table (gemm_variants.h); retired and unknown ids are rejected
 hipError_t launch_gemm(const GemmArgs& a, int epi, int variant, hipStream_t s);
-int gemm_num_variants();
-bool gemm_variant_exists(int variant);   // ids of retired variants are rejected by launch_gemm
 // Fused QKV projection + RoPE + attention for ntok == 128 (W = group-major fused weight [Hkv][5*64+64+64][K]):
 // one block per (sample, KV group); a.out = attention output bf16 [M, D]; a.N = Hkv * 448.
 hipError_t launch_qkv_attn(const GemmArgs& a, hipStream_t s);
-void gemm_variant_tile(int variant, int* bm, int* bn);
-int gemm_variant_wave_n(int variant);   // columns per wave tile (fold_part slot width)
-bool gemm_variant_coalesced(int variant);
 
 // ---- attention -----------------------------------------------------------------------------------
 struct AttnArgs {

@@ -168,3 +168,53 @@ def test_fast_gelu_expression_is_far_below_a_bf16_ulp():
     big = np.array([10.0, 100.0, 1e4], np.float32)
     assert np.all(np.abs(gelu_fast(big) / big - 1) < 1.2e-5)
     assert np.all(np.abs(gelu_fast(-big)) < 1.2e-5 * big)
+
+
+def test_gemm_plan_matches_the_recorded_plans():
+    """Which tile variant and K-split the forward gives each GEMM (csrc/gemm_plan.cpp through jat_k_gemm_plan) against
+    tests/golden/gemm_plan.json, recorded before the planner was moved out of jat_api.cpp (tools/gen_gemm_plan_golden.py says
+    how): every entry, exactly.  The chooser reads its A/B variables once per process, so the plans are collected in a child
+    process without them."""
+    import json
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    try:
+        import gen_gemm_plan_golden as G
+    finally:
+        sys.path.pop(0)
+    env = {k: v for k, v in os.environ.items() if k not in G.CHOOSER_ENV}
+    got = json.loads(subprocess.run([sys.executable, os.path.join(ROOT, "tools", "gen_gemm_plan_golden.py"), "--print"],
+                                    capture_output=True, text=True, check=True, env=env, cwd=ROOT).stdout)
+    want = json.load(open(G.PATH))
+    assert got["M"] == want["M"] == G.MS and got["NK"] == want["NK"]
+    assert set(got["plans"]) == set(want["plans"]) == set(G.MODELS)
+    n = 0
+    for model, by_switch in want["plans"].items():
+        assert set(got["plans"][model]) == set(by_switch) == set(G.SWITCHES)
+        for sw, table in by_switch.items():
+            for site in range(5):
+                for folding in (0, 1):
+                    for i, (N, K) in enumerate(want["NK"][model]):
+                        for j, M in enumerate(want["M"]):
+                            assert got["plans"][model][sw][site][folding][i][j] == table[site][folding][i][j], \
+                                (model, sw, site, folding, M, N, K)
+                            n += 1
+    assert n == 2 * 3 * 5 * 2 * 9 * len(G.MS)
+
+
+def test_gemm_variant_table_is_consistent():
+    """The variant table (csrc/gemm_variants.h) against itself: the wave-tile width of every id 0..39 is what it was before the
+    table replaced the hand-kept arrays (recorded in tests/golden/gemm_plan.json), and the live ids are the ones the GPU tests
+    sweep (tests/test_gpu_kernels.py LIVE_VARIANTS)."""
+    import json
+    want = json.load(open(os.path.join(ROOT, "tests", "golden", "gemm_plan.json")))["wave_n"]
+    got = [L.lib().jat_k_gemm_wave_n(v) for v in range(40)]
+    assert len(want) == 40 and got == want
+    src = open(os.path.join(ROOT, "tests", "test_gpu_kernels.py")).read()
+    live = [int(v) for v in re.search(r"^LIVE_VARIANTS = \[([0-9, ]+)\]", src, re.M).group(1).split(",")]
+    assert [v for v in range(40) if got[v]] == live
+    assert L.lib().jat_k_gemm_wave_n(-1) == 0 and L.lib().jat_k_gemm_wave_n(40) == 0
+    # every plan the forward makes names a live variant
+    plans = json.load(open(os.path.join(ROOT, "tests", "golden", "gemm_plan.json")))["plans"]
+    used = {p[0] for m in plans.values() for t in m.values() for a in t for b in a for c in b for p in c}
+    assert used <= set(live)
