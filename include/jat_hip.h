@@ -474,6 +474,33 @@ int jat_audio_metrics_run(jat_audio_metrics* h, const float* pred, const float* 
  * signal rides in the imaginary part of the same transforms; y and Y are null together. */
 int jat_stft(jat_audio_metrics* h, const float* x, const float* y, int32_t B, int64_t L, void* X, void* Y, void* stream);
 
+/* ---- training data: batch assembly from a device-resident fp16 latent store, per-step monitor sums ---------------- */
+/* Replaces LatentDataset / ValidationDataset.__getitem__ + collate + the host-to-device copy + the two normalisations
+ * (train_ddp_v3mod2.py:509-535, 561-597, 849-857) by one launch.  For sample b of B the device tables give the address of
+ * its HR and LR source (fp16, row-major [C, len[b]], as the latent files store them; 2-byte aligned), its length len[b] >= 1
+ * and its crop start start[b] >= 0.  For every b, c, j < T:
+ *   out[b, c, j] = (float(src_b[c, (start[b] + j) mod len[b]]) - mean[c]) / std[c]
+ * in fp32, the expression of jat_channel_affine, so the result has the bits of jat_channel_affine(crop.float()); with the
+ * four statistics vectors null (all or none) it is the plain conversion.  A crop that does not wrap is fetched as whole
+ * aligned 16-byte lines: the kernel reads the 16-byte-aligned lines that enclose each crop row, up to 14 bytes before the
+ * first and after the last element of the [C, len] array, so those lines must be readable (true of any array inside a
+ * device allocation that starts and ends on 16-byte boundaries, as hipMalloc's and PyTorch's do; not of an array placed by
+ * a 2-byte sub-allocator at the very edge of a mapping).  The bytes outside the crop are never used.  The mod is the loop-repeat of clips shorter
+ * than T (:520-524); with start[b] + T <= len[b] nothing wraps and the row is fetched with 16-byte loads.  hr_out, lr_out:
+ * fp32 [B, C, T], 16-byte aligned, written with plain 16-byte (T % 4 == 0) or 8-byte vector stores.  T <= 8176.  No
+ * atomics: the output depends on the inputs alone.  A table entry with len < 1 or a null address leaves its rows as they were. */
+int jat_latent_gather(const void* const* hr_src, const void* const* lr_src, const int64_t* len, const int64_t* start,
+                      const float* hr_mean, const float* hr_std, const float* lr_mean, const float* lr_std, float* hr_out,
+                      float* lr_out, int32_t B, int32_t C, int32_t T, void* stream);
+/* The sums behind the per-step figures the reference logs (train_ddp_v3mod2.py:902-919: PredictionMean, PredictionStd,
+ * SNR_dB, CondNoiseStd) in one pass over pred, target (= hr_norm) and the optional cond_clean (= lr_norm before the condition
+ * noise), each fp32 [n], 16-byte aligned:  out[6] fp64 (device) = sum p, sum p^2, sum h^2, sum (p - h)^2, sum l, sum l^2
+ * (the last two 0 without cond_clean).  Terms are formed and added in fp64; two stages in a fixed order (a constant number
+ * of partial sums in `work`, then one block), no atomics: the same bits from run to run.  work: JAT_MONITOR_WORK_BYTES. */
+#define JAT_MONITOR_WORK_BYTES 49152
+int jat_train_monitor(const float* pred, const float* target, const float* cond_clean, int64_t n, double* out, void* work,
+                      size_t work_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -21,6 +21,10 @@ _LAZY = {
     "stft": "metrics", "mel_filterbank": "metrics", "calculate_lsd": "metrics", "calculate_mel_loss": "metrics",
     "calculate_multi_scale_mel_loss": "metrics", "evaluate": "metrics", "load_audio": "metrics",
     "Trainer": "train", "u_shaped_timestep_sampling": "train", "get_lr": "train", "GradScaler": "train",
+    "train_monitor": "train", "monitor_figures": "train",
+    "LatentStore": "data", "epoch_batches": "data", "val_crop_start": "data", "train_crop_start": "data",
+    "train_batch_plan": "data", "val_batch_plan": "data",
+    "find_latest_checkpoint_dir": "fit", "resolve_run_dir": "fit",
 }
 __all__ = ["recipe"] + sorted(_LAZY)
 

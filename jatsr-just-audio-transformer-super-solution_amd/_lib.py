@@ -133,7 +133,10 @@ SIGNATURES = {
     "jat_audio_metrics_workspace_bytes": (C.c_int, [_VP, _I32, _I64, C.POINTER(_SZ)]),
     "jat_audio_metrics_run": (C.c_int, [_VP, _VP, _VP, _I32, _I64, _I32, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "jat_stft": (C.c_int, [_VP, _VP, _VP, _I32, _I64, _VP, _VP, _VP]),
+    "jat_latent_gather": (C.c_int, [_VP] * 10 + [_I32] * 3 + [_VP]),
+    "jat_train_monitor": (C.c_int, [_VP, _VP, _VP, _I64, _VP, _VP, _SZ, _VP]),
 }
+MONITOR_WORK_BYTES = 49152   # JAT_MONITOR_WORK_BYTES
 
 GRAD_HOOK = C.CFUNCTYPE(None, C.c_int64, C.c_int64, C.c_void_p)   # jat_trainer_set_grad_hook callback
 

@@ -110,6 +110,40 @@ def reduce_validation_sums(acc, group=None):
     return float(acc[0]) / steps, metrics
 
 
+def train_monitor(pred, target, cond_clean=None):
+    """-> fp64 [6] on the device: sum p, sum p^2, sum h^2, sum (p - h)^2, sum l, sum l^2 over fp32 tensors of one shape
+    (`jat_train_monitor`: fp64 terms, fixed-order two-stage sum, the same bits from run to run)."""
+    tensors = [x.contiguous() for x in (pred, target) + ((cond_clean,) if cond_clean is not None else ())]
+    for x in tensors:
+        if x.dtype != torch.float32 or not x.is_cuda or x.shape != tensors[0].shape:
+            raise ValueError(f"train_monitor: expected fp32 CUDA tensors of one shape, got {tuple(x.shape)} {x.dtype} on {x.device}")
+    out = torch.empty(6, dtype=torch.float64, device=pred.device)
+    work = torch.empty(L.MONITOR_WORK_BYTES, dtype=torch.uint8, device=pred.device)
+    L.check(L.lib().jat_train_monitor(L.ptr(tensors[0]), L.ptr(tensors[1]), L.ptr(tensors[2]) if len(tensors) > 2 else None,
+                                      tensors[0].numel(), L.ptr(out), L.ptr(work), work.numel(), L.stream_ptr()))
+    return out
+
+
+def monitor_figures(sums, n, condition_noise_ratio=0.0, use_adaptive_noise=True):
+    """The six sums of `train_monitor` over n elements -> the reference's logged figures (train_ddp_v3mod2.py:902-919):
+    pred_mean, pred_std (unbiased, Tensor.std()), snr_db = 10 log10(mean h^2 / (mean (p - h)^2 + 1e-8)), cond_noise_std =
+    ratio * clamp(std(l), 0.5, 2.0) with adaptive noise, else ratio."""
+    sp, spp, shh, sdd, sl, sll = (float(v) for v in sums)
+
+    def std(s1, s2):
+        return math.sqrt(max(s2 - s1 * s1 / n, 0.0) / (n - 1)) if n > 1 else float("nan")
+    figures = dict(pred_mean=sp / n, pred_std=std(sp, spp), snr_db=10.0 * math.log10((shh / n) / (sdd / n + 1e-8)) if shh > 0 else float("-inf"))
+    figures["cond_noise_std"] = (condition_noise_ratio * min(max(std(sl, sll), 0.5), 2.0) if use_adaptive_noise
+                                 else float(condition_noise_ratio))
+    return figures
+
+
+def _check_norm_batch(x, device):
+    if not torch.is_tensor(x) or x.dtype != torch.float32 or x.device != device or x.dim() != 3:
+        raise ValueError("normalised=True takes fp32 [B, C, T] tensors on the trainer's device")
+    return x.contiguous()
+
+
 class Trainer:
     """One rank of the reference training loop.  Hyper-parameter names and defaults are TrainConfig's
     (train_ddp_v3m2.py:55-101)."""
@@ -130,6 +164,13 @@ class Trainer:
         amp_dtype: "bf16" (train_ddp_v3m2.py:545) or "fp16" (`torch.amp.autocast('cuda')` of train_ddp_v3mod2.py:854, with
         the dynamic loss scale of :745); must match the operand dtype of the loaded library, which is a process-level
         choice (JAT_OPERAND_DTYPE=fp16 loads libjat_hip_fp16.so).  None: whatever the library is."""
+        # argument errors first: nothing below (the release of the model's previous trainer, 15-28 GB of new workspace) has
+        # happened when a mistyped flag is reported
+        if loss not in ("mse", "charbonnier"):
+            raise ValueError(f"loss must be 'mse' or 'charbonnier', got {loss!r}")
+        if loss == "charbonnier" and float(latent_loss_weight) != 0.0:
+            raise ValueError("the latent perceptual loss is defined on top of the MSE loss (train_ddp_v3mod2.py:889-896); "
+                             "the Charbonnier trainer (train_ddp_v3m2mod1.py) has no latent term")
         L.require_gpu()
         have = L.operand_dtype()
         want = {None: have, "bf16": "bf16", "bfloat16": "bf16", "fp16": "fp16", "float16": "fp16"}[amp_dtype]
@@ -205,11 +246,6 @@ class Trainer:
                                 ms_weight=float(ms_loss_weight), consistency_weight=float(consistency_weight),
                                 low_freq_phase_ratio=float(low_freq_phase_ratio), strict_cutoff=float(strict_cutoff),
                                 soft_cutoff=float(soft_cutoff))
-        if loss not in ("mse", "charbonnier"):
-            raise ValueError(f"loss must be 'mse' or 'charbonnier', got {loss!r}")
-        if loss == "charbonnier" and float(latent_loss_weight) != 0.0:
-            raise ValueError("the latent perceptual loss is defined on top of the MSE loss (train_ddp_v3mod2.py:889-896); "
-                             "the Charbonnier trainer (train_ddp_v3m2mod1.py) has no latent term")
         self.loss, self.charbonnier_eps = loss, float(charbonnier_eps)
         L.check(L.lib().jat_trainer_set_latent_loss(self.ptr, *self.latent_loss.values()))
         L.check(L.lib().jat_trainer_set_charbonnier(self.ptr, self.charbonnier_eps if loss == "charbonnier" else 0.0))
@@ -387,21 +423,40 @@ class Trainer:
         loss, gnorm = self.optimizer_step()
         return dict(loss=loss, grad_norm=gnorm, lr=self.last_lr, step=self.global_step)
 
+    def step_normalised(self, hr_norm, lr_norm, monitor=False, lr=None):
+        """One optimisation step on latents that are already normalised (what `LatentStore.batch` returns with the
+        statistics): prepare -> forward_backward(..., cond_clean=lr_norm) -> optimizer_step, `train_step` without its two
+        normalisation passes.  monitor=True also keeps the prediction and returns the figures the reference logs
+        (train_ddp_v3mod2.py:902-919): snr_db, pred_mean, pred_std, cond_noise_std, from one `jat_train_monitor` pass."""
+        z_t, t, cond = self.prepare(hr_norm, lr_norm)
+        pred = self.forward_backward(z_t, t, cond, hr_norm, want_pred=monitor, cond_clean=lr_norm)
+        sums = train_monitor(pred, hr_norm, lr_norm) if monitor else None      # queued before the step's one host sync
+        loss, gnorm = self.optimizer_step(lr)
+        out = dict(loss=loss, grad_norm=gnorm, lr=self.last_lr, step=self.global_step)
+        if monitor:
+            out.update(monitor_figures(sums.tolist(), pred.numel(), self.condition_noise_ratio, self.use_adaptive_noise))
+        return out
+
     # -- validation (train_ddp_v3mod2.py:1026-1118 / train_ddp_v3m2.py:695-745) -------------------------------------------
     @torch.no_grad()
-    def validate(self, batches, hr_mean, hr_std, lr_mean, lr_std, t=None, noise=None):
+    def validate(self, batches, hr_mean=None, hr_std=None, lr_mean=None, lr_std=None, t=None, noise=None, normalised=False):
         """Eval-mode loss over an iterable of (hr, lr) raw-latent batches: uniform t, no condition noise, no CFG dropout,
         no Dropout / DropPath; the same loss as the training step.  Returns (avg_loss, loss_std, metrics) — the
         reference's triple; the sums of all ranks are combined by ONE all-reduce of an 8-float vector (the reference
-        issues seven 1-float all-reduces, :1087-1096).  `t` / `noise`: optional per-batch lists (tests)."""
+        issues seven 1-float all-reduces, :1087-1096).  `t` / `noise`: optional per-batch lists (tests).
+        normalised=True: the batches are fp32 device tensors that are normalised already (`LatentStore.batch` with the
+        statistics); the four vectors are then not used."""
         from .sampler import channel_affine
         acc = torch.zeros(8, dtype=torch.float64, device=self.device)   # loss, steps, mse, freq, ms, cons, latent, -
         losses = []
         ll = self.latent_loss
         out6 = torch.zeros(6, dtype=torch.float32, device=self.device)
         for i, (hr, lr) in enumerate(batches):
-            hr_norm = channel_affine(hr.to(self.device, torch.float32), hr_mean, hr_std)
-            lr_norm = channel_affine(lr.to(self.device, torch.float32), lr_mean, lr_std)
+            if normalised:
+                hr_norm, lr_norm = _check_norm_batch(hr, self.device), _check_norm_batch(lr, self.device)
+            else:
+                hr_norm = channel_affine(hr.to(self.device, torch.float32), hr_mean, hr_std)
+                lr_norm = channel_affine(lr.to(self.device, torch.float32), lr_mean, lr_std)
             Bv, Cv, Tv = hr_norm.shape
             tt = t[i].to(self.device, torch.float32) if t is not None else torch.rand(Bv, device=self.device, generator=self.gen)
             nz = noise[i].to(self.device) if noise is not None else torch.randn(hr_norm.shape, device=self.device, generator=self.gen)
@@ -459,11 +514,14 @@ class Trainer:
             self.exp_avg_sq[off:off + n].view(shape).copy_(st["exp_avg_sq"].to(self.device, torch.float32))
             self.opt_step = int(float(st["step"]))       # AdamW's own counter: bias correction resumes where it stopped
 
-    def save_checkpoint(self, path, epoch=0, best_val_loss=float("inf")):
+    def save_checkpoint(self, path, epoch=0, best_val_loss=float("inf"), extra=None):
+        """The reference's checkpoint dict (train_ddp_v3mod2.py:1137-1146); `extra`: further entries merged into it."""
         ck = dict(epoch=epoch, global_step=self.global_step, best_val_loss=best_val_loss,
                   model_state_dict={k: v.detach().cpu().clone() for k, v in self.model.state_dict().items()},
                   optimizer_state_dict=self.optimizer_state_dict(), scaler_state_dict=self.scaler.state_dict(),
                   config=dict(self.model.config(), dropout=max(self.dropout), drop_path_rate=max(self.drop_path)))
+        if extra:
+            ck.update(extra)
         torch.save(ck, path)
         return ck
 
