@@ -15,6 +15,8 @@ pytestmark = pytest.mark.gpu
 
 import jatsr_amd._lib as L  # noqa: E402
 
+import forward_ref as R  # noqa: E402
+
 # operand dtype of the loaded library: bf16, or fp16 when the process runs with JAT_OPERAND_DTYPE=fp16 (the v3mod2 trainer's
 # autocast dtype; tests/test_gpu_fp16.py re-runs this module that way).  fp16 has 3 more mantissa bits: same gates hold.
 OP = torch.float16 if L.OPERAND_DTYPE == "fp16" else torch.bfloat16
@@ -382,6 +384,98 @@ def test_attention_spiky_rows():
     ref = _attention_ref(qf, kf, vf, B, N, Hq, Hkv)
     assert rel(o, ref) < 6e-3
     assert (o.double() - ref).abs().max() < 2e-2 * float(ref.abs().max())
+
+
+def _rope_pair_rows(w):
+    """rows (or bias entries) of q / k heads in the rotate-half pair order of cast_bf16_rope_rows_kernel: inside every head, packed
+    row 2i holds source row i and packed row 2i + 1 holds source row i + 32"""
+    H = w.shape[0] // 64
+    return w.reshape(H, 2, 32, -1).permute(0, 2, 1, 3).reshape(w.shape)
+
+
+def _pack_group_major(q, k, v, Hkv):
+    """[Hkv][5 q heads, the k head, the v head] = 448 rows per KV group, q / k heads pair-interleaved"""
+    return torch.cat([torch.cat([_rope_pair_rows(q[g * 320:(g + 1) * 320]), _rope_pair_rows(k[g * 64:(g + 1) * 64]),
+                                 v[g * 64:(g + 1) * 64]]) for g in range(Hkv)]).contiguous()
+
+
+def _qkv_attn_case(M, K, Hkv, np_, a_scale=1.0):
+    """Runs jat_k_qkv_attn on weights packed here from plain Wq / Wk / Wv, into a poisoned arena; returns what the checks need."""
+    B = M // 128
+    A, Af = bf16_bits(gen((M, K), 300 + K, a_scale))
+    (Wq, Wqf), (Wk, Wkf), (Wv, Wvf) = (bf16_bits(gen((Hkv * r, K), 301 + i, 1.0 / np.sqrt(K))) for i, r in enumerate((320, 64, 64)))
+    Wg = _pack_group_major(Wq, Wk, Wv, Hkv)
+    invf = torch.from_numpy(R.rope_inv_freq()).to(A.device)
+    assert torch.allclose(invf.double(), 10000.0 ** (-2.0 * torch.arange(32, device=A.device).double() / 64), rtol=1e-6)
+    bias = part = rs = None
+    bq = bk = bv = None
+    if np_:
+        bq, bk, bv = gen((Hkv * 320,), 310, 0.3), gen((Hkv * 64,), 311, 0.3), gen((Hkv * 64,), 312, 0.3)
+        bias = _pack_group_major(bq, bk, bv, Hkv)
+        part = gen((M, np_), 313).abs() * K / np_ + 0.1
+        rs = torch.rsqrt(part.double().sum(1) / K + 1e-6).view(B, 128, 1)
+    ld = Hkv * 320
+    arena = torch.full(((M + 128) * ld,), float("nan"), device=A.device).to(OP)
+    out = arena[:M * ld].view(M, ld)
+
+    def launch(a, o, m, p):
+        L.check(L.lib().jat_k_qkv_attn(L.ptr(a), L.ptr(Wg), L.ptr(bias), L.ptr(o), m, Hkv, K, L.ptr(invf), L.ptr(p), np_,
+                                       L.stream_ptr()))
+    launch(A, out, M, part)
+    torch.cuda.synchronize()
+    assert torch.isnan(arena[M * ld:]).all() and torch.isfinite(out).all()     # the 128 guard rows stay poisoned
+    # every sample of the batch equals the same sample run alone, bit for bit
+    for b in range(B):
+        alone = torch.full((128, ld), float("nan"), device=A.device).to(OP)
+        launch(A[b * 128:(b + 1) * 128], alone, 128, part[b * 128:(b + 1) * 128] if np_ else None)
+        assert torch.equal(alone, out[b * 128:(b + 1) * 128]), b
+    refs = []
+    for rnd in (R.identity, R.make_rnd(OP)):
+        refs.append(torch.cat([R.qkv_attention_group(
+            Af.double().view(B, 128, K), Wqf[g * 320:(g + 1) * 320].double(), Wkf[g * 64:(g + 1) * 64].double(),
+            Wvf[g * 64:(g + 1) * 64].double(), rnd, invf.cpu().numpy(),
+            *((bq[g * 320:(g + 1) * 320].double(), bk[g * 64:(g + 1) * 64].double(), bv[g * 64:(g + 1) * 64].double(), rs)
+              if np_ else ())) for g in range(Hkv)], -1).view(M, ld))
+    exact, rounded = refs
+    err, e0 = rel(out, exact), rel(rounded, exact)
+    ma, ma0 = float((out.double() - exact).abs().max()), float((rounded - exact).abs().max())
+    print(f"qkv_attn M={M} K={K} Hkv={Hkv} np={np_}: error {err:.3e} / E0 {e0:.3e} = {err / e0:.3f}, max-abs {ma:.3e} / {ma0:.3e} = "
+          f"{ma / ma0:.3f}")
+    return err, e0, ma, ma0
+
+
+@pytest.mark.parametrize("np_", [0, 4, 8, 16])
+@pytest.mark.parametrize("Hkv", [4, 1])
+@pytest.mark.parametrize("K", [64, 128, 192, 1280])
+@pytest.mark.parametrize("M", [128, 256, 7168])
+def test_qkv_attn_fused_kernel(M, K, Hkv, np_):
+    """jat_k_qkv_attn (q/k/v projection + RoPE + GQA attention of one (sample, KV group) per block) on its own: the group-major,
+    pair-interleaved weight is packed HERE from plain Wq / Wk / Wv; 1, 2, 3 and 20 K-tiles; 1, 2 and 56 samples; 4 KV groups and 1;
+    without row statistics, and with the folded norms' consumer side (np_ = 4 / 8 / 16 partial sums per row: accumulator rows
+    scaled by rsqrt(sum part / K + 1e-6) before the bias, bias in the packed order).
+    Reference: tests/forward_ref.py `qkv_attention_group` in fp64 on the same rounded A and W, with rope_inv_freq[i] =
+    10000^(-2i/64).  Gate: error against the exact twin (rnd = identity) <= 1.5 E0, E0 = the error of the twin that rounds q, k,
+    v, P and the output — relative L2 and max-abs.  Measured (MI355X, bf16): error / E0 0.998 ... 1.005 over the 96 cases and
+    the spiky one (E0 3.2e-3 ... 3.4e-3), max-abs ratio 1.000.  The output lies in a
+    poisoned arena (128 guard rows stay NaN) and every sample equals its stand-alone run bit for bit."""
+    err, e0, ma, ma0 = _qkv_attn_case(M, K, Hkv, np_)
+    assert err <= 1.5 * e0 and ma <= 1.5 * ma0
+
+
+def test_qkv_attn_fused_kernel_spiky_rows():
+    """Logits of standard deviation ~9 (A scaled by 3): most query rows are dominated by one or two keys, as in
+    test_attention_spiky_rows; same gate."""
+    err, e0, ma, ma0 = _qkv_attn_case(256, 128, 4, 16, a_scale=3.0)
+    assert err <= 1.5 * e0 and ma <= 1.5 * ma0
+
+
+def test_qkv_attn_fused_kernel_rejects_unsupported_shapes():
+    z = torch.zeros(256, 128, dtype=OP, device=dev())
+    w = torch.zeros(448, 128, dtype=OP, device=dev())
+    o = torch.zeros(256, 320, dtype=OP, device=dev())
+    invf = torch.ones(32, device=dev())
+    for M, K in ((100, 128), (128, 96)):     # M must be whole 128-token samples, K whole 64-deep K-tiles
+        assert L.lib().jat_k_qkv_attn(L.ptr(z), L.ptr(w), None, L.ptr(o), M, 1, K, L.ptr(invf), None, 0, L.stream_ptr()) != 0
 
 
 @pytest.mark.parametrize("use_cfg,t", [(True, 0.3), (False, 0.5), (True, 0.9995)])
