@@ -76,7 +76,8 @@ int jat_model_load_weights(jat_model* m, const jat_tensor_ref* named, int32_t n,
 int jat_model_workspace_bytes(const jat_model* m, int32_t B, int32_t T, size_t* out);
 /* Behaviour switches of this handle.  Their defaults come from the JAT_* environment variables, which are read ONCE, in
  * jat_model_create (INTEGRATION.md "Environment switches"); nothing on the enqueue path reads the environment.  Names:
- * "fuse_qkv_attn" (0 / 1 / 2), "qkv_split", "fuse_finish", "fold_norm" (0 / 1 / 2), "split_patch", "patch_split", "fold_cap_mb".
+ * "fuse_qkv_attn" (0 / 1 / 2), "qkv_split", "fuse_finish", "fold_norm" (0 / 1 / 2), "split_patch", "patch_split", "fold_cap_mb",
+ * "fuse_euler" (CFG sampler: CFG combine + Euler step inside the final Linear, the latent kept in patch layout over the steps).
  * Takes effect for forwards enqueued and samplers created afterwards. */
 int jat_model_set_switch(jat_model* m, const char* name, int32_t value);
 
@@ -108,6 +109,11 @@ void jat_sampler_destroy(jat_sampler* s);
  * fused QKV + RoPE + attention kernel, *fold_bytes = size of the folded-weight table shared through the model.  Any pointer
  * may be NULL. */
 int jat_sampler_info(const jat_sampler* sampler, int32_t* folded, int32_t* fused_attn, int64_t* fold_bytes);
+/* 1 when the sampler's steps run the fused tail: the final Linear walks the cond / uncond rows in pairs and applies
+ * the CFG combine + Euler update (:161-179) in its epilogue to the latent kept in patch layout, so no unpatchify store, no
+ * jat_cfg_euler_step launch and no per-step patchify run.  Needs cfg_scale != 1, the "split_patch" and "fuse_euler" switches, T % 4 == 0
+ * and a final-Linear tile that has the epilogue; 0: the separate launches.  Both produce the same bits. */
+int jat_sampler_tail_fused(const jat_sampler* sampler);
 /* Rows of the bucket that are SHORTER than T (the last chunk of a file, infer_test_v3m2.py:353-361,370-398, batched with
  * the full-length chunks instead of sampled alone): frames[b] in (0, T] valid latent frames of row b; the caller zero-pads
  * lr_latent / z0 beyond them and ignores z_out there.  Attention masks the padded keys, every other operator is row-wise,
@@ -216,6 +222,18 @@ int jat_k_gemm(const uint16_t* A, const uint16_t* W, const float* bias, void* C,
 int jat_k_gemm_fold(const uint16_t* A, const uint16_t* W, const float* bias, void* C, int32_t M, int32_t N, int32_t K,
                     int32_t epilogue, const float* gate, int64_t gate_bstride, int32_t rows_per_batch, uint16_t* hi,
                     uint16_t* lo, float* part_out, const float* part_in, int32_t part_in_np, int32_t variant, void* stream);
+/* The CFG sampler's step tail on caller buffers: the final Linear [M = 2 B ntok, N = 4 C, K] over A = [cond rows ; uncond rows]
+ * (rows_per_batch = ntok tokens per sample; part_in as in jat_k_gemm_fold's consumer side), the CFG combine + Euler update of
+ * jat_cfg_euler_step(t, dt) and the next step's bf16 patch operand a_patch [M/2, N] (frames: optional [B] valid frames per
+ * sample, a_patch reads zero from there on; NULL: all).
+ *   fused != 0: ONE launch; z is the latent in PATCH layout [M/2, N] (element [(b, tok)][c*4 + p] = latent[b][c][4 tok + p]),
+ *     updated in place; xpred is not used.  Variants 20, 28, 33, 35 (csrc/gemm_variants.h).
+ *   fused == 0: the three launches it replaces: unpatchify store into xpred [2B, C, 4 ntok], jat_cfg_euler_step on z [B, C, 4 ntok],
+ *     patchify of z.  Same bits as the fused form, in the other layout. */
+int jat_k_gemm_cfg_euler(const uint16_t* A, const uint16_t* W, const float* bias, int32_t M, int32_t N, int32_t K,
+                         int32_t rows_per_batch, const float* part_in, int32_t part_in_np, float* z, uint16_t* a_patch,
+                         float* xpred, const int32_t* frames, float cfg_scale, float t, float dt, int32_t variant, int32_t fused,
+                         void* stream);
 /* Split-K slices of the same product: parts[z][M][N] fp32 = A[:, z K/ksplit : (z+1) K/ksplit] W[:, same]^T, z < ksplit, no
  * bias; summed in order by the caller / the finishing pass.  This is what the un-folded forward's fc2 and out_proj
  * (jat_audiosr_v3.py:300,306) launch when their tiles would leave CUs idle; variant 39 = the 224 x 160 k-step-pair tile

@@ -4,6 +4,7 @@
 #include "jat_kernels.h"
 #include "jat_gelu.h"
 #include "jat_dtype.h"
+#include "jat_cfg_euler.h"
 #include <cstdlib>
 
 __device__ __forceinline__ unsigned short f2bf_e(float f) { return jat_f2op(f); }
@@ -424,20 +425,20 @@ __global__ void __launch_bounds__(256) cfg_euler_kernel(const float* __restrict_
       float4 c = *(const float4*)(xp + i);
       if (use_cfg) {
         const float4 u = *(const float4*)(xp + n + i);
-        c.x = u.x + cfg_scale * (c.x - u.x); c.y = u.y + cfg_scale * (c.y - u.y);
-        c.z = u.z + cfg_scale * (c.z - u.z); c.w = u.w + cfg_scale * (c.w - u.w);
+        c.x = jat_cfg_combine(c.x, u.x, cfg_scale); c.y = jat_cfg_combine(c.y, u.y, cfg_scale);
+        c.z = jat_cfg_combine(c.z, u.z, cfg_scale); c.w = jat_cfg_combine(c.w, u.w, cfg_scale);
       }
       if (!direct) {
         const float4 zz = *(const float4*)(z + i);
-        c.x = zz.x + __fdiv_rn(c.x - zz.x, denom) * dt; c.y = zz.y + __fdiv_rn(c.y - zz.y, denom) * dt;
-        c.z = zz.z + __fdiv_rn(c.z - zz.z, denom) * dt; c.w = zz.w + __fdiv_rn(c.w - zz.w, denom) * dt;
+        c.x = jat_euler_step(c.x, zz.x, denom, dt); c.y = jat_euler_step(c.y, zz.y, denom, dt);
+        c.z = jat_euler_step(c.z, zz.z, denom, dt); c.w = jat_euler_step(c.w, zz.w, denom, dt);
       }
       *(float4*)(z + i) = c;
     } else {
       for (int64_t j = i; j < n; ++j) {
         float c = xp[j];
-        if (use_cfg) { const float u = xp[n + j]; c = u + cfg_scale * (c - u); }
-        if (!direct) c = z[j] + __fdiv_rn(c - z[j], denom) * dt;
+        if (use_cfg) c = jat_cfg_combine(c, xp[n + j], cfg_scale);
+        if (!direct) c = jat_euler_step(c, z[j], denom, dt);
         z[j] = c;
       }
     }
@@ -453,6 +454,33 @@ hipError_t launch_cfg_euler(const float* xp, float* z, float cfg_scale, float t,
   hipLaunchKernelGGL(cfg_euler_kernel, dim3((unsigned)blocks), dim3(256), 0, s, xp, z, cfg_scale, denom, dt, use_cfg,
                      direct, n_per_half);
   return hipGetLastError();
+}
+
+// ---- the latent between [B, C, T] and patch layout [(b, tok)][c*4 + p], fp32 (T % 4 == 0) -------------------------------
+// The CFG sampler keeps z in patch layout over its steps (EPI_CFG_EULER, gemm.hip); these run once per sampler run, before and
+// after the steps.  One 16-B patch per thread, channel fastest: the patch-layout side is contiguous.
+template <bool TO_PATCH>
+__global__ void __launch_bounds__(256) patch_f32_kernel(const float* __restrict__ in, float* __restrict__ out, int C, int ntok,
+                                                        int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;   // (b * ntok + tok) * C + c: the patch-layout index
+  if (i >= n) return;
+  const int c = (int)(i % C);
+  const int64_t row = i / C, b = row / ntok, tok = row - b * ntok;
+  const int64_t zi = ((b * C + c) * ntok + tok) * 4, pi = i * 4;
+  *(float4*)(out + (TO_PATCH ? pi : zi)) = *(const float4*)(in + (TO_PATCH ? zi : pi));
+}
+template <bool TO_PATCH>
+static hipError_t launch_patch_f32_dir(const float* in, float* out, int B, int C, int T, hipStream_t s) {
+  if (B <= 0 || C <= 0 || T <= 0 || (T & 3) != 0) return hipErrorInvalidValue;
+  const int64_t n = (int64_t)B * C * (T / 4);
+  hipLaunchKernelGGL(patch_f32_kernel<TO_PATCH>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in, out, C, T / 4, n);
+  return hipGetLastError();
+}
+hipError_t launch_patch_f32(const float* z, float* zp, int B, int C, int T, hipStream_t s) {
+  return launch_patch_f32_dir<true>(z, zp, B, C, T, s);
+}
+hipError_t launch_unpatch_f32(const float* zp, float* z, int B, int C, int T, hipStream_t s) {
+  return launch_patch_f32_dir<false>(zp, z, B, C, T, s);
 }
 
 // ---- per-channel (de)normalisation (infer_test_v3m2.py:381-382, 394) -------------------------------------

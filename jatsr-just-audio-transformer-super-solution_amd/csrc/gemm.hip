@@ -28,6 +28,7 @@
 #include "jat_kernels.h"
 #include "jat_dtype.h"
 #include "gemm_variants.h"
+#include "jat_cfg_euler.h"
 
 #include <type_traits>
 #include <utility>
@@ -65,6 +66,26 @@ __device__ __forceinline__ uint2 gelu_pack4(float a, float b, float c, float d) 
 // QKV paths would then differ in the last fp32 bit (visible after rounding to fp16; caught by the bit-identity test).
 __device__ __forceinline__ float2 rope_rot(float a, float b, float c, float s) {
   return float2{__builtin_fmaf(a, c, -(b * s)), __builtin_fmaf(b, c, a * s)};
+}
+
+// The final Linear's pred, acc * rstd + bias, with the product and the sum rounded separately (what the compiler made of
+// EPI_UNPATCH when the bias sat under a branch there).  EPI_UNPATCH and EPI_CFG_EULER both form their preds here, with contraction
+// off, so that the two tails of the sampler agree bit for bit whatever a compiler would fuse.
+__device__ __forceinline__ f32x4 unpatch_pred(f32x4 acc, float rstd, float4 b, bool has_bias) {
+#pragma clang fp contract(off)
+  f32x4 v = acc * rstd;
+  if (has_bias) { v[0] += b.x; v[1] += b.y; v[2] += b.z; v[3] += b.w; }
+  return v;
+}
+// the same with the bias row still in memory (nullptr: none): the load stays under the branch, as EPI_UNPATCH has always had it
+__device__ __forceinline__ f32x4 unpatch_pred(f32x4 acc, float rstd, const float* bias4) {
+#pragma clang fp contract(off)
+  f32x4 v = acc * rstd;
+  if (bias4) {
+    const float4 b = *(const float4*)bias4;
+    v[0] += b.x; v[1] += b.y; v[2] += b.z; v[3] += b.w;
+  }
+  return v;
 }
 
 // consumer side of the norm folding: 1/rms of row m of the A operand from the producer's partial sums (fixed order)
@@ -188,7 +209,14 @@ __global__ void __launch_bounds__((WM * WN + (PIPE == 6 ? 4 : 0)) * 64, (WM * WN
   const int wm = wave / WN, wn = wave % WN;
 
   // ---- block -> tile: XCD-contiguous chunks, then grouped-M order -------------------------------
-  const int tiles_m = (p.M + BM - 1) / BM, tiles_n = p.N / BN;
+  // EPI_CFG_EULER walks PAIRED rows: A = [cond ; uncond] (Mh rows each) and a tile takes its first BM/2 rows from the cond half
+  // and its last BM/2 rows from the matching rows of the uncond half, so that the waves (wm, wn) and (wm + WM/2, wn) hold the two
+  // preds of the same (sample, token, feature) and the block finishes z itself.  m0 stays the tile's first row in tile units
+  // (tile_m * BM), m0h = m0 / 2 its first row inside either half.
+  constexpr bool PR = EPI == EPI_CFG_EULER;
+  static_assert(!PR || (WM % 2 == 0 && PIPE != 6), "paired rows: the wave rows split evenly over the halves; no DMA-wave form");
+  [[maybe_unused]] const int Mh = p.M >> 1;
+  const int tiles_m = PR ? (Mh + BM / 2 - 1) / (BM / 2) : (p.M + BM - 1) / BM, tiles_n = p.N / BN;
   int id;
   {
     const int nwg = gridDim.x, bid = blockIdx.x;
@@ -202,6 +230,12 @@ __global__ void __launch_bounds__((WM * WN + (PIPE == 6 ? 4 : 0)) * 64, (WM * WN
   const int in_g = id % per_group;
   const int m0 = (first_m + in_g % gsz) * BM;
   const int n0 = (in_g / gsz) * BN;
+  [[maybe_unused]] const int m0h = m0 >> 1;
+  // paired rows: the row of A behind tile row r (clamped inside its half, like the plain tiles clamp against M)
+  [[maybe_unused]] auto pair_row = [&](int r) {
+    const int h = r >= BM / 2 ? 1 : 0;
+    return h * Mh + min(m0h + r - h * (BM / 2), Mh - 1);
+  };
 
   // ---- staging addresses (source-side swizzle) ---------------------------------------------------
   const int srow = lane >> 3;
@@ -211,7 +245,7 @@ __global__ void __launch_bounds__((WM * WN + (PIPE == 6 ? 4 : 0)) * 64, (WM * WN
 #pragma unroll
   for (int j = 0; j < AI; ++j) {
     const int r = min(wave + j * NW, PA - 1) * 8 + srow;
-    const int gm = min(m0 + r, p.M - 1);
+    const int gm = PR ? pair_row(r) : min(m0 + r, p.M - 1);
     a_src[j] = p.A + (int64_t)gm * p.lda + schunk * 8;
   }
 #pragma unroll
@@ -278,7 +312,9 @@ __global__ void __launch_bounds__((WM * WN + (PIPE == 6 ? 4 : 0)) * 64, (WM * WN
 #pragma unroll
   for (int i = 0; i < TM; ++i) rstd_rows[i] = 1.0f;
   if (p.rs_part) {
-    rows_rstd_issue<TM>(p, m0 + wm * TM * 16, lane, rstd_raw);
+    // paired rows: a wave's TM * 16 rows are consecutive rows of ONE half (BM / 2 = WM / 2 wave rows)
+    const int rs_row0 = PR ? (wm >= WM / 2 ? Mh : 0) + m0h + (wm % (WM / 2 > 0 ? WM / 2 : 1)) * TM * 16 : m0 + wm * TM * 16;
+    rows_rstd_issue<TM>(p, rs_row0, lane, rstd_raw);
     if constexpr (PIPE != 8) rows_rstd_reduce<TM, 0>(p, rstd_raw, rstd_sums);   // PIPE 8: behind its prologue DMA, below
   }
 
@@ -383,7 +419,7 @@ __global__ void __launch_bounds__((WM * WN + (PIPE == 6 ? 4 : 0)) * 64, (WM * WN
     constexpr int CA0 = (PA0 + 7) / 8, CA1 = (PA1 + 7) / 8, CB0 = (PB0 + 7) / 8, CB1 = (PB1 + 7) / 8;
     constexpr int CTILE = CA0 + CA1 + CB0 + CB1;
     const int grp = wave >> 2;
-    const char* a_base = (const char*)(p.A + (int64_t)m0 * p.lda);
+    const char* a_base = (const char*)(p.A + (int64_t)(PR ? m0h : m0) * p.lda);
     const char* b_base = (const char*)(p.W + (int64_t)n0 * p.ldw);
     // per-lane byte offsets (32-bit, relative to the tile's first row) and wave-uniform LDS offsets of my pieces
     unsigned oa0[CA0], oa1[CA1 > 0 ? CA1 : 1], ob0[CB0], ob1[CB1];
@@ -395,13 +431,15 @@ __global__ void __launch_bounds__((WM * WN + (PIPE == 6 ? 4 : 0)) * 64, (WM * WN
 #pragma unroll
     for (int j = 0; j < CA0; ++j) {
       const int r = piece_row(min(wave + 8 * j, PA0 - 1), TMa * 2, TM, 0);
-      oa0[j] = (unsigned)((min(m0 + r + srow, p.M - 1) - m0) * (int)p.lda * 2 + schunk * 16);
+      oa0[j] = PR ? (unsigned)((pair_row(r + srow) - m0h) * (int)p.lda * 2 + schunk * 16)
+                  : (unsigned)((min(m0 + r + srow, p.M - 1) - m0) * (int)p.lda * 2 + schunk * 16);
       la0[j] = r * 128;
     }
 #pragma unroll
     for (int j = 0; j < CA1; ++j) {
       const int r = piece_row(min(wave + 8 * j, PA1 - 1), TMb * 2, TM, TMa);
-      oa1[j] = (unsigned)((min(m0 + r + srow, p.M - 1) - m0) * (int)p.lda * 2 + schunk * 16);
+      oa1[j] = PR ? (unsigned)((pair_row(r + srow) - m0h) * (int)p.lda * 2 + schunk * 16)
+                  : (unsigned)((min(m0 + r + srow, p.M - 1) - m0) * (int)p.lda * 2 + schunk * 16);
       la1[j] = r * 128;
     }
     auto piece_row_b = [&](int q, int per, int first) {   // the same for a B part, through the column-tile map
@@ -1122,6 +1160,76 @@ __global__ void __launch_bounds__((WM * WN + (PIPE == 6 ? 4 : 0)) * 64, (WM * WN
     return;
   }
 
+  // ---- CFG + Euler on paired rows: the sampler's step tail inside the final Linear.  Every wave forms its preds as EPI_UNPATCH
+  // does; the cond wave (wm < WM/2) and its uncond partner (wm + WM/2, same wn) hold the two preds of the same elements in the
+  // same lanes and registers, and feature n = c*4 + p of token row m IS element [m][n] of the latent in patch layout.  The pair
+  // splits the row tiles (cond wave: [0, TA), uncond wave: [TA, TM)), hands the other's share over through the idle staging
+  // buffers, and each finishes its share: z' (jat_cfg_euler.h) back into zp, bf16(z') into the next step's patch operand.
+  if constexpr (PR) {
+    constexpr int TA = (TM + 1) / 2;
+    constexpr int XPAIR = TM * TN * 1024;              // one 1-KiB slot per accumulator tile of the pair
+    static_assert((NW / 2) * XPAIR <= 2 * STAGE, "exchange buffers do not fit the staging buffers");
+    __builtin_amdgcn_s_barrier();                      // every wave is done reading the staging buffers
+    if (p.M <= 0) return;                              // see the coalesced epilogue
+    const int hc = wm >= WM / 2 ? 1 : 0, wmh = wm - hc * (WM / 2);
+    char* xb = smem + (wmh * WN + wn) * XPAIR + lane * 16;
+    float4 bb[TN];
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+      bb[j] = p.bias ? *(const float4*)(p.bias + nw0 + j * 16 + fg * 4) : float4{0.f, 0.f, 0.f, 0.f};
+    const bool has_bias = p.bias != nullptr;
+#pragma unroll
+    for (int i = 0; i < TM; ++i)
+#pragma unroll
+      for (int j = 0; j < TN; ++j) acc[i][j] = unpatch_pred(acc[i][j], rstd_rows[i], bb[j], has_bias);
+    static_for<0, TM>([&](auto ic) __attribute__((always_inline)) {
+      constexpr int i = decltype(ic)::value;
+      if ((i >= TA) == (hc == 0)) {                    // the partner's share
+#pragma unroll
+        for (int j = 0; j < TN; ++j) *(f32x4*)(xb + (i * TN + j) * 1024) = acc[i][j];
+      }
+    });
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    float* const zp = (float*)p.out;
+    const float cs = p.ce_scale, denom = p.ce_denom, dt = p.ce_dt;
+    const bool direct = p.ce_direct != 0;
+    static_for<0, TM>([&](auto ic) __attribute__((always_inline)) {
+      constexpr int i = decltype(ic)::value;
+      if ((i >= TA) == (hc == 1)) {                    // my share
+        const int mh = m0h + wmh * TM * 16 + i * 16 + frow;
+        if (mh < Mh) {
+          const int b = mh / p.ntok, tok = mh - b * p.ntok;
+          // frames of this token that are valid: patch element p (= register e) is frame 4 tok + e
+          const int left = p.ce_frames ? p.ce_frames[b] - 4 * tok : 4;
+          float* zr = zp + (int64_t)mh * p.ldo + nw0 + fg * 4;
+          bf16_t* ar = p.ce_patch + (int64_t)mh * p.ldo + nw0 + fg * 4;
+          float4 zz[TN];
+          if (!direct) {
+#pragma unroll
+            for (int j = 0; j < TN; ++j) zz[j] = *(const float4*)(zr + j * 16);
+          }
+#pragma unroll
+          for (int j = 0; j < TN; ++j) {
+            const f32x4 o = *(const f32x4*)(xb + (i * TN + j) * 1024);
+            const f32x4 c = hc ? o : acc[i][j], u = hc ? acc[i][j] : o;
+            float x[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) x[e] = jat_cfg_combine(c[e], u[e], cs);
+            if (!direct) {
+              x[0] = jat_euler_step(x[0], zz[j].x, denom, dt); x[1] = jat_euler_step(x[1], zz[j].y, denom, dt);
+              x[2] = jat_euler_step(x[2], zz[j].z, denom, dt); x[3] = jat_euler_step(x[3], zz[j].w, denom, dt);
+            }
+            *(float4*)(zr + j * 16) = float4{x[0], x[1], x[2], x[3]};
+            *(uint2*)(ar + j * 16) = pack4(left > 0 ? x[0] : 0.f, left > 1 ? x[1] : 0.f, left > 2 ? x[2] : 0.f, left > 3 ? x[3] : 0.f);
+          }
+        }
+      }
+    });
+    JAT_TL_FLUSH()
+    return;
+  }
+
   // ---- direct epilogue: lane owns C[m][n..n+3], m = tile row (lane&15), n = 4*(lane>>4) + reg -----------
 #pragma unroll
   for (int i = 0; i < TM; ++i) {
@@ -1137,7 +1245,12 @@ __global__ void __launch_bounds__((WM * WN + (PIPE == 6 ? 4 : 0)) * 64, (WM * WN
     for (int j = 0; j < TN; ++j) {
       const int nt = nw0 + j * 16;          // wave-uniform first column of this 16-wide MFMA tile
       const int n = nt + fg * 4;
-      f32x4 v = acc[i][j] * rstd_d;
+      f32x4 v;
+      if constexpr (EPI == EPI_UNPATCH) {   // the pred, rounded as EPI_CFG_EULER rounds it whatever the compiler would contract
+        v = unpatch_pred(acc[i][j], rstd_d, p.bias ? p.bias + n : nullptr);
+      } else {
+        v = acc[i][j] * rstd_d;
+      }
       if constexpr (EPI == EPI_QKV_ROPE) {
         // Wq / Wk rows are packed pair-interleaved per head (position 2d <- feature d, 2d+1 <- feature d+32),
         // so the RoPE pair (d, d+32) (jat_audiosr_v3.py:87-108) sits in adjacent registers of one lane.
@@ -1158,7 +1271,7 @@ __global__ void __launch_bounds__((WM * WN + (PIPE == 6 ? 4 : 0)) * 64, (WM * WN
           for (int r = 0; r < 4; ++r) dst[(int64_t)r * p.npad] = f2bf(v[r]);
         }
       } else {
-        if (p.bias) {
+        if (EPI != EPI_UNPATCH && p.bias) {
           const float4 bb = *(const float4*)(p.bias + n);
           v[0] += bb.x; v[1] += bb.y; v[2] += bb.z; v[3] += bb.w;
         }
@@ -1883,12 +1996,21 @@ static hipError_t launch_one(const GemmArgs& a, hipStream_t s) {
     attr_set = true;
   }
   if (a.N % BN != 0 || a.K % 64 != 0 || a.M <= 0) return hipErrorInvalidValue;
-  const int tiles = ((a.M + BM - 1) / BM) * (a.N / BN);
+  // paired rows: ceil(Mh / (BM/2)) row tiles; the PIPE 8 loop addresses A rows by 32-bit byte offsets from the tile's first row
+  if (EPI == EPI_CFG_EULER && (a.M % 2 != 0 || !a.out || !a.ce_patch || a.ntok <= 0 || a.ldo < a.N || a.ldo % 4 != 0 ||
+                               (int64_t)a.M * a.lda * 2 >= (1ll << 31)))
+    return hipErrorInvalidValue;
+  const int tiles = (EPI == EPI_CFG_EULER ? (a.M / 2 + BM / 2 - 1) / (BM / 2) : (a.M + BM - 1) / BM) * (a.N / BN);
   if (a.ksplit > 1 && EPI != EPI_F32) return hipErrorInvalidValue;
   hipLaunchKernelGGL(kern, dim3(tiles, a.ksplit > 1 ? a.ksplit : 1), dim3((WM * WN + (PIPE == 6 ? 4 : 0)) * 64), LDS, s, a);
   return hipGetLastError();
 }
 
+// The tiles EPI_CFG_EULER is built for: what the planner can choose for the final Linear [2 B ntok, 4 C, D] (N a multiple of 128):
+// 64 x 128 and 128 x 128 (two blocks per CU) for small batches, 224 x 256 / 256 x 256 quadrant ping-pong for full ones.
+static constexpr bool cfg_euler_tile(int WM, int WN, int TM, int TN, int PIPE, int CE) {
+  return CE == 1 && WM == 2 && TN == 4 && ((PIPE == 2 && WN == 2 && (TM == 2 || TM == 4)) || (PIPE == 8 && WN == 4 && (TM == 7 || TM == 8)));
+}
 template <int WM, int WN, int TM, int TN, int PIPE, int CE = 0>
 static hipError_t launch_epi(const GemmArgs& a, int epi, hipStream_t s) {
   switch (epi) {
@@ -1898,6 +2020,9 @@ static hipError_t launch_epi(const GemmArgs& a, int epi, hipStream_t s) {
     case EPI_RESID: return launch_one<WM, WN, TM, TN, PIPE, CE, EPI_RESID>(a, s);
     case EPI_QKV_ROPE: return launch_one<WM, WN, TM, TN, PIPE, CE, EPI_QKV_ROPE>(a, s);
     case EPI_UNPATCH: return launch_one<WM, WN, TM, TN, PIPE, CE, EPI_UNPATCH>(a, s);
+    case EPI_CFG_EULER:
+      if constexpr (cfg_euler_tile(WM, WN, TM, TN, PIPE, CE)) return launch_one<WM, WN, TM, TN, PIPE, CE, EPI_CFG_EULER>(a, s);
+      break;
   }
   return hipErrorInvalidValue;
 }
@@ -1925,6 +2050,11 @@ static hipError_t launch_rows(int id, const GemmArgs& a, int epi, hipStream_t s,
   hipError_t e = hipErrorInvalidValue;
   (void)((kGemmVariants[I].id == id && ((e = launch_row<I>(a, epi, s)), true)) || ...);
   return e;
+}
+
+bool gemm_cfg_euler_supported(int variant) {
+  const GemmVariant* v = gemm_variant(variant);
+  return v && v->fallback < 0 && cfg_euler_tile(v->WM, v->WN, v->TM, v->TN, v->PIPE, v->CE);
 }
 
 hipError_t launch_gemm(const GemmArgs& a, int epi, int variant, hipStream_t s) {

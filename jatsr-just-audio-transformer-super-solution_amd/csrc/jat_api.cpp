@@ -105,7 +105,7 @@ extern "C" int jat_model_create(const jat_config* c, jat_model** out) {
   auto env_int = [](const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; };
   m->sw.fuse_qkv_attn = env_int("JAT_FUSE_QKV_ATTN", 1); m->sw.qkv_split = env_int("JAT_QKV_SPLIT", 1);
   m->sw.fuse_finish = env_int("JAT_FUSE_FINISH", 1); m->sw.fold_norm = env_int("JAT_FOLD_NORM", 1);
-  m->sw.split_patch = env_int("JAT_SPLIT_PATCH", 1);
+  m->sw.split_patch = env_int("JAT_SPLIT_PATCH", 1); m->sw.fuse_euler = env_int("JAT_FUSE_EULER", 1);
   m->sw.fold_cap_mb = env_int("JAT_FOLD_CAP_MB", 0); m->sw.patch_split = env_int("JAT_PATCH_SPLIT", 1);
   if (const char* v = getenv("JAT_GEMM_VARIANT"))
     for (int i = 0; i < 5; ++i) m->variants[i] = atoi(v);
@@ -123,7 +123,8 @@ extern "C" int jat_model_set_switch(jat_model* m, const char* name, int32_t valu
   const std::string n(name);
   int* slot = n == "fuse_qkv_attn" ? &m->sw.fuse_qkv_attn : n == "qkv_split" ? &m->sw.qkv_split : n == "fuse_finish" ? &m->sw.fuse_finish
             : n == "fold_norm" ? &m->sw.fold_norm : n == "split_patch" ? &m->sw.split_patch
-            : n == "fold_cap_mb" ? &m->sw.fold_cap_mb : n == "patch_split" ? &m->sw.patch_split : nullptr;
+            : n == "fold_cap_mb" ? &m->sw.fold_cap_mb : n == "patch_split" ? &m->sw.patch_split
+            : n == "fuse_euler" ? &m->sw.fuse_euler : nullptr;
   if (!slot) return fail(JAT_E_INVALID, "unknown switch '%s'", name);
   *slot = value;
   return JAT_OK;
@@ -485,12 +486,20 @@ static int patch_linear1(const jat_model* m, const Workspace& w, int rows, int K
   return jat_gemm(m, G_OTHER, w.a_patch, K, m->pe_w1, m->Kp, rows, m->bott, K, EPI_BF16_GELU, e, s, &plan);
 }
 
+// The CFG sampler's fused step tail (EPI_CFG_EULER): the latent lives in patch layout (zp fp32, w.a_patch bf16) over the steps; the
+// final Linear applies the CFG combine + Euler step of time t / step dt itself and writes both for the next step.
+struct FusedTail {
+  float* zp;
+  float cfg_scale, t, dt;
+};
+
 // Whole forward over B batch rows.  x_t rows are read modulo B_src and the condition is zero from batch row
 // cond_zero_from on: this is how the CFG double batch [z;z],[lr;0] (infer_test_v3m2.py:154-156) is fed
 // without materialising the concatenations.  mod == nullptr: compute the modulation from t [B].
 static int forward_impl(const jat_model* m, const Workspace& w, const float* x_t, int B_src, const float* x_cond,
                         int cond_zero_from, const float* t, const float* mod, int64_t mod_bstride, float* x_pred,
-                        int B, int T, hipStream_t s, const Fold* f = nullptr, const float* pc = nullptr) {
+                        int B, int T, hipStream_t s, const Fold* f = nullptr, const float* pc = nullptr,
+                        const FusedTail* tail = nullptr) {
   const int ntok = (T + 3) / 4, M = B * ntok, D = m->D;
   if (!mod) {
     JCHK(time_path(m, w, t, B, s));
@@ -508,7 +517,8 @@ static int forward_impl(const jat_model* m, const Workspace& w, const float* x_t
     // CFG sampler: the first patch-embed Linear is linear in [z ; cond], the z part is the same for the cond and
     // uncond halves and the cond part (pc = patch(lr) @ W1[:, cond]^T, fp32) does not change over the 50 steps:
     // h_cond = gelu(S_z + pc + b1), h_uncond = gelu(S_z + b1) from ONE quarter-size GEMM (M/2 rows, K/2 deep).
-    KCHK(launch_patchify(x_t, nullptr, w.a_patch, B_src, B_src, B_src, m->Cin, 0, T, ntok, s, w.tvalid));
+    // fused tail: w.a_patch already holds patch(z), written by the previous step's final Linear (or by the run's start)
+    if (!tail) KCHK(launch_patchify(x_t, nullptr, w.a_patch, B_src, B_src, B_src, m->Cin, 0, T, ntok, s, w.tvalid));
     JCHK(patch_linear1(m, w, M / 2, m->P * m->Cin, pc, ntok, s));
   } else {
     KCHK(launch_patchify(x_t, x_cond, w.a_patch, B, B_src, cond_zero_from, m->Cin, m->Cc, T, ntok, s, w.tvalid));
@@ -534,7 +544,11 @@ static int forward_impl(const jat_model* m, const Workspace& w, const float* x_t
     GemmArgs e{};
     e.out = x_pred; e.bias = m->bfinal; e.ntok = ntok; e.C_out = m->Cin; e.T_orig = T;
     if (f) e.rs_part = w.part;
-    JCHK(jat_gemm(m, G_OTHER, w.xn, D, f ? f->wfinal : m->wfinal, D, M, m->Fout, D, EPI_UNPATCH, e, s));
+    if (tail) {
+      e.out = tail->zp; e.ldo = m->Fout; e.ce_patch = w.a_patch; e.ce_frames = w.tvalid;
+      e.ce_scale = tail->cfg_scale; e.ce_denom = 1.0f - tail->t + 1e-5f; e.ce_dt = tail->dt; e.ce_direct = !(tail->t < 0.999f);   // launch_cfg_euler
+    }
+    JCHK(jat_gemm(m, G_OTHER, w.xn, D, f ? f->wfinal : m->wfinal, D, M, m->Fout, D, tail ? EPI_CFG_EULER : EPI_UNPATCH, e, s));
   }
   return JAT_OK;
 }
@@ -615,6 +629,8 @@ struct jat_sampler {
   std::vector<float> ts;  // [host] linspace(0,1,steps+1)
   char* blob = nullptr;   // private device allocation
   float *z, *lr, *xpred, *mod_table, *ts_dev;
+  float* zp = nullptr;               // fused tail: the latent in patch layout [B ntok, 4 C] over the steps of a run
+  bool tail_fused = false;           // the final Linear applies CFG + Euler (EPI_CFG_EULER); no cfg_euler / per-step patchify launches
   std::shared_ptr<FoldTable> fold;   // per-step folded weights (RMSNorm models), shared through the model's cache
   bool fused_attn = false;           // this bucket runs the fused QKV+attention kernel (group-major folded weights)
   float* pc = nullptr;   // CFG: patch(lr) @ W1[:, cond]^T, recomputed once per run (split patch embed)
@@ -649,6 +665,22 @@ static int sampler_cond_part(jat_sampler* sp, hipStream_t s) {
   return jat_gemm(m, G_OTHER, sp->w.a_patch, Kc, m->pe_w1 + (int64_t)m->P * m->Cin, m->Kp, sp->B * ntok, m->bott, Kc, EPI_F32, e, s);
 }
 
+// Around the steps of a run (outside the captured graph).  begin: the condition part, then (fused tail) the latent into patch
+// layout, fp32 for the update and bf16 as the first step's patch operand (sampler_cond_part uses a_patch as scratch: after it);
+// end: back to [B, C, T].
+static int sampler_begin(jat_sampler* sp, hipStream_t s) {
+  JCHK(sampler_cond_part(sp, s));
+  if (!sp->tail_fused) return JAT_OK;
+  const jat_model* m = sp->m;
+  KCHK(launch_patch_f32(sp->z, sp->zp, sp->B, m->Cin, sp->T, s));
+  KCHK(launch_patchify(sp->z, nullptr, sp->w.a_patch, sp->B, sp->B, sp->B, m->Cin, 0, sp->T, sp->T / 4, s, sp->w.tvalid));
+  return JAT_OK;
+}
+static int sampler_end(jat_sampler* sp, hipStream_t s) {
+  if (sp->tail_fused) KCHK(launch_unpatch_f32(sp->zp, sp->z, sp->B, sp->m->Cin, sp->T, s));
+  return JAT_OK;
+}
+
 static int sampler_steps(jat_sampler* sp, hipStream_t s) {
   jat_model* m = sp->m;
   const int64_t n_half = (int64_t)sp->B * m->Cin * sp->T;
@@ -665,9 +697,10 @@ static int sampler_steps(jat_sampler* sp, hipStream_t s) {
       f.bf = ft.bf + (int64_t)i * dl * m->mlp;
       f.wfinal = ft.wfinal;
     }
+    const FusedTail tail{sp->zp, sp->cfg_scale, t_curr, dt};
     JCHK(forward_impl(m, sp->w, sp->z, sp->B, sp->lr, sp->B, nullptr, sp->mod_table + i * row, 0, sp->xpred, sp->Bf,
-                      sp->T, s, sp->folded ? &f : nullptr, sp->pc));
-    KCHK(launch_cfg_euler(sp->xpred, sp->z, sp->cfg_scale, t_curr, dt, sp->use_cfg ? 1 : 0, n_half, s));
+                      sp->T, s, sp->folded ? &f : nullptr, sp->pc, sp->tail_fused ? &tail : nullptr));
+    if (!sp->tail_fused) KCHK(launch_cfg_euler(sp->xpred, sp->z, sp->cfg_scale, t_curr, dt, sp->use_cfg ? 1 : 0, n_half, s));
   }
   return JAT_OK;
 }
@@ -785,7 +818,15 @@ extern "C" int jat_sampler_create(jat_model* m, int32_t B, int32_t T, int32_t st
   const size_t ws_bytes = carve(m, Bws, ntok, nullptr).total;
   size_t off = 0;
   auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes, 256); return o; };
-  const size_t o_z = take(lat), o_lr = take(lat), o_xp = take((size_t)sp->Bf * m->Cin * T * 4);
+  // Fused step tail ("fuse_euler"): CFG with the split patch embed (a_patch is then exactly patch(z), [B ntok, 4 C]), whole patches,
+  // and a final-Linear tile that has the epilogue (its A rows are addressed by 32-bit byte offsets); anything else keeps the
+  // unpatchify store + cfg_euler + patchify launches.  The tile must have it whether or not the folded-weight table gets built below.
+  const int Mf = sp->Bf * ntok;
+  sp->tail_fused = m->sw.fuse_euler && sp->use_cfg && m->sw.split_patch && T % 4 == 0 && (int64_t)Mf * m->D * 2 < (1ll << 31) &&
+                   gemm_cfg_euler_supported(plan_gemm(m, G_OTHER, Mf, m->Fout, 1, true).variant) &&
+                   gemm_cfg_euler_supported(plan_gemm(m, G_OTHER, Mf, m->Fout, 1, false).variant);
+  // the fused tail keeps the latent in patch layout (zp) and never stores x_pred; the separate launches need x_pred and no zp
+  const size_t o_z = take(lat), o_lr = take(lat), o_xp = take(sp->tail_fused ? 0 : (size_t)sp->Bf * m->Cin * T * 4);
   const size_t o_tab = take((size_t)steps * row * 4), o_ts = take((size_t)steps * 4), o_ws = take(ws_bytes);
   // Norm folding (default on for RMSNorm models; JAT_FOLD_NORM=0 keeps the norm kernels): decided per sampler.
   sp->folded = plan_fold_norms(m, sp->Bf * ntok);
@@ -794,15 +835,18 @@ extern "C" int jat_sampler_create(jat_model* m, int32_t B, int32_t T, int32_t st
   const size_t o_sh = take((size_t)steps * m->D * 2);
   const size_t o_lens = take((size_t)sp->Bf * 4), o_frames = take((size_t)B * 4);
   const size_t o_pc = take((size_t)B * ntok * m->bott * 4);
+  const size_t o_zp = take(sp->tail_fused ? lat : 0);
   hipError_t e = hipMalloc((void**)&sp->blob, off);
   if (e != hipSuccess) { delete sp; return fail(JAT_E_HIP, "hipMalloc(%zu): %s", off, hipGetErrorString(e)); }
-  sp->z = (float*)(sp->blob + o_z); sp->lr = (float*)(sp->blob + o_lr); sp->xpred = (float*)(sp->blob + o_xp);
+  sp->z = (float*)(sp->blob + o_z); sp->lr = (float*)(sp->blob + o_lr);
+  sp->xpred = sp->tail_fused ? nullptr : (float*)(sp->blob + o_xp);
   sp->mod_table = (float*)(sp->blob + o_tab); sp->ts_dev = (float*)(sp->blob + o_ts);
   sp->ws = sp->blob + o_ws; sp->ws_bytes = ws_bytes;
   bf16_t* sh_bf16 = (bf16_t*)(sp->blob + o_sh);
   sp->lens_dev = (int*)(sp->blob + o_lens);
   sp->frames_dev = (int*)(sp->blob + o_frames);
   if (sp->use_cfg && m->sw.split_patch) sp->pc = (float*)(sp->blob + o_pc);
+  if (sp->tail_fused) sp->zp = (float*)(sp->blob + o_zp);
 
   int rc = JAT_OK;
   auto bail = [&](int code) { jat_sampler_destroy(sp); return code; };
@@ -858,8 +902,9 @@ extern "C" int jat_sampler_create(jat_model* m, int32_t B, int32_t T, int32_t st
   {
     const int saved = sp->steps;
     sp->steps = 1;
-    if ((rc = sampler_cond_part(sp, s)) != JAT_OK) return bail(rc);
+    if ((rc = sampler_begin(sp, s)) != JAT_OK) return bail(rc);
     rc = sampler_steps(sp, s);
+    if (rc == JAT_OK) rc = sampler_end(sp, s);
     sp->steps = saved;
     if (rc != JAT_OK) return bail(rc);
     if (hipStreamSynchronize(s) != hipSuccess)
@@ -892,6 +937,8 @@ extern "C" int jat_sampler_info(const jat_sampler* sp, int32_t* folded, int32_t*
   return JAT_OK;
 }
 
+extern "C" int jat_sampler_tail_fused(const jat_sampler* sp) { return sp && sp->tail_fused ? 1 : 0; }
+
 extern "C" int jat_sampler_set_lengths(jat_sampler* sp, const int32_t* frames, int32_t n, void* stream) {
   if (!sp || !frames) return fail(JAT_E_INVALID, "null argument");
   if (n != sp->B) return fail(JAT_E_INVALID, "need one length per batch row (%d), got %d", sp->B, n);
@@ -919,12 +966,13 @@ extern "C" int jat_sampler_run(jat_sampler* sp, const float* lr_latent, const fl
   const size_t lat = (size_t)sp->B * sp->m->Cin * sp->T * 4;
   HIPCHK(hipMemcpyAsync(sp->lr, lr_latent, lat, hipMemcpyDeviceToDevice, s));
   HIPCHK(hipMemcpyAsync(sp->z, z0, lat, hipMemcpyDeviceToDevice, s));
-  JCHK(sampler_cond_part(sp, s));
+  JCHK(sampler_begin(sp, s));
   if (use_graph) {
     HIPCHK(hipGraphLaunch(sp->exec, s));
   } else {
     JCHK(sampler_steps(sp, s));
   }
+  JCHK(sampler_end(sp, s));
   HIPCHK(hipMemcpyAsync(z_out, sp->z, lat, hipMemcpyDeviceToDevice, s));
   return JAT_OK;
 }
@@ -1019,6 +1067,37 @@ extern "C" int jat_k_gemm_fold(const uint16_t* A, const uint16_t* W, const float
   a.rs_part = part_in; a.rs_np = part_in_np;
   a.dbg_out = timeline_out();
   KCHK(launch_gemm(a, epilogue, variant, (hipStream_t)stream));
+  return JAT_OK;
+}
+// The CFG sampler's step tail on caller buffers: final Linear [M = 2 B ntok, N = 4 C, K] of A = [cond ; uncond] + CFG combine + Euler
+// step + next step's patch operand.  fused != 0: one EPI_CFG_EULER launch on the latent in patch layout (z = zp [M/2, N], updated in
+// place; xpred unused).  fused == 0: the composition it replaces — EPI_UNPATCH into xpred [2B, C, T = 4 ntok], cfg_euler on
+// z [B, C, T], patchify of z — so that a test can compare the two bit for bit.
+extern "C" int jat_k_gemm_cfg_euler(const uint16_t* A, const uint16_t* W, const float* bias, int32_t M, int32_t N, int32_t K,
+                                    int32_t rows_per_batch, const float* part_in, int32_t part_in_np, float* z, uint16_t* a_patch,
+                                    float* xpred, const int32_t* frames, float cfg_scale, float t, float dt, int32_t variant,
+                                    int32_t fused, void* stream) {
+  if (!A || !W || !z || !a_patch || M <= 0 || M % 2 != 0 || N % 128 != 0 || K % 64 != 0 || rows_per_batch <= 0 ||
+      (M / 2) % rows_per_batch != 0)
+    return fail(JAT_E_INVALID, "bad argument");
+  if (part_in && part_in_np != 4 && part_in_np != 8 && part_in_np != 16) return fail(JAT_E_INVALID, "part_in_np must be 4, 8 or 16");
+  if (fused ? !gemm_cfg_euler_supported(variant) : (!gemm_variant(variant) || !xpred))
+    return fail(JAT_E_INVALID, fused ? "variant has no CFG + Euler epilogue" : "unknown variant or no xpred");
+  hipStream_t s = (hipStream_t)stream;
+  const int ntok = rows_per_batch, B = M / 2 / ntok, C = N / 4, T = ntok * 4;
+  GemmArgs a{};
+  a.A = A; a.W = W; a.lda = K; a.ldw = K; a.M = M; a.N = N; a.K = K; a.bias = bias; a.ntok = ntok;
+  a.rs_part = part_in; a.rs_np = part_in_np;
+  if (fused) {
+    a.out = z; a.ldo = N; a.ce_patch = a_patch; a.ce_frames = frames;
+    a.ce_scale = cfg_scale; a.ce_denom = 1.0f - t + 1e-5f; a.ce_dt = dt; a.ce_direct = !(t < 0.999f);
+    KCHK(launch_gemm(a, EPI_CFG_EULER, variant, s));
+    return JAT_OK;
+  }
+  a.out = xpred; a.C_out = C; a.T_orig = T;
+  KCHK(launch_gemm(a, EPI_UNPATCH, variant, s));
+  KCHK(launch_cfg_euler(xpred, z, cfg_scale, t, dt, 1, (int64_t)B * C * T, s));
+  KCHK(launch_patchify(z, nullptr, a_patch, B, B, B, C, 0, T, ntok, s, frames));
   return JAT_OK;
 }
 // per-kernel entry point (unit parity, tools/tl_probe.py): fused QKV projection + RoPE + GQA attention of 128-token samples,

@@ -16,6 +16,8 @@ enum GemmEpi : int {
   EPI_QKV_ROPE = 4,  // RoPE on q,k heads; q->[M,D], k->[M,kvD], v->vt[B,Hkv,64,Npad] (:154-160)
   EPI_QKV_ATTN = 6,  // fused: QKV projection + RoPE + GQA attention of one (sample, KV group) per block; out = attn_out
   EPI_UNPATCH = 5,   // out fp32 [B,C,T_orig]: feature c*4+p of token n -> [b,c,4n+p] (:406-420,465-469)
+  EPI_CFG_EULER = 7, // CFG sampler tail on PAIRED rows (A = [cond ; uncond], M/2 rows each): out = zp fp32 [M/2,ldo], the latent in
+                     // patch layout, updated in place by the CFG combine + Euler step of the two preds; ce_patch = bf16(zp)
 };
 
 struct GemmArgs {
@@ -30,11 +32,16 @@ struct GemmArgs {
   const float* gate;     // EPI_RESID: gate + b*gate_bstride + n
   int64_t gate_bstride;
   int ntok;              // rows per batch sample (b = m / ntok, pos = m % ntok)
-  // EPI_QKV_ROPE
-  bf16_t* k_out;
+  // EPI_QKV_ROPE.  EPI_CFG_EULER (jat_cfg_euler.h) keeps its arguments in the same storage (the two never meet, and the argument
+  // block of every kernel keeps its size and layout): the next step's bf16 patch operand [M/2, ldo]; the step's scalars (CFG scale,
+  // 1 - t + 1e-5, dt); optionally the valid frames per sample [M/2/ntok]: ce_patch reads zero from frame ce_frames[b] on, as
+  // patchify does with tvalid; ce_direct (below): z' = x, the schedule's last steps.
+  union { bf16_t* k_out; bf16_t* ce_patch; };
   bf16_t* vt_out;
-  int D, kvD, npad;
-  const float* rope_cos; // [max_pos, 32]
+  union { int D; float ce_scale; };
+  union { int kvD; float ce_denom; };
+  union { int npad; float ce_dt; };
+  union { const float* rope_cos; const int* ce_frames; };  // rope_cos: [max_pos, 32]
   const float* rope_sin;
   const float* rope_inv_freq;  // [32] fp32: 1/10000^(2i/64), for in-register sin/cos (coalesced epilogue)
   // EPI_UNPATCH
@@ -64,11 +71,14 @@ struct GemmArgs {
   // (fp32 elements); the caller sums the partials in fixed order (launch_sum_partials).  0 / 1: off.
   int ksplit;
   int64_t split_stride;
-  int variant_hint;   // unused (the plan travels beside the arguments: jat_gemm); kept so that the kernels' argument block keeps its size
+  union { int variant_hint; int ce_direct; };   // variant_hint: unused (the plan travels beside the arguments: jat_gemm); kept so that the
+                                                // kernels' argument block keeps its size
 };
 
 // variant: an id of the tile variant table (gemm_variants.h); retired and unknown ids are rejected
 hipError_t launch_gemm(const GemmArgs& a, int epi, int variant, hipStream_t s);
+// whether launch_gemm runs EPI_CFG_EULER on this variant's own tile (the tiles the final Linear is planned on)
+bool gemm_cfg_euler_supported(int variant);
 // Fused QKV projection + RoPE + attention for ntok == 128 (W = group-major fused weight [Hkv][5*64+64+64][K]):
 // one block per (sample, KV group); a.out = attention output bf16 [M, D]; a.N = Hkv * 448.
 hipError_t launch_qkv_attn(const GemmArgs& a, hipStream_t s);
@@ -136,6 +146,9 @@ hipError_t launch_gather_cast_rows(const float* in, int64_t in_stride, bf16_t* o
 // z += ((u + s(c-u)) - z)/(1-t+1e-5)*dt  (or z = x when t >= 0.999)  (infer_test_v3m2.py:161-179)
 hipError_t launch_cfg_euler(const float* xp, float* z, float cfg_scale, float t, float dt, int use_cfg,
                             int64_t n_per_half, hipStream_t s);
+// the latent between its two layouts, fp32: zp[(b,tok)][c*4+p] <-> z[b][c][4*tok+p]   (T % 4 == 0)
+hipError_t launch_patch_f32(const float* z, float* zp, int B, int C, int T, hipStream_t s);
+hipError_t launch_unpatch_f32(const float* zp, float* z, int B, int C, int T, hipStream_t s);
 hipError_t launch_channel_affine(const float* in, const float* mean, const float* std, float* out, int B,
                                  int C, int T, int inverse, hipStream_t s);
 hipError_t launch_crossfade_pair(const float* prev, int Tp, const float* cur, int Tc, int overlap,

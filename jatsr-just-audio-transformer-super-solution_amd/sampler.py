@@ -52,6 +52,11 @@ class Sampler:
         L.check(L.lib().jat_sampler_info(self.ptr, C.byref(f), C.byref(a), C.byref(n)))
         return {"folded": bool(f.value), "fused_attn": bool(a.value), "fold_bytes": int(n.value)}
 
+    def tail_fused(self):
+        """True when the steps run the fused tail (`jat_sampler_tail_fused`): CFG combine + Euler update inside the final Linear,
+        the latent kept in patch layout between the steps."""
+        return bool(L.lib().jat_sampler_tail_fused(self.ptr))
+
     def run(self, lr_latent, z0, use_graph=True, lengths=None):
         """lengths: optional valid frame count per batch row (rows shorter than the bucket's T, zero-padded by the caller:
         the last chunk of a file batched with the full-length ones).  Their valid frames equal a stand-alone run."""
