@@ -492,6 +492,44 @@ int jat_audio_metrics_run(jat_audio_metrics* h, const float* pred, const float* 
  * signal rides in the imaginary part of the same transforms; y and Y are null together. */
 int jat_stft(jat_audio_metrics* h, const float* x, const float* y, int32_t B, int64_t L, void* X, void* Y, void* stream);
 
+/* ---- inverse STFT, long-term spectrum and low-band splice --------------------------------------------------------- */
+/* The counterpart of jat_stft and the closing stage of the audio path, on the window and twiddles of a jat_audio_metrics
+ * handle (conventions as above: periodic Hann w, center=True, frames = 1 + L / hop, bins = 1 + n_fft / 2).
+ *   inverse  y_pad[f hop + i] += w[i] irfft(X[:, f])[i],  env[f hop + i] += w[i]^2,
+ *            y[t] = y_pad[t + n_fft / 2] / env[t + n_fft / 2] for t in [0, L)
+ *            (what torch.istft(X, n_fft, hop, window=w, center=True, length=L) computes; the imaginary parts of the DC and
+ *            Nyquist bins are ignored).  hop must divide n_fft with 4 <= n_fft / hop <= 64: env > 0 on all of [0, L).
+ *   splice   g = generated, s = source, both cut to n = min(L_gen, L_src); a[k] in [0, 1] a real gain per bin (1 = source):
+ *            out[t] = g[t] + iSTFT(a STFT(s - g))[t] = iSTFT(a S + (1 - a) G)[t] for t < n,  out[t] = g[t] for t in [n, L_gen)
+ *   gain     f_k = k sr / n_fft, lo = cutoff_hz - transition_hz:  a[k] = 0 for f_k >= cutoff_hz, 1 for f_k <= lo,
+ *            0.5 + 0.5 cos(pi (f_k - lo) / transition_hz) between: the transition lies below the cutoff
+ *   ltas     P[k] = mean_f |X[k, f]|^2 in fp64
+ * Two real frames (2 p, 2 p + 1) share one complex transform; the windowed output frames go to the workspace
+ * [B, frames, n_fft] fp32 and a gather pass sums the covering frames of every sample in ascending frame order and divides
+ * by a host-made envelope table.  fp32 in both operand-dtype builds, no atomics: the same bits from run to run, for a row
+ * alone or in a batch, whatever the launch shape.  A gain of zeros returns `generated` bit for bit. */
+/* [host, no GPU needed] bytes of the frames workspace of jat_istft for B rows of L samples.  Fails on n_fft not a power of
+ * two in 64..4096, hop not dividing n_fft, hop > n_fft / 4, n_fft / hop > 64, B outside 1..65535, L < 1, or sizes beyond
+ * 31 bits. */
+int jat_istft_workspace_bytes(int32_t n_fft, int32_t hop, int32_t B, int64_t L, size_t* bytes);
+/* X complex64 [B, bins, 1 + L / hop] (device) -> y fp32 [B, L].  The handle's hop must pass the checks above.
+ * JAT_E_STATE when work_bytes is below jat_istft_workspace_bytes. */
+int jat_istft(jat_audio_metrics* h, const void* X, int32_t B, int64_t L, float* y, void* work, size_t work_bytes, void* stream);
+/* x fp32 [B, L] -> P fp64 [B, bins] (device).  Partial spectra over JAT_LTAS_SLICES fixed slices of the frames are added in
+ * frame order, then slice by slice; no spectrogram reaches memory.  work: at least B * JAT_LTAS_SLICES * bins * 8 bytes. */
+#define JAT_LTAS_SLICES 64
+int jat_ltas(jat_audio_metrics* h, const float* x, int32_t B, int64_t L, double* P, void* work, size_t work_bytes, void* stream);
+/* [host, no GPU needed] the gain table a[bins] fp32 (computed in fp64).  cutoff_hz <= 0 gives zeros; cutoff_hz -
+ * transition_hz >= sr / 2 gives ones.  Fails on sr < 1, a bad n_fft, a negative transition or non-finite arguments. */
+int jat_band_gain(int32_t sr, int32_t n_fft, double cutoff_hz, double transition_hz, float* a);
+/* [host, no GPU needed] bytes of the frames workspace of jat_band_splice; the checks of jat_istft_workspace_bytes on both
+ * lengths (each at least 1). */
+int jat_band_splice_workspace_bytes(int32_t n_fft, int32_t hop, int32_t B, int64_t L_gen, int64_t L_src, size_t* bytes);
+/* generated fp32 [B, L_gen], source fp32 [B, L_src], a fp32 [bins] (all device) -> out fp32 [B, L_gen]; out may be
+ * `generated` itself.  JAT_E_STATE when work_bytes is below jat_band_splice_workspace_bytes. */
+int jat_band_splice(jat_audio_metrics* h, const float* generated, const float* source, int32_t B, int64_t L_gen, int64_t L_src,
+                    const float* a, float* out, void* work, size_t work_bytes, void* stream);
+
 /* ---- training data: batch assembly from a device-resident fp16 latent store, per-step monitor sums ---------------- */
 /* Replaces LatentDataset / ValidationDataset.__getitem__ + collate + the host-to-device copy + the two normalisations
  * (train_ddp_v3mod2.py:509-535, 561-597, 849-857) by one launch.  For sample b of B the device tables give the address of

@@ -20,6 +20,7 @@ _LAZY = {
     "prepare_audio": "prepare", "chunk_bounds": "prepare",
     "stft": "metrics", "mel_filterbank": "metrics", "calculate_lsd": "metrics", "calculate_mel_loss": "metrics",
     "calculate_multi_scale_mel_loss": "metrics", "evaluate": "metrics", "load_audio": "metrics",
+    "istft": "splice", "splice_lowband": "splice", "detect_cutoff": "splice",
     "Trainer": "train", "u_shaped_timestep_sampling": "train", "get_lr": "train", "GradScaler": "train",
     "train_monitor": "train", "monitor_figures": "train",
     "LatentStore": "data", "epoch_batches": "data", "val_crop_start": "data", "train_crop_start": "data",

@@ -135,10 +135,17 @@ SIGNATURES = {
     "jat_audio_metrics_workspace_bytes": (C.c_int, [_VP, _I32, _I64, C.POINTER(_SZ)]),
     "jat_audio_metrics_run": (C.c_int, [_VP, _VP, _VP, _I32, _I64, _I32, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "jat_stft": (C.c_int, [_VP, _VP, _VP, _I32, _I64, _VP, _VP, _VP]),
+    "jat_istft_workspace_bytes": (C.c_int, [_I32, _I32, _I32, _I64, C.POINTER(_SZ)]),
+    "jat_istft": (C.c_int, [_VP, _VP, _I32, _I64, _VP, _VP, _SZ, _VP]),
+    "jat_ltas": (C.c_int, [_VP, _VP, _I32, _I64, _VP, _VP, _SZ, _VP]),
+    "jat_band_gain": (C.c_int, [_I32, _I32, C.c_double, C.c_double, _VP]),
+    "jat_band_splice_workspace_bytes": (C.c_int, [_I32, _I32, _I32, _I64, _I64, C.POINTER(_SZ)]),
+    "jat_band_splice": (C.c_int, [_VP, _VP, _VP, _I32, _I64, _I64, _VP, _VP, _VP, _SZ, _VP]),
     "jat_latent_gather": (C.c_int, [_VP] * 10 + [_I32] * 3 + [_VP]),
     "jat_train_monitor": (C.c_int, [_VP, _VP, _VP, _I64, _VP, _VP, _SZ, _VP]),
 }
 MONITOR_WORK_BYTES = 49152   # JAT_MONITOR_WORK_BYTES
+LTAS_SLICES = 64             # JAT_LTAS_SLICES
 
 GRAD_HOOK = C.CFUNCTYPE(None, C.c_int64, C.c_int64, C.c_void_p)   # jat_trainer_set_grad_hook callback
 

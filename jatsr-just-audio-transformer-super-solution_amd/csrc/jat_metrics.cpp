@@ -1,5 +1,6 @@
 // C ABI of the audio-quality metrics (include/jat_hip.h): the Slaney mel filterbank, the Hann window and the per-pass
-// twiddle tables in fp64 on the host, the metrics handle, the launches of metrics.hip.
+// twiddle tables in fp64 on the host, the metrics handle (which also carries the tables of jat_splice.cpp), the launches of
+// metrics.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -7,12 +8,7 @@
 
 #include "jat_internal.h"
 #include "jat_metrics_kernels.h"
-
-struct jat_audio_metrics {
-  MetricsPlan plan;
-  MetricsTables tab;
-  void* dev = nullptr;   // one allocation behind every table
-};
+#include "jat_splice_kernels.h"
 
 namespace {
 
@@ -157,7 +153,12 @@ int jat_audio_metrics_create(int32_t sr, int32_t n_fft, int32_t hop, int32_t n_m
     int per_cu = 0;
     KCHK(metrics_blocks_per_cu(h->plan, &per_cu));
     h->plan.slots = cus * per_cu < 1 ? 1 : cus * per_cu;
+    KCHK(splice_blocks_per_cu(h->plan, &per_cu));
+    h->splice_slots = cus * per_cu < 1 ? 1 : cus * per_cu;
   }
+  // the overlap-add envelope of the inverse transform, where hop allows one (jat_splice_kernels.h)
+  std::vector<float> env;
+  if (splice_hop_ok(n_fft, hop)) splice_envelope_table(n_fft, hop, &env);
   // one device allocation: twiddles, window, band tables, weights
   std::vector<char> host;
   auto put = [&](const void* p, size_t n) {
@@ -169,6 +170,7 @@ int jat_audio_metrics_create(int32_t sr, int32_t n_fft, int32_t hop, int32_t n_m
   const size_t o_tw = put(tw.data(), tw.size() * sizeof(float2)), o_win = put(window.data(), window.size() * sizeof(float));
   const size_t o_first = put(first.data(), first.size() * sizeof(int)), o_count = put(count.data(), count.size() * sizeof(int));
   const size_t o_off = put(off.data(), off.size() * sizeof(int)), o_w = put(bw.data(), bw.size() * sizeof(float));
+  const size_t o_env = put(env.data(), env.size() * sizeof(float));
   host.resize(align_up(host.size() + 16, 16));
   hipStream_t s = (hipStream_t)stream;
   HIPCHK(hipMalloc(&h->dev, host.size()));
@@ -182,6 +184,7 @@ int jat_audio_metrics_create(int32_t sr, int32_t n_fft, int32_t hop, int32_t n_m
   h->tab.tw = (const float2*)(d + o_tw), h->tab.window = (const float*)(d + o_win);
   h->tab.band_first = (const int*)(d + o_first), h->tab.band_count = (const int*)(d + o_count);
   h->tab.band_off = (const int*)(d + o_off), h->tab.band_w = (const float*)(d + o_w);
+  h->envelope = env.empty() ? nullptr : (const float*)(d + o_env);
   *out = h.release();
   return JAT_OK;
 }

@@ -31,6 +31,15 @@ struct MetricsTables {
   const float* band_w = nullptr;       // the non-zero weights, band after band
 };
 
+// what a jat_audio_metrics handle owns (jat_metrics.cpp creates and destroys it; jat_splice.cpp uses it as well)
+struct jat_audio_metrics {
+  MetricsPlan plan;
+  MetricsTables tab;
+  void* dev = nullptr;                 // one allocation behind every table
+  const float* envelope = nullptr;     // overlap-add envelope table of jat_splice_kernels.h; null when hop does not allow it
+  int splice_slots = 1;                // blocks of the splice transform kernel the device holds at once
+};
+
 // frame groups one block runs through, and the blocks per row that follow from it; a result never depends on it
 int metrics_groups_per_block(const MetricsPlan& p, int B, int frames);
 inline int metrics_blocks_per_row(const MetricsPlan& p, int B, int frames) {

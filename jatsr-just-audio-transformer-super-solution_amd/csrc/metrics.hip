@@ -5,34 +5,21 @@
 // STFT pass: a block takes a run of frame groups of one batch row; a group is max(1, 1024 / n_fft) frames transformed
 // side by side.  pred and gt of a frame travel as one complex signal z = w (pred + i gt):
 //   X_pred[k] = (Z[k] + conj Z[N-k]) / 2,   X_gt[k] = (Z[k] - conj Z[N-k]) / (2i).
-// The transform is a Stockham autosort FFT, radix 4 with a closing radix-2 pass when log2 N is odd, between two LDS
-// buffers.  Every pass reads float2 at unit stride over the lanes (no bank conflict) and writes at j0 + r Ns: unit stride
-// from Ns = 16 on; the first pass has no twiddles and runs on the samples as they arrive from memory (zeros outside
-// [0, L): the centre padding), each thread storing its four outputs as 32 contiguous bytes.  Twiddles come from per-pass
-// tables made in fp64 on the host and staged in LDS once per block, indexed [r - 1][k] so that lanes read consecutive entries.
+// The transform is a Stockham autosort FFT (jat_fft.h, shared with splice.hip), radix 4 with a closing radix-2 pass when
+// log2 N is odd, between two LDS buffers.  Every pass reads float2 at unit stride over the lanes (no bank conflict) and
+// writes at j0 + r Ns: unit stride from Ns = 16 on; the first pass has no twiddles and runs on the samples as they arrive
+// from memory (zeros outside [0, L): the centre padding), each thread storing its four outputs as 32 contiguous bytes.
+// Twiddles come from per-pass tables made in fp64 on the host and staged in LDS once per block, indexed [r - 1][k] so that
+// lanes read consecutive entries.
 // Epilogue per frame: |X|^2 of both signals into LDS; the squared log-magnitude difference summed over bins by a fixed
 // shuffle tree in fp64 (lsd_frames); the sparse mel bands, each eight lanes' strided fp32 sums and a fixed tree.  Every
 // output is summed in an order that depends on neither the batch nor the block it falls in, maxima are exact, and there are
 // no atomics: the same bits from run to run and for a row alone or in a batch.  The two signals of a frame share the
 // rounding of one transform: a bin is accurate to about 1e-7 of the frame's energy in BOTH signals, so a signal far below
 // its partner (more than about 120 dB) reads as the partner's rounding noise; a frame of exact zeros is kept exactly zero.
-#include "jat_metrics_kernels.h"
+#include "jat_fft.h"
 
 namespace {
-
-__device__ __forceinline__ float2 cmul(float2 a, float2 b) { return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
-__device__ __forceinline__ float2 cadd(float2 a, float2 b) { return make_float2(a.x + b.x, a.y + b.y); }
-__device__ __forceinline__ float2 csub(float2 a, float2 b) { return make_float2(a.x - b.x, a.y - b.y); }
-
-// forward 4-point DFT: o[r] = sum_q v[q] (-i)^(r q)
-__device__ __forceinline__ void dft4(float2 v0, float2 v1, float2 v2, float2 v3, float2* o) {
-  const float2 a0 = cadd(v0, v2), a1 = csub(v0, v2), a2 = cadd(v1, v3), d = csub(v1, v3);
-  const float2 a3 = make_float2(d.y, -d.x);   // -i (v1 - v3)
-  o[0] = cadd(a0, a2);
-  o[1] = cadd(a1, a3);
-  o[2] = csub(a0, a2);
-  o[3] = csub(a1, a3);
-}
 
 __global__ void __launch_bounds__(MT_THREADS)
 stft_metrics_kernel(MetricsPlan p, MetricsTables t, const float* __restrict__ pred, const float* __restrict__ gt, int L,
@@ -75,47 +62,11 @@ stft_metrics_kernel(MetricsPlan p, MetricsTables t, const float* __restrict__ pr
       // a frame of zeros has a zero spectrum: kept exact, not left to the rounding of the partner's transform
       if (v[0].x != 0.f || v[1].x != 0.f || v[2].x != 0.f || v[3].x != 0.f) live[2 * g] = 1;
       if (v[0].y != 0.f || v[1].y != 0.f || v[2].y != 0.f || v[3].y != 0.f) live[2 * g + 1] = 1;
-      float2 o[4];
-      dft4(v[0], v[1], v[2], v[3], o);
-      float4* dst = (float4*)(buf0 + g * N + 4 * j);
-      dst[0] = make_float4(o[0].x, o[0].y, o[1].x, o[1].y);
-      dst[1] = make_float4(o[2].x, o[2].y, o[3].x, o[3].y);
+      fft_first_pass(v, buf0 + g * N, j);
     }
     __syncthreads();
-    float2* src = buf0;
-    float2* dst = buf1;
-    for (int ps = 1; ps < p.n_pass; ++ps) {
-      const int ns = p.ns[ps], sh = 31 - __clz(ns);
-      const float2* tp = tw + p.off[ps];
-      if (p.radix[ps] == 4) {
-        for (int jj = tid; jj < G * q; jj += MT_THREADS) {
-          const int g = jj >> lq, j = jj & (q - 1), k = j & (ns - 1);
-          const float2* sp = src + g * N + j;
-          const float2 v0 = sp[0], v1 = cmul(sp[q], tp[k]), v2 = cmul(sp[2 * q], tp[ns + k]), v3 = cmul(sp[3 * q], tp[2 * ns + k]);
-          float2 o[4];
-          dft4(v0, v1, v2, v3, o);
-          float2* dp = dst + g * N + (((j >> sh) << (sh + 2)) | k);
-          dp[0] = o[0];
-          dp[ns] = o[1];
-          dp[2 * ns] = o[2];
-          dp[3 * ns] = o[3];
-        }
-      } else {
-        const int h = N >> 1, lh = lq + 1;
-        for (int jj = tid; jj < G * h; jj += MT_THREADS) {
-          const int g = jj >> lh, j = jj & (h - 1), k = j & (ns - 1);
-          const float2* sp = src + g * N + j;
-          const float2 v0 = sp[0], v1 = cmul(sp[h], tp[k]);
-          float2* dp = dst + g * N + (((j >> sh) << (sh + 1)) | k);
-          dp[0] = cadd(v0, v1);
-          dp[ns] = csub(v0, v1);
-        }
-      }
-      __syncthreads();
-      float2* x = src;
-      src = dst;
-      dst = x;
-    }
+    float2* dst;
+    float2* src = fft_later_passes(p, tw, buf0, buf1, G, tid, &dst);
 
     // epilogue, part 1: split Z into the two spectra; powers into LDS (the buffer the last pass read from)
     const int f = fbase + ge;

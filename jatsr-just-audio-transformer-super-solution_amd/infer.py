@@ -13,7 +13,11 @@ per-channel normalisation (:381-394).  Differences, all outside the hot path's s
   * `--seed` makes the initial noise reproducible (the reference draws it with torch.randn, :133);
   * `--metrics` (with `--dac-weights`, where an HR ground truth exists: `--simulate-lr`, or a latent file with `hr_latent`)
     evaluates the decoded generated / HR / LR audio as the reference's calculate_metrics.py does (jatsr_amd.metrics) and
-    writes `{stem}_metrics.json` (with the `_cfgX` suffix of the generated files, if any) next to the WAVs.
+    writes `{stem}_metrics.json` (with the `_cfgX` suffix of the generated files, if any) next to the WAVs;
+  * `--lf-replace [HZ]` (with `--dac-weights`) also writes `{stem}_generated{suffix}_lf.wav`: the decoded audio with its
+    band below HZ (bare flag: the detected band limit of the source) replaced by the source's own (jatsr_amd.splice,
+    csrc/splice.hip).  The source is the 44.1 kHz waveform that was encoded (`--input-audio`), the whole file taken through
+    the LR simulation (`--simulate-lr`), or the decoded LR latent (latent-file input).  Every other file is unchanged.
 
     python -m jatsr_amd.infer --checkpoint ckpt.pt --input-file clip.pt --stats-file stats.json --cfg-scale 3.0
 """
@@ -59,10 +63,25 @@ def build_parser():
     p.add_argument("--metrics", action="store_true",
                    help="LSD and mel losses of the decoded generated and LR audio against the HR ground truth, written as "
                         "{stem}_metrics.json (needs --dac-weights and a ground truth: --simulate-lr or a latent file with hr_latent)")
+    p.add_argument("--lf-replace", type=str, nargs="?", const="auto", default=None, metavar="HZ",
+                   help="also write {stem}_generated_lf.wav: the decoded audio with the band below HZ (bare flag: the "
+                        "detected band limit of the source) taken from the source waveform (needs --dac-weights).  With a "
+                        "latent-file input the source is the decoded LR latent: that only removes generator drift, not "
+                        "codec error")
+    p.add_argument("--lf-transition-hz", type=float, default=500.0,
+                   help="with --lf-replace: width of the crossfade in frequency, below the cutoff")
     return p
 
 
 def run(args):
+    if args.lf_replace is not None:
+        if not args.dac_weights:
+            raise SystemExit("--lf-replace needs --dac-weights")
+        if args.lf_replace != "auto":
+            try:
+                float(args.lf_replace)
+            except ValueError:
+                raise SystemExit(f"--lf-replace: {args.lf_replace!r} is not a frequency in Hz")
     if args.input_audio and (args.input_file or not args.dac_weights):
         raise SystemExit("--input-audio needs --dac-weights and cannot be combined with --input-file")
     if (args.resample or args.simulate_lr is not None) and not args.input_audio:
@@ -72,10 +91,10 @@ def run(args):
     device = torch.device(args.device)
     os.makedirs(args.output_dir, exist_ok=True)
     model = load_model(args.checkpoint, device=device, cls=JaT_AudioSR_V2 if args.layernorm else JaT_AudioSR_V3)
-    codec = None
+    codec = source = None
     if args.input_audio:
         path = args.input_audio
-        codec, hr, lr = encode_audio(args, device)
+        codec, hr, lr, source = encode_audio(args, device)
     elif args.input_file:
         path = args.input_file if os.path.exists(args.input_file) else os.path.join(args.val_dir, args.input_file)
         if not os.path.exists(path):
@@ -115,15 +134,16 @@ def run(args):
                                    "frames": total, "seconds": dt})
     print(f"generated {gen.shape[-1]} frames in {dt:.2f} s -> {out_path}")
     if args.dac_weights:
-        decode_to_wav(args, gen, hr, lr, total, stem, suffix, device, codec)
+        decode_to_wav(args, gen, hr, lr, total, stem, suffix, device, codec, source)
     return out_path
 
 
 def encode_audio(args, device):
     """--input-audio: the WAV's DAC latent (the reference's data preparation, prepare_dataset_v5.py:206-219) becomes the
-    LR latent; there is no HR latent.  -> (codec, None, lr fp32 [1024, T] on the CPU).  With --resample a WAV of another
-    rate is converted to 44.1 kHz first; with --simulate-lr the WAV is the HR recording and both latents come from
-    prepare_audio -> (codec, hr, lr)."""
+    LR latent; there is no HR latent.  -> (codec, None, lr fp32 [1024, T] on the CPU, source).  With --resample a WAV of
+    another rate is converted to 44.1 kHz first; with --simulate-lr the WAV is the HR recording and both latents come from
+    prepare_audio -> (codec, hr, lr, source).  source: with --lf-replace the 44.1 kHz low-resolution waveform fp32 [L] on
+    the GPU, else None."""
     from .dac import load_dac_codec
     x, sr = jio.read_wav(args.input_audio)
     if args.simulate_lr is not None:
@@ -134,7 +154,8 @@ def encode_audio(args, device):
             raise SystemExit(f"{args.input_audio}: shorter than 1 s")
         print(f"prepared {os.path.basename(args.input_audio)}: {x.shape[0]} samples at {sr} Hz -> {res['count']} frames "
               f"(HR and LR through {args.simulate_lr} Hz, DAC {args.dac_precision})")
-        return codec, res["hr_latent"].cpu(), res["lr_latent"].cpu()
+        source = simulated_lr_waveform(x, sr, codec, args.simulate_lr, device) if args.lf_replace is not None else None
+        return codec, res["hr_latent"].cpu(), res["lr_latent"].cpu(), source
     if sr != 44100 and not args.resample:
         raise SystemExit(f"{args.input_audio}: sample rate {sr} Hz; the DAC 44.1 kHz model needs 44100 Hz "
                          "(resampling is not provided unless --resample is given)")
@@ -147,11 +168,27 @@ def encode_audio(args, device):
     z = codec.encode(audio[None])[0]
     print(f"encoded {os.path.basename(args.input_audio)}: {x.shape[0]} samples -> {z.shape[-1]} frames "
           f"(DAC {args.dac_precision})")
-    return codec, None, z[0].cpu()
+    return codec, None, z[0].cpu(), audio[0].contiguous() if args.lf_replace is not None else None
 
 
-def decode_to_wav(args, gen, hr, lr, total, stem, suffix, device, codec=None):
-    """DAC decode of the generated, HR and LR latents and the three WAV files of infer_test_v3m2.py:408-437."""
+def simulated_lr_waveform(x, sr, codec, low_sr, device):
+    """The whole recording through the resample calls prepare_audio runs on its chunks (peak rule, -> 48 kHz ->
+    simulate_lr -> codec rate): the low-resolution waveform at 44.1 kHz, fp32 [L] on the GPU."""
+    from .prepare import HIGH_SR, to_codec_rate
+    from .resample import resample, simulate_lr
+    w = torch.as_tensor(x).to(device, torch.float32)
+    if w.dim() == 2:
+        w = w.mean(dim=0)
+    peak = float(w.abs().max())
+    if peak > 1.0:
+        w = w / peak
+    hr48 = resample(w[None], sr, HIGH_SR) if sr != HIGH_SR else w[None]
+    return to_codec_rate(simulate_lr(hr48, HIGH_SR, low_sr), codec)[0].contiguous()
+
+
+def decode_to_wav(args, gen, hr, lr, total, stem, suffix, device, codec=None, source=None):
+    """DAC decode of the generated, HR and LR latents and the three WAV files of infer_test_v3m2.py:408-437; with
+    --lf-replace also the generated audio with its low band taken from `source` (the decoded LR latent when None)."""
     from .dac import load_dac_codec
     if codec is None:
         codec = load_dac_codec(args.dac_weights, device=device, precision=args.dac_precision)
@@ -160,12 +197,23 @@ def decode_to_wav(args, gen, hr, lr, total, stem, suffix, device, codec=None):
         outs.append((f"{stem}_hr_gt.wav", hr[None, :, :total].to(device)))
     outs.append((f"{stem}_lr_input.wav", lr[None, :, :total].to(device)))
     decoded = []
+    keep = args.metrics or args.lf_replace is not None
     for name, z in outs:
         audio = codec.decode(z)                      # [1, 1, frames * 512]
         jio.write_wav_float32(os.path.join(args.output_dir, name), audio[0, 0], codec.sample_rate)
-        if args.metrics:
+        if keep:
             decoded.append(audio[0, 0].float().contiguous())
     print(f"decoded {len(outs)} latents with DAC ({args.dac_precision}) -> {[n for n, _ in outs]}")
+    spliced = None
+    if args.lf_replace is not None:
+        from .splice import splice_lowband
+        spliced, hz = splice_lowband(decoded[0], decoded[-1] if source is None else source,
+                                     None if args.lf_replace == "auto" else float(args.lf_replace),
+                                     args.lf_transition_hz, sr=codec.sample_rate)
+        name = f"{stem}_generated{suffix}_lf.wav"
+        jio.write_wav_float32(os.path.join(args.output_dir, name), spliced, codec.sample_rate)
+        print(f"low band below {hz:.1f} Hz ({'detected' if args.lf_replace == 'auto' else 'given'}) taken from the "
+              f"{'decoded LR latent' if source is None else 'input waveform'} -> {name}")
     if args.metrics:
         import json
 
@@ -173,6 +221,11 @@ def decode_to_wav(args, gen, hr, lr, total, stem, suffix, device, codec=None):
         generated, hr_gt, lr_input = decoded
         rep = metrics.evaluate(generated, hr_gt, lr_input, sr=codec.sample_rate)
         print(metrics.format_report(rep))
+        if spliced is not None:
+            lf = metrics.evaluate(spliced, hr_gt, sr=codec.sample_rate)
+            rep["generated_lf"] = lf["generated"]
+            print("low band replaced (generated_lf) vs GT:")
+            print(metrics.format_report(lf))
         out = os.path.join(args.output_dir, f"{stem}_metrics{suffix}.json")
         with open(out, "w") as f:
             json.dump(rep, f, indent=2)
