@@ -103,6 +103,37 @@ int jat_time_embed(jat_model* m, const float* t, float* t_emb, int32_t B, void* 
  * buffers, and ONE hipGraph holding all `steps` CFG double-batch forwards + Euler updates. */
 int jat_sampler_create(jat_model* m, int32_t B, int32_t T, int32_t steps, float cfg_scale,
                        jat_sampler** out);
+/* ---- solvers and time grids ----
+ * x^(z, t) = CFG combine of the two predictions; den(t) = fp32(fp32(1 - t) + 1e-5); v(z, t) = (x^ - z) / den(t).  A grid is fp32,
+ * strictly increasing, from exactly 0 to exactly 1.  Step i: t = times[i], dt = fp32(times[i+1] - t), h = fp32(dt / 2).
+ *   JAT_SOLVER_EULER:    z' = z + dt v(z, t); from t >= 0.999 on z' = x^ (the reference's step, infer_test_v3m2.py:161-179)
+ *   JAT_SOLVER_MIDPOINT: z~ = z + h v(z, t);   z' = z + dt v(z~, t2),              t2 = fp32(t + h)
+ *   JAT_SOLVER_HEUN:     z~ = z + dt v(z, t);  z' = z/2 + z~/2 + h v(z~, t2),      t2 = times[i+1]
+ * A step whose t2 is not < 0.999 is taken as the Euler step (v is singular at t = 1): Heun on N steps costs 2N - 1 evaluations. */
+#define JAT_SOLVER_EULER 0
+#define JAT_SOLVER_MIDPOINT 1
+#define JAT_SOLVER_HEUN 2
+/* One model evaluation of a run.  stage 0: the Euler step of length c (direct != 0: z' = x^).  stage 1: z_base = z, then the Euler
+ * formula with step length c (save != 0).  stage 2: z' = a z_base + b z + c (x^ - z) / den.  time_index: the position of t among
+ * the run's distinct evaluation times (bit-equal fp32 values share one modulation row and one folded-weight entry). */
+typedef struct jat_solver_eval {
+  float t;
+  int32_t time_index;
+  float den, a, b, c;
+  int32_t stage, save, direct;
+} jat_solver_eval;
+/* The evaluation list of `solver` over times[n] (NULL: torch.linspace(0, 1, n) in fp32).  Host code only: no device is touched.
+ * evals / distinct (either may be NULL) have room for `cap` entries; 2 (n - 1) always suffice.  *n_evals / *n_distinct (may be
+ * NULL) are set whenever the grid and the solver are valid.  JAT_E_INVALID: n < 2, a grid that does not start at 0, end at 1 and
+ * strictly increase (a NaN never does), an unknown solver, or too little room. */
+int jat_solver_plan(const float* times, int32_t n, int32_t solver, jat_solver_eval* evals, int32_t cap, int32_t* n_evals,
+                    float* distinct, int32_t* n_distinct);
+/* jat_sampler_create with a solver and a time grid of n_times values (times == NULL: linspace(0, 1, n_times));
+ * jat_sampler_create(m, B, T, steps, s, out) is jat_sampler_create_ex(m, B, T, NULL, steps + 1, JAT_SOLVER_EULER, s, out).
+ * The whole evaluation list is captured as one graph; the folded-weight table is shared between samplers of one model whose
+ * lists of distinct times are equal. */
+int jat_sampler_create_ex(jat_model* m, int32_t B, int32_t T, const float* times, int32_t n_times, int32_t solver,
+                          float cfg_scale, jat_sampler** out);
 void jat_sampler_destroy(jat_sampler* s);
 /* What the sampler's captured graph runs: *folded != 0 = per-step folded weights (0 after the fallback to the
  * norm kernels: not an RMSNorm model, over the "fold_cap_mb" switch, or the table did not fit the device), *fused_attn != 0 = the
@@ -129,6 +160,11 @@ int jat_sampler_run(jat_sampler* s, const float* lr_latent, const float* z0_nois
  * x_pred_2B = [cond; uncond] is [2B,C,T] when cfg_scale != 1, else [B,C,T]. */
 int jat_cfg_euler_step(const float* x_pred_2B, float* z, float cfg_scale, float t, float dt, int32_t B,
                        int32_t C, int32_t T, void* stream);
+
+/* One stage of a two-stage solver in place on z [B,C,T], z_base [B,C,T] beside it; den = fp32(fp32(1 - t) + 1e-5).
+ * save != 0: z_base = z, z += (x^ - z) / den * c.   save == 0: z = a z_base + b z + c (x^ - z) / den. */
+int jat_cfg_stage_step(const float* x_pred_2B, float* z, float* z_base, float cfg_scale, float t, float a, float b, float c,
+                       int32_t save, int32_t B, int32_t C, int32_t T, void* stream);
 
 /* ---- chunk driver pieces (infer_test_v3m2.py:188-233, 381-394) ------------------------------------- */
 /* out[c,t] = (in[c,t] - mean[c]) / std[c]   (inverse=0)  |  in[c,t]*std[c] + mean[c]   (inverse=1) */
@@ -234,6 +270,12 @@ int jat_k_gemm_cfg_euler(const uint16_t* A, const uint16_t* W, const float* bias
                          int32_t rows_per_batch, const float* part_in, int32_t part_in_np, float* z, uint16_t* a_patch,
                          float* xpred, const int32_t* frames, float cfg_scale, float t, float dt, int32_t variant, int32_t fused,
                          void* stream);
+/* The same tail for one stage of a two-stage solver (jat_cfg_stage_step): z_base has the layout z has (patch layout when
+ * fused != 0, [B, C, 4 ntok] otherwise).  Same variants, same bits in both forms. */
+int jat_k_gemm_cfg_stage(const uint16_t* A, const uint16_t* W, const float* bias, int32_t M, int32_t N, int32_t K,
+                         int32_t rows_per_batch, const float* part_in, int32_t part_in_np, float* z, float* z_base,
+                         uint16_t* a_patch, float* xpred, const int32_t* frames, float cfg_scale, float t, float a, float b,
+                         float c, int32_t save, int32_t variant, int32_t fused, void* stream);
 /* Split-K slices of the same product: parts[z][M][N] fp32 = A[:, z K/ksplit : (z+1) K/ksplit] W[:, same]^T, z < ksplit, no
  * bias; summed in order by the caller / the finishing pass.  This is what the un-folded forward's fc2 and out_proj
  * (jat_audiosr_v3.py:300,306) launch when their tiles would leave CUs idle; variant 39 = the 224 x 160 k-step-pair tile

@@ -61,18 +61,23 @@ SIGNATURES = {
     "jat_attn_forward": (C.c_int, [_VP, _I32, _VP, _VP, _I32, _I32, _VP, _SZ, _VP]),
     "jat_time_embed": (C.c_int, [_VP, _VP, _VP, _I32, _VP, _SZ, _VP]),
     "jat_sampler_create": (C.c_int, [_VP, _I32, _I32, _I32, _F32, C.POINTER(_VP)]),
+    "jat_solver_plan": (C.c_int, [_VP, _I32, _I32, _VP, _I32, _VP, _VP, _VP]),
+    "jat_sampler_create_ex": (C.c_int, [_VP, _I32, _I32, _VP, _I32, _I32, _F32, C.POINTER(_VP)]),
     "jat_sampler_destroy": (None, [_VP]),
     "jat_sampler_run": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _VP]),
     "jat_sampler_info": (C.c_int, [_VP, _VP, _VP, _VP]),
     "jat_sampler_tail_fused": (C.c_int, [_VP]),
     "jat_sampler_set_lengths": (C.c_int, [_VP, C.POINTER(_I32), _I32, _VP]),
     "jat_cfg_euler_step": (C.c_int, [_VP, _VP, _F32, _F32, _F32, _I32, _I32, _I32, _VP]),
+    "jat_cfg_stage_step": (C.c_int, [_VP, _VP, _VP, _F32, _F32, _F32, _F32, _F32, _I32, _I32, _I32, _I32, _VP]),
     "jat_channel_affine": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _VP]),
     "jat_crossfade_pair": (C.c_int, [_VP, _I32, _VP, _I32, _I32, _VP, _I32, _VP]),
     "jat_k_norm_modulate": (C.c_int, [_VP, _VP, _VP, _VP, _I64, _VP, _I32, _I32, _I32, _I32, _VP]),
     "jat_k_gemm": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _VP, _I64, _I32, _I32, _VP]),
     "jat_k_gemm_fold": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _VP, _I64, _I32, _VP, _VP, _VP, _VP, _I32, _I32, _VP]),
     "jat_k_gemm_cfg_euler": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _VP, _I32, _VP, _VP, _VP, _VP, _F32, _F32, _F32, _I32, _I32, _VP]),
+    "jat_k_gemm_cfg_stage": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _VP, _I32, _VP, _VP, _VP, _VP, _VP, _F32, _F32, _F32, _F32,
+                                       _F32, _I32, _I32, _I32, _VP]),
     "jat_k_gemm_splitk": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP]),
     "jat_k_gemm_wave_n": (C.c_int, [_I32]),
     "jat_k_gemm_plan": (C.c_int, [_VP, _I32, _I32, _I32, _I32, _I32, _VP, _VP]),

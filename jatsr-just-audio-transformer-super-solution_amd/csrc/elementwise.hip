@@ -456,6 +456,56 @@ hipError_t launch_cfg_euler(const float* xp, float* z, float cfg_scale, float t,
   return hipGetLastError();
 }
 
+// ---- one stage of a two-stage solver (midpoint / Heun), un-fused tail: jat_cfg_euler.h -------------------------------------
+// save: z_base = z;  z += (x - z) / denom * c          (stage 1: the Euler formula with step length c)
+// else: z = a z_base + b z + c (x - z) / denom         (stage 2)
+__global__ void __launch_bounds__(256) cfg_stage_kernel(const float* __restrict__ xp, float* __restrict__ z,
+                                                        float* __restrict__ zb, float cfg_scale, float denom, float a, float b,
+                                                        float c, int use_cfg, int save, int64_t n) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x * 4;
+  const bool vec = !use_cfg || (n & 3) == 0;   // the uncond half starts at xp + n: 16-byte loads only when that is aligned
+  for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; i < n; i += stride) {
+    if (vec && i + 3 < n) {
+      float4 x = *(const float4*)(xp + i);
+      if (use_cfg) {
+        const float4 u = *(const float4*)(xp + n + i);
+        x.x = jat_cfg_combine(x.x, u.x, cfg_scale); x.y = jat_cfg_combine(x.y, u.y, cfg_scale);
+        x.z = jat_cfg_combine(x.z, u.z, cfg_scale); x.w = jat_cfg_combine(x.w, u.w, cfg_scale);
+      }
+      const float4 zz = *(const float4*)(z + i);
+      if (save) {
+        *(float4*)(zb + i) = zz;
+        x.x = jat_euler_step(x.x, zz.x, denom, c); x.y = jat_euler_step(x.y, zz.y, denom, c);
+        x.z = jat_euler_step(x.z, zz.z, denom, c); x.w = jat_euler_step(x.w, zz.w, denom, c);
+      } else {
+        const float4 bb = *(const float4*)(zb + i);
+        x.x = jat_stage_step(x.x, zz.x, bb.x, denom, a, b, c); x.y = jat_stage_step(x.y, zz.y, bb.y, denom, a, b, c);
+        x.z = jat_stage_step(x.z, zz.z, bb.z, denom, a, b, c); x.w = jat_stage_step(x.w, zz.w, bb.w, denom, a, b, c);
+      }
+      *(float4*)(z + i) = x;
+    } else {
+      for (int64_t j = i; j < i + 4 && j < n; ++j) {
+        float x = xp[j];
+        if (use_cfg) x = jat_cfg_combine(x, xp[n + j], cfg_scale);
+        const float zz = z[j];
+        if (save) { zb[j] = zz; x = jat_euler_step(x, zz, denom, c); }
+        else x = jat_stage_step(x, zz, zb[j], denom, a, b, c);
+        z[j] = x;
+      }
+    }
+  }
+}
+hipError_t launch_cfg_stage(const float* xp, float* z, float* z_base, float cfg_scale, float denom, float a, float b, float c,
+                            int use_cfg, int save, int64_t n_per_half, hipStream_t s) {
+  if (!xp || !z || !z_base || n_per_half <= 0) return hipErrorInvalidValue;
+  int64_t blocks = (n_per_half / 4 + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  if (blocks < 1) blocks = 1;
+  hipLaunchKernelGGL(cfg_stage_kernel, dim3((unsigned)blocks), dim3(256), 0, s, xp, z, z_base, cfg_scale, denom, a, b, c,
+                     use_cfg, save, n_per_half);
+  return hipGetLastError();
+}
+
 // ---- the latent between [B, C, T] and patch layout [(b, tok)][c*4 + p], fp32 (T % 4 == 0) -------------------------------
 // The CFG sampler keeps z in patch layout over its steps (EPI_CFG_EULER, gemm.hip); these run once per sampler run, before and
 // after the steps.  One 16-B patch per thread, channel fastest: the patch-layout side is contiguous.

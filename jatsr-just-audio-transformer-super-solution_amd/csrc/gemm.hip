@@ -213,7 +213,7 @@ __global__ void __launch_bounds__((WM * WN + (PIPE == 6 ? 4 : 0)) * 64, (WM * WN
   // and its last BM/2 rows from the matching rows of the uncond half, so that the waves (wm, wn) and (wm + WM/2, wn) hold the two
   // preds of the same (sample, token, feature) and the block finishes z itself.  m0 stays the tile's first row in tile units
   // (tile_m * BM), m0h = m0 / 2 its first row inside either half.
-  constexpr bool PR = EPI == EPI_CFG_EULER;
+  constexpr bool PR = EPI == EPI_CFG_EULER || EPI == EPI_CFG_STAGE;
   static_assert(!PR || (WM % 2 == 0 && PIPE != 6), "paired rows: the wave rows split evenly over the halves; no DMA-wave form");
   [[maybe_unused]] const int Mh = p.M >> 1;
   const int tiles_m = PR ? (Mh + BM / 2 - 1) / (BM / 2) : (p.M + BM - 1) / BM, tiles_n = p.N / BN;
@@ -1193,7 +1193,54 @@ __global__ void __launch_bounds__((WM * WN + (PIPE == 6 ? 4 : 0)) * 64, (WM * WN
     __builtin_amdgcn_s_barrier();
     float* const zp = (float*)p.out;
     const float cs = p.ce_scale, denom = p.ce_denom, dt = p.ce_dt;
-    const bool direct = p.ce_direct != 0;
+    [[maybe_unused]] const bool direct = p.ce_direct != 0;
+    if constexpr (EPI == EPI_CFG_STAGE) {
+      // one stage of a two-stage solver: the same walk with the start-of-step latent cs_base beside zp.  save: the Euler formula
+      // with step ce_dt, the old latent stored; else the three-term second stage (jat_stage_step)
+      float* const zbp = p.cs_base;
+      const float ca = p.cs_a, cb = p.cs_b;
+      const bool save = p.cs_save != 0;
+      static_for<0, TM>([&](auto ic) __attribute__((always_inline)) {
+        constexpr int i = decltype(ic)::value;
+        if ((i >= TA) == (hc == 1)) {                    // my share
+          const int mh = m0h + wmh * TM * 16 + i * 16 + frow;
+          if (mh < Mh) {
+            const int b = mh / p.ntok, tok = mh - b * p.ntok;
+            const int left = p.ce_frames ? p.ce_frames[b] - 4 * tok : 4;
+            float* zr = zp + (int64_t)mh * p.ldo + nw0 + fg * 4;
+            float* br = zbp + (int64_t)mh * p.ldo + nw0 + fg * 4;
+            bf16_t* ar = p.ce_patch + (int64_t)mh * p.ldo + nw0 + fg * 4;
+            float4 zz[TN], zb[TN];
+#pragma unroll
+            for (int j = 0; j < TN; ++j) zz[j] = *(const float4*)(zr + j * 16);
+            if (!save) {
+#pragma unroll
+              for (int j = 0; j < TN; ++j) zb[j] = *(const float4*)(br + j * 16);
+            }
+#pragma unroll
+            for (int j = 0; j < TN; ++j) {
+              const f32x4 o = *(const f32x4*)(xb + (i * TN + j) * 1024);
+              const f32x4 c = hc ? o : acc[i][j], u = hc ? acc[i][j] : o;
+              float x[4];
+#pragma unroll
+              for (int e = 0; e < 4; ++e) x[e] = jat_cfg_combine(c[e], u[e], cs);
+              if (save) {
+                *(float4*)(br + j * 16) = zz[j];
+                x[0] = jat_euler_step(x[0], zz[j].x, denom, dt); x[1] = jat_euler_step(x[1], zz[j].y, denom, dt);
+                x[2] = jat_euler_step(x[2], zz[j].z, denom, dt); x[3] = jat_euler_step(x[3], zz[j].w, denom, dt);
+              } else {
+                x[0] = jat_stage_step(x[0], zz[j].x, zb[j].x, denom, ca, cb, dt); x[1] = jat_stage_step(x[1], zz[j].y, zb[j].y, denom, ca, cb, dt);
+                x[2] = jat_stage_step(x[2], zz[j].z, zb[j].z, denom, ca, cb, dt); x[3] = jat_stage_step(x[3], zz[j].w, zb[j].w, denom, ca, cb, dt);
+              }
+              *(float4*)(zr + j * 16) = float4{x[0], x[1], x[2], x[3]};
+              *(uint2*)(ar + j * 16) = pack4(left > 0 ? x[0] : 0.f, left > 1 ? x[1] : 0.f, left > 2 ? x[2] : 0.f, left > 3 ? x[3] : 0.f);
+            }
+          }
+        }
+      });
+      JAT_TL_FLUSH()
+      return;
+    }
     static_for<0, TM>([&](auto ic) __attribute__((always_inline)) {
       constexpr int i = decltype(ic)::value;
       if ((i >= TA) == (hc == 1)) {                    // my share
@@ -1997,16 +2044,18 @@ static hipError_t launch_one(const GemmArgs& a, hipStream_t s) {
   }
   if (a.N % BN != 0 || a.K % 64 != 0 || a.M <= 0) return hipErrorInvalidValue;
   // paired rows: ceil(Mh / (BM/2)) row tiles; the PIPE 8 loop addresses A rows by 32-bit byte offsets from the tile's first row
-  if (EPI == EPI_CFG_EULER && (a.M % 2 != 0 || !a.out || !a.ce_patch || a.ntok <= 0 || a.ldo < a.N || a.ldo % 4 != 0 ||
+  constexpr bool PAIRED = EPI == EPI_CFG_EULER || EPI == EPI_CFG_STAGE;
+  if (PAIRED && (a.M % 2 != 0 || !a.out || !a.ce_patch || a.ntok <= 0 || a.ldo < a.N || a.ldo % 4 != 0 ||
                                (int64_t)a.M * a.lda * 2 >= (1ll << 31)))
     return hipErrorInvalidValue;
-  const int tiles = (EPI == EPI_CFG_EULER ? (a.M / 2 + BM / 2 - 1) / (BM / 2) : (a.M + BM - 1) / BM) * (a.N / BN);
+  if (EPI == EPI_CFG_STAGE && !a.cs_base) return hipErrorInvalidValue;
+  const int tiles = (PAIRED ? (a.M / 2 + BM / 2 - 1) / (BM / 2) : (a.M + BM - 1) / BM) * (a.N / BN);
   if (a.ksplit > 1 && EPI != EPI_F32) return hipErrorInvalidValue;
   hipLaunchKernelGGL(kern, dim3(tiles, a.ksplit > 1 ? a.ksplit : 1), dim3((WM * WN + (PIPE == 6 ? 4 : 0)) * 64), LDS, s, a);
   return hipGetLastError();
 }
 
-// The tiles EPI_CFG_EULER is built for: what the planner can choose for the final Linear [2 B ntok, 4 C, D] (N a multiple of 128):
+// The tiles EPI_CFG_EULER and EPI_CFG_STAGE are built for: what the planner can choose for the final Linear [2 B ntok, 4 C, D] (N a multiple of 128):
 // 64 x 128 and 128 x 128 (two blocks per CU) for small batches, 224 x 256 / 256 x 256 quadrant ping-pong for full ones.
 static constexpr bool cfg_euler_tile(int WM, int WN, int TM, int TN, int PIPE, int CE) {
   return CE == 1 && WM == 2 && TN == 4 && ((PIPE == 2 && WN == 2 && (TM == 2 || TM == 4)) || (PIPE == 8 && WN == 4 && (TM == 7 || TM == 8)));
@@ -2022,6 +2071,9 @@ static hipError_t launch_epi(const GemmArgs& a, int epi, hipStream_t s) {
     case EPI_UNPATCH: return launch_one<WM, WN, TM, TN, PIPE, CE, EPI_UNPATCH>(a, s);
     case EPI_CFG_EULER:
       if constexpr (cfg_euler_tile(WM, WN, TM, TN, PIPE, CE)) return launch_one<WM, WN, TM, TN, PIPE, CE, EPI_CFG_EULER>(a, s);
+      break;
+    case EPI_CFG_STAGE:
+      if constexpr (cfg_euler_tile(WM, WN, TM, TN, PIPE, CE)) return launch_one<WM, WN, TM, TN, PIPE, CE, EPI_CFG_STAGE>(a, s);
       break;
   }
   return hipErrorInvalidValue;

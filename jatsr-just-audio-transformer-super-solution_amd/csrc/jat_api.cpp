@@ -5,11 +5,13 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -488,9 +490,13 @@ static int patch_linear1(const jat_model* m, const Workspace& w, int rows, int K
 
 // The CFG sampler's fused step tail (EPI_CFG_EULER): the latent lives in patch layout (zp fp32, w.a_patch bf16) over the steps; the
 // final Linear applies the CFG combine + Euler step of time t / step dt itself and writes both for the next step.
+// stage != 0 (EPI_CFG_STAGE): one stage of a two-stage solver (jat_solver_plan), with the start-of-step latent z_base beside zp.
 struct FusedTail {
   float* zp;
   float cfg_scale, t, dt;
+  int stage = 0;              // 0: Euler step of length dt at time t; 1 / 2: first / second stage, step coefficient dt
+  float* z_base = nullptr;
+  float den = 0.f, a = 0.f, b = 0.f;
 };
 
 // Whole forward over B batch rows.  x_t rows are read modulo B_src and the condition is zero from batch row
@@ -547,8 +553,12 @@ static int forward_impl(const jat_model* m, const Workspace& w, const float* x_t
     if (tail) {
       e.out = tail->zp; e.ldo = m->Fout; e.ce_patch = w.a_patch; e.ce_frames = w.tvalid;
       e.ce_scale = tail->cfg_scale; e.ce_denom = 1.0f - tail->t + 1e-5f; e.ce_dt = tail->dt; e.ce_direct = !(tail->t < 0.999f);   // launch_cfg_euler
+      if (tail->stage) {   // launch_cfg_stage
+        e.ce_denom = tail->den; e.cs_base = tail->z_base; e.cs_a = tail->a; e.cs_b = tail->b; e.cs_save = tail->stage == 1;
+      }
     }
-    JCHK(jat_gemm(m, G_OTHER, w.xn, D, f ? f->wfinal : m->wfinal, D, M, m->Fout, D, tail ? EPI_CFG_EULER : EPI_UNPATCH, e, s));
+    JCHK(jat_gemm(m, G_OTHER, w.xn, D, f ? f->wfinal : m->wfinal, D, M, m->Fout, D,
+                  !tail ? EPI_UNPATCH : tail->stage ? EPI_CFG_STAGE : EPI_CFG_EULER, e, s));
   }
   return JAT_OK;
 }
@@ -623,10 +633,12 @@ extern "C" int jat_attn_forward(jat_model* m, int32_t layer, const float* x, flo
 // ---------------------------------------------------------------------------------------------------------
 struct jat_sampler {
   jat_model* m;
-  int B, T, steps, Bf;  // Bf = batch rows per forward (2B with CFG)
+  int B, T, Bf;  // Bf = batch rows per forward (2B with CFG)
   float cfg_scale;
   bool use_cfg;
-  std::vector<float> ts;  // [host] linspace(0,1,steps+1)
+  std::vector<jat_solver_eval> plan;   // the model evaluations of a run, in order (jat_solver_plan)
+  std::vector<float> times;            // the distinct evaluation times: rows of mod_table, entries of the folded-weight table
+  float* z_base = nullptr;             // two-stage solvers: the latent at the start of the step, in the layout z / zp has
   char* blob = nullptr;   // private device allocation
   float *z, *lr, *xpred, *mod_table, *ts_dev;
   float* zp = nullptr;               // fused tail: the latent in patch layout [B ntok, 4 C] over the steps of a run
@@ -652,6 +664,49 @@ static void linspace01(int n, std::vector<float>& out) {
   const float step = 1.0f / (float)(n - 1);
   for (int i = 0; i < n; ++i)
     out[i] = i < n / 2 ? (float)((double)step * i) : (float)(1.0 - (double)step * (n - 1 - i));
+}
+
+// The evaluation list of a solver over a time grid (include/jat_hip.h).  Pure host code.
+//   euler:    z' = z + dt v(z, t)                                                       (the reference's step, direct from t >= 0.999)
+//   midpoint: z~ = z + h v(z, t);   z' = z_base + dt v(z~, t + h)                       h = dt / 2
+//   heun:     z~ = z + dt v(z, t);  z' = z_base / 2 + z~ / 2 + h v(z~, t_next)
+// A step whose second time is not < 0.999 is taken as the Euler step: v = (x - z) / (1 - t + 1e-5) is singular at t = 1.
+static uint32_t f32_bits(float v) { uint32_t u; memcpy(&u, &v, 4); return u; }
+extern "C" int jat_solver_plan(const float* times, int32_t n, int32_t solver, jat_solver_eval* evals, int32_t cap, int32_t* n_evals,
+                               float* distinct, int32_t* n_distinct) {
+  if (n < 2) return fail(JAT_E_INVALID, "a time grid needs at least two values, got %d", n);
+  if (solver != JAT_SOLVER_EULER && solver != JAT_SOLVER_MIDPOINT && solver != JAT_SOLVER_HEUN)
+    return fail(JAT_E_INVALID, "unknown solver %d", solver);
+  std::vector<float> lin;
+  if (!times) { linspace01(n, lin); times = lin.data(); }
+  if (!(times[0] == 0.0f) || !(times[n - 1] == 1.0f)) return fail(JAT_E_INVALID, "the time grid must start at 0 and end at 1");
+  for (int i = 0; i + 1 < n; ++i)
+    if (!(times[i + 1] > times[i])) return fail(JAT_E_INVALID, "the time grid must be strictly increasing (index %d)", i + 1);
+  std::vector<jat_solver_eval> ev;
+  std::vector<float> dis;
+  std::map<uint32_t, int> index;
+  auto push = [&](float t, int stage, float a, float b, float c) {
+    auto it = index.find(f32_bits(t));
+    if (it == index.end()) { it = index.emplace(f32_bits(t), (int)dis.size()).first; dis.push_back(t); }
+    jat_solver_eval e{};
+    e.t = t; e.time_index = it->second; e.den = 1.0f - t + 1e-5f; e.a = a; e.b = b; e.c = c;
+    e.stage = stage; e.save = stage == 1; e.direct = stage == 0 && !(t < 0.999f);
+    ev.push_back(e);
+  };
+  for (int i = 0; i + 1 < n; ++i) {
+    const float t = times[i], dt = times[i + 1] - t, h = 0.5f * dt;
+    const float t2 = solver == JAT_SOLVER_MIDPOINT ? t + h : times[i + 1];
+    if (solver == JAT_SOLVER_EULER || !(t2 < 0.999f)) { push(t, 0, 0.0f, 1.0f, dt); continue; }
+    if (solver == JAT_SOLVER_MIDPOINT) { push(t, 1, 0.0f, 1.0f, h); push(t2, 2, 1.0f, 0.0f, dt); }
+    else { push(t, 1, 0.0f, 1.0f, dt); push(t2, 2, 0.5f, 0.5f, h); }
+  }
+  if (n_evals) *n_evals = (int32_t)ev.size();
+  if (n_distinct) *n_distinct = (int32_t)dis.size();
+  if ((evals && cap < (int32_t)ev.size()) || (distinct && cap < (int32_t)dis.size()))
+    return fail(JAT_E_INVALID, "room for %d entries, the plan has %zu evaluations", cap, ev.size());
+  if (evals) std::copy(ev.begin(), ev.end(), evals);
+  if (distinct) std::copy(dis.begin(), dis.end(), distinct);
+  return JAT_OK;
 }
 
 // pc = patch(lr) @ W1[:, cond columns]^T (fp32, no bias): once per run, before the captured steps
@@ -681,12 +736,20 @@ static int sampler_end(jat_sampler* sp, hipStream_t s) {
   return JAT_OK;
 }
 
-static int sampler_steps(jat_sampler* sp, hipStream_t s) {
+// The evaluations of the plan in order.  warm_up: only the first evaluation of each launch kind (Euler step / solver stage): the
+// eager pass before the capture that sets the kernels' function attributes.
+static int sampler_steps(jat_sampler* sp, hipStream_t s, bool warm_up = false) {
   jat_model* m = sp->m;
   const int64_t n_half = (int64_t)sp->B * m->Cin * sp->T;
   const int64_t row = (int64_t)m->depth * 6 * m->D;
-  for (int i = 0; i < sp->steps; ++i) {
-    const float t_curr = sp->ts[i], dt = sp->ts[i + 1] - sp->ts[i];
+  bool seen[2] = {false, false};
+  for (const jat_solver_eval& ev : sp->plan) {
+    if (warm_up) {
+      if (seen[ev.stage != 0]) continue;
+      seen[ev.stage != 0] = true;
+    }
+    const int i = ev.time_index;
+    const float t_curr = ev.t, dt = ev.c;
     Fold f{};
     if (sp->folded) {
       const FoldTable& ft = *sp->fold;
@@ -697,10 +760,12 @@ static int sampler_steps(jat_sampler* sp, hipStream_t s) {
       f.bf = ft.bf + (int64_t)i * dl * m->mlp;
       f.wfinal = ft.wfinal;
     }
-    const FusedTail tail{sp->zp, sp->cfg_scale, t_curr, dt};
+    const FusedTail tail{sp->zp, sp->cfg_scale, t_curr, dt, ev.stage, sp->z_base, ev.den, ev.a, ev.b};
     JCHK(forward_impl(m, sp->w, sp->z, sp->B, sp->lr, sp->B, nullptr, sp->mod_table + i * row, 0, sp->xpred, sp->Bf,
                       sp->T, s, sp->folded ? &f : nullptr, sp->pc, sp->tail_fused ? &tail : nullptr));
-    if (!sp->tail_fused) KCHK(launch_cfg_euler(sp->xpred, sp->z, sp->cfg_scale, t_curr, dt, sp->use_cfg ? 1 : 0, n_half, s));
+    if (!sp->tail_fused && !ev.stage) KCHK(launch_cfg_euler(sp->xpred, sp->z, sp->cfg_scale, t_curr, dt, sp->use_cfg ? 1 : 0, n_half, s));
+    if (!sp->tail_fused && ev.stage)
+      KCHK(launch_cfg_stage(sp->xpred, sp->z, sp->z_base, sp->cfg_scale, ev.den, ev.a, ev.b, ev.c, sp->use_cfg ? 1 : 0, ev.save, n_half, s));
   }
   return JAT_OK;
 }
@@ -798,19 +863,34 @@ extern "C" void jat_sampler_destroy(jat_sampler* sp) {
 
 extern "C" int jat_sampler_create(jat_model* m, int32_t B, int32_t T, int32_t steps, float cfg_scale,
                                   jat_sampler** out) {
+  if (steps <= 0) return fail(JAT_E_INVALID, "B, T, steps must be positive");
+  return jat_sampler_create_ex(m, B, T, nullptr, steps + 1, JAT_SOLVER_EULER, cfg_scale, out);
+}
+
+extern "C" int jat_sampler_create_ex(jat_model* m, int32_t B, int32_t T, const float* times, int32_t n_times, int32_t solver,
+                                     float cfg_scale, jat_sampler** out) {
   if (!m || !out) return fail(JAT_E_INVALID, "null argument");
   if (!m->loaded) return fail(JAT_E_STATE, "weights not loaded");
-  if (B <= 0 || T <= 0 || steps <= 0) return fail(JAT_E_INVALID, "B, T, steps must be positive");
+  if (B <= 0 || T <= 0) return fail(JAT_E_INVALID, "B, T, steps must be positive");
+  // the evaluation list first: it validates the grid and the solver, and sizes the tables (one row / entry per distinct time)
+  std::vector<jat_solver_eval> plan((size_t)(n_times > 1 ? 2 * (n_times - 1) : 0));
+  std::vector<float> distinct(plan.size());
+  int32_t n_evals = 0, n_distinct = 0;
+  JCHK(jat_solver_plan(times, n_times, solver, plan.data(), (int32_t)plan.size(), &n_evals, distinct.data(), &n_distinct));
+  plan.resize((size_t)n_evals);
+  distinct.resize((size_t)n_distinct);
+  const int steps = n_distinct;   // rows of the modulation table and entries of the folded-weight table
   const int ntok = (T + 3) / 4;
   if (ntok > MAX_LEN) return fail(JAT_E_SEQLEN, "Sequence length %d exceeds max_len %d", ntok, MAX_LEN);
   // The tables and the captured graph are built on a private stream: order them after everything already enqueued on
   // the caller's streams (e.g. an asynchronous weight re-pack).  Creation is a slow path; a device sync is the simple order.
   HIPCHK(hipDeviceSynchronize());
   jat_sampler* sp = new jat_sampler();
-  sp->m = m; sp->B = B; sp->T = T; sp->steps = steps; sp->cfg_scale = cfg_scale;
+  sp->m = m; sp->B = B; sp->T = T; sp->cfg_scale = cfg_scale;
+  sp->plan = plan; sp->times = distinct;
   sp->use_cfg = cfg_scale != 1.0f;  // infer_test_v3m2.py:139
   sp->Bf = sp->use_cfg ? 2 * B : B;
-  linspace01(steps + 1, sp->ts);
+  const bool two_stage = std::any_of(plan.begin(), plan.end(), [](const jat_solver_eval& e) { return e.stage != 0; });
 
   const size_t lat = (size_t)B * m->Cin * T * 4;
   const size_t row = (size_t)m->depth * 6 * m->D;
@@ -836,6 +916,7 @@ extern "C" int jat_sampler_create(jat_model* m, int32_t B, int32_t T, int32_t st
   const size_t o_lens = take((size_t)sp->Bf * 4), o_frames = take((size_t)B * 4);
   const size_t o_pc = take((size_t)B * ntok * m->bott * 4);
   const size_t o_zp = take(sp->tail_fused ? lat : 0);
+  const size_t o_zb = take(two_stage ? lat : 0);
   hipError_t e = hipMalloc((void**)&sp->blob, off);
   if (e != hipSuccess) { delete sp; return fail(JAT_E_HIP, "hipMalloc(%zu): %s", off, hipGetErrorString(e)); }
   sp->z = (float*)(sp->blob + o_z); sp->lr = (float*)(sp->blob + o_lr);
@@ -847,6 +928,7 @@ extern "C" int jat_sampler_create(jat_model* m, int32_t B, int32_t T, int32_t st
   sp->frames_dev = (int*)(sp->blob + o_frames);
   if (sp->use_cfg && m->sw.split_patch) sp->pc = (float*)(sp->blob + o_pc);
   if (sp->tail_fused) sp->zp = (float*)(sp->blob + o_zp);
+  if (two_stage) sp->z_base = (float*)(sp->blob + o_zb);
 
   int rc = JAT_OK;
   auto bail = [&](int code) { jat_sampler_destroy(sp); return code; };
@@ -854,29 +936,31 @@ extern "C" int jat_sampler_create(jat_model* m, int32_t B, int32_t T, int32_t st
     return bail(fail(JAT_E_HIP, "hipStreamCreate failed"));
   hipStream_t s = sp->cap_stream;
 
-  // modulation table [steps, depth*6D]: every row of step i shares t = ts[i] (infer_test_v3m2.py:150)
+  // modulation table [distinct times, depth*6D]: every row of an evaluation shares its t (infer_test_v3m2.py:150)
   {
     Workspace wt = carve(m, steps, ntok, (char*)sp->ws);
-    if (hipMemcpyAsync(sp->ts_dev, sp->ts.data(), (size_t)steps * 4, hipMemcpyHostToDevice, s) != hipSuccess)
+    if (hipMemcpyAsync(sp->ts_dev, sp->times.data(), (size_t)steps * 4, hipMemcpyHostToDevice, s) != hipSuccess)
       return bail(fail(JAT_E_HIP, "memcpy ts"));
     if ((rc = time_path(m, wt, sp->ts_dev, steps, s)) != JAT_OK) return bail(rc);
     if ((rc = adaln_path(m, wt.t_silu, sp->mod_table, steps, 0, m->depth, s)) != JAT_OK) return bail(rc);
     if (sp->folded) {
-      // per-step folded weights: shared by every sampler of this model with the same step count (model-level cache)
-      // The cache keeps at most TWO step counts alive on its own (a table is ~0.5 GB per step for v3mod2: 25 GB at 50 steps,
+      // folded weights per distinct time: shared by every sampler of this model with the same list of times (model-level cache:
+      // Heun over a grid shares Euler's).  The cache keeps at most TWO lists alive on its own (a table is ~0.5 GB per step for v3mod2: 25 GB at 50 steps,
       // 50 GB at the 100 steps the reference README also offers); tables that a live sampler still holds stay until it is destroyed.
+      std::vector<uint32_t> key(sp->times.size());
+      for (size_t i = 0; i < key.size(); ++i) key[i] = f32_bits(sp->times[i]);
       for (auto it = m->fold_cache.begin(); it != m->fold_cache.end() && m->fold_cache.size() >= 2;)
-        it = (it->first != steps && it->second.use_count() == 1) ? m->fold_cache.erase(it) : std::next(it);
+        it = (it->first != key && it->second.use_count() == 1) ? m->fold_cache.erase(it) : std::next(it);
       const size_t Nq = (size_t)m->D + 2 * m->kvD;
       const size_t need = (size_t)steps * m->depth * ((Nq + m->mlp) * m->D * 2 + (Nq + m->mlp) * 4) + (size_t)m->Fout * m->D * 2;
       const bool over_cap = m->sw.fold_cap_mb > 0 && need > (size_t)m->sw.fold_cap_mb * 1048576;   // "fold_cap_mb": operator's bound
-      std::shared_ptr<FoldTable>& slot = m->fold_cache[steps];
+      std::shared_ptr<FoldTable>& slot = m->fold_cache[key];
       if (!slot) slot = std::make_shared<FoldTable>();
       if (over_cap || build_fold_table(m, *slot, steps, sp->mod_table, sp->fused_attn, sh_bf16, s) != JAT_OK) {
         (void)hipStreamSynchronize(s);
         // over the cap or out of memory: run this sampler with the norm kernels.  What was already built stays for the samplers
         // that hold it; an EMPTY entry is dropped so that a later, smaller request starts clean
-        if (!slot->w1 && !slot->qkv_g && !slot->qkv_i) m->fold_cache.erase(steps);
+        if (!slot->w1 && !slot->qkv_g && !slot->qkv_i) m->fold_cache.erase(key);
         sp->folded = false;
       } else {
         sp->fold = slot;
@@ -899,18 +983,16 @@ extern "C" int jat_sampler_create(jat_model* m, int32_t B, int32_t T, int32_t st
   // one eager pass first: sets every kernel's function attributes outside of capture and validates launches
   if (hipMemsetAsync(sp->z, 0, lat, s) != hipSuccess || hipMemsetAsync(sp->lr, 0, lat, s) != hipSuccess)
     return bail(fail(JAT_E_HIP, "memset"));
+  if (two_stage && hipMemsetAsync(sp->z_base, 0, lat, s) != hipSuccess) return bail(fail(JAT_E_HIP, "memset"));
   {
-    const int saved = sp->steps;
-    sp->steps = 1;
     if ((rc = sampler_begin(sp, s)) != JAT_OK) return bail(rc);
-    rc = sampler_steps(sp, s);
+    rc = sampler_steps(sp, s, true);
     if (rc == JAT_OK) rc = sampler_end(sp, s);
-    sp->steps = saved;
     if (rc != JAT_OK) return bail(rc);
     if (hipStreamSynchronize(s) != hipSuccess)
       return bail(fail(JAT_E_HIP, "eager warm-up step failed: %s", hipGetErrorString(hipGetLastError())));
   }
-  // capture all `steps` forwards + Euler updates into one graph
+  // capture all the plan's forwards + updates into one graph
   if (hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) != hipSuccess)
     return bail(fail(JAT_E_HIP, "hipStreamBeginCapture failed"));
   rc = sampler_steps(sp, s);
@@ -932,7 +1014,7 @@ extern "C" int jat_sampler_info(const jat_sampler* sp, int32_t* folded, int32_t*
   if (fold_bytes) {
     const jat_model* m = sp->m;
     const size_t Nq = (size_t)m->D + 2 * m->kvD;
-    *fold_bytes = sp->folded ? (int64_t)((size_t)sp->steps * m->depth * ((Nq + m->mlp) * m->D * 2 + (Nq + m->mlp) * 4) + (size_t)m->Fout * m->D * 2) : 0;
+    *fold_bytes = sp->folded ? (int64_t)((size_t)sp->times.size() * m->depth * ((Nq + m->mlp) * m->D * 2 + (Nq + m->mlp) * 4) + (size_t)m->Fout * m->D * 2) : 0;
   }
   return JAT_OK;
 }
@@ -981,6 +1063,14 @@ extern "C" int jat_cfg_euler_step(const float* x_pred_2B, float* z, float cfg_sc
                                   int32_t C, int32_t T, void* stream) {
   KCHK(launch_cfg_euler(x_pred_2B, z, cfg_scale, t, dt, cfg_scale != 1.0f ? 1 : 0, (int64_t)B * C * T,
                         (hipStream_t)stream));
+  return JAT_OK;
+}
+
+extern "C" int jat_cfg_stage_step(const float* x_pred_2B, float* z, float* z_base, float cfg_scale, float t, float a, float b,
+                                  float c, int32_t save, int32_t B, int32_t C, int32_t T, void* stream) {
+  if (!x_pred_2B || !z || !z_base || B <= 0 || C <= 0 || T <= 0) return fail(JAT_E_INVALID, "bad argument");
+  KCHK(launch_cfg_stage(x_pred_2B, z, z_base, cfg_scale, 1.0f - t + 1e-5f, a, b, c, cfg_scale != 1.0f ? 1 : 0, save ? 1 : 0,
+                        (int64_t)B * C * T, (hipStream_t)stream));
   return JAT_OK;
 }
 
@@ -1097,6 +1187,36 @@ extern "C" int jat_k_gemm_cfg_euler(const uint16_t* A, const uint16_t* W, const 
   a.out = xpred; a.C_out = C; a.T_orig = T;
   KCHK(launch_gemm(a, EPI_UNPATCH, variant, s));
   KCHK(launch_cfg_euler(xpred, z, cfg_scale, t, dt, 1, (int64_t)B * C * T, s));
+  KCHK(launch_patchify(z, nullptr, a_patch, B, B, B, C, 0, T, ntok, s, frames));
+  return JAT_OK;
+}
+// The same for one stage of a two-stage solver (EPI_CFG_STAGE; jat_cfg_euler.h): z_base in the layout z has.  fused == 0:
+// EPI_UNPATCH into xpred, cfg_stage_kernel on z / z_base [B, C, T], patchify of z.
+extern "C" int jat_k_gemm_cfg_stage(const uint16_t* A, const uint16_t* W, const float* bias, int32_t M, int32_t N, int32_t K,
+                                    int32_t rows_per_batch, const float* part_in, int32_t part_in_np, float* z, float* z_base,
+                                    uint16_t* a_patch, float* xpred, const int32_t* frames, float cfg_scale, float t, float a,
+                                    float b, float c, int32_t save, int32_t variant, int32_t fused, void* stream) {
+  if (!A || !W || !z || !z_base || !a_patch || M <= 0 || M % 2 != 0 || N % 128 != 0 || K % 64 != 0 || rows_per_batch <= 0 ||
+      (M / 2) % rows_per_batch != 0)
+    return fail(JAT_E_INVALID, "bad argument");
+  if (part_in && part_in_np != 4 && part_in_np != 8 && part_in_np != 16) return fail(JAT_E_INVALID, "part_in_np must be 4, 8 or 16");
+  if (fused ? !gemm_cfg_euler_supported(variant) : (!gemm_variant(variant) || !xpred))
+    return fail(JAT_E_INVALID, fused ? "variant has no solver-stage epilogue" : "unknown variant or no xpred");
+  hipStream_t s = (hipStream_t)stream;
+  const int ntok = rows_per_batch, B = M / 2 / ntok, C = N / 4, T = ntok * 4;
+  const float den = 1.0f - t + 1e-5f;
+  GemmArgs g{};
+  g.A = A; g.W = W; g.lda = K; g.ldw = K; g.M = M; g.N = N; g.K = K; g.bias = bias; g.ntok = ntok;
+  g.rs_part = part_in; g.rs_np = part_in_np;
+  if (fused) {
+    g.out = z; g.ldo = N; g.ce_patch = a_patch; g.ce_frames = frames;
+    g.ce_scale = cfg_scale; g.ce_denom = den; g.ce_dt = c; g.cs_base = z_base; g.cs_a = a; g.cs_b = b; g.cs_save = save ? 1 : 0;
+    KCHK(launch_gemm(g, EPI_CFG_STAGE, variant, s));
+    return JAT_OK;
+  }
+  g.out = xpred; g.C_out = C; g.T_orig = T;
+  KCHK(launch_gemm(g, EPI_UNPATCH, variant, s));
+  KCHK(launch_cfg_stage(xpred, z, z_base, cfg_scale, den, a, b, c, 1, save ? 1 : 0, (int64_t)B * C * T, s));
   KCHK(launch_patchify(z, nullptr, a_patch, B, B, B, C, 0, T, ntok, s, frames));
   return JAT_OK;
 }

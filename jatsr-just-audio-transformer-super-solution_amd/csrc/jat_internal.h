@@ -90,7 +90,7 @@ struct jat_model {
   mutable int last_fold_np = 0;            // partial-sum slots per row written by the latest folding producer
   float* wfinal32 = nullptr;               // fp32 copy of final_layer.1.weight (fold source)
   bool fold_src_ok = false;                // fp32 copies match the packed weights (false after a training re-pack)
-  std::map<int, std::shared_ptr<FoldTable>> fold_cache;   // by step count; dropped whenever the weights change
+  std::map<std::vector<uint32_t>, std::shared_ptr<FoldTable>> fold_cache;   // by the list of distinct evaluation times (fp32 bits); dropped whenever the weights change
   bool group_copy_stale = false;           // the training re-pack skips wqkv_g: the fused QKV+attention kernel is off until
                                            // the next full jat_model_load_weights
 };

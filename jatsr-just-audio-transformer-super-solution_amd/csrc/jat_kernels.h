@@ -18,6 +18,8 @@ enum GemmEpi : int {
   EPI_UNPATCH = 5,   // out fp32 [B,C,T_orig]: feature c*4+p of token n -> [b,c,4n+p] (:406-420,465-469)
   EPI_CFG_EULER = 7, // CFG sampler tail on PAIRED rows (A = [cond ; uncond], M/2 rows each): out = zp fp32 [M/2,ldo], the latent in
                      // patch layout, updated in place by the CFG combine + Euler step of the two preds; ce_patch = bf16(zp)
+  EPI_CFG_STAGE = 8, // the same tail for one stage of a two-stage solver (jat_cfg_euler.h): cs_save != 0: the Euler formula with step
+                     // ce_dt, the old latent stored into cs_base; else zp = cs_a cs_base + cs_b zp + ce_dt (x - zp) / ce_denom
 };
 
 struct GemmArgs {
@@ -35,9 +37,11 @@ struct GemmArgs {
   // EPI_QKV_ROPE.  EPI_CFG_EULER (jat_cfg_euler.h) keeps its arguments in the same storage (the two never meet, and the argument
   // block of every kernel keeps its size and layout): the next step's bf16 patch operand [M/2, ldo]; the step's scalars (CFG scale,
   // 1 - t + 1e-5, dt); optionally the valid frames per sample [M/2/ntok]: ce_patch reads zero from frame ce_frames[b] on, as
-  // patchify does with tvalid; ce_direct (below): z' = x, the schedule's last steps.
+  // patchify does with tvalid; ce_direct (below): z' = x, the schedule's last steps.  EPI_CFG_STAGE adds, in slots neither of the
+  // two uses: cs_base fp32 [M/2, ldo] (the latent at the start of the step, indexed like zp), the coefficients cs_a, cs_b (the
+  // third is ce_dt) and cs_save (below).
   union { bf16_t* k_out; bf16_t* ce_patch; };
-  bf16_t* vt_out;
+  union { bf16_t* vt_out; float* cs_base; };
   union { int D; float ce_scale; };
   union { int kvD; float ce_denom; };
   union { int npad; float ce_dt; };
@@ -45,7 +49,8 @@ struct GemmArgs {
   const float* rope_sin;
   const float* rope_inv_freq;  // [32] fp32: 1/10000^(2i/64), for in-register sin/cos (coalesced epilogue)
   // EPI_UNPATCH
-  int C_out, T_orig;
+  union { int C_out; float cs_a; };
+  union { int T_orig; float cs_b; };
   // ---- norm folding (sampler path; coalesced-epilogue variants only) ------------------------------------------
   // RMSNorm commutes with the matmul, and in the sampler every row shares the modulation (one t per step), so
   //   (x * rstd * w * (1 + scale) + shift) @ W^T  =  rstd[m] * (bf16(x) @ W'^T) + (shift @ W^T),   W' = W diag(w (1 + scale))
@@ -71,13 +76,14 @@ struct GemmArgs {
   // (fp32 elements); the caller sums the partials in fixed order (launch_sum_partials).  0 / 1: off.
   int ksplit;
   int64_t split_stride;
-  union { int variant_hint; int ce_direct; };   // variant_hint: unused (the plan travels beside the arguments: jat_gemm); kept so that the
+  union { int variant_hint; int ce_direct; int cs_save; };   // variant_hint: unused (the plan travels beside the arguments: jat_gemm); kept so that the
                                                 // kernels' argument block keeps its size
 };
 
 // variant: an id of the tile variant table (gemm_variants.h); retired and unknown ids are rejected
 hipError_t launch_gemm(const GemmArgs& a, int epi, int variant, hipStream_t s);
 // whether launch_gemm runs EPI_CFG_EULER on this variant's own tile (the tiles the final Linear is planned on)
+// (EPI_CFG_STAGE is built for exactly the same tiles)
 bool gemm_cfg_euler_supported(int variant);
 // Fused QKV projection + RoPE + attention for ntok == 128 (W = group-major fused weight [Hkv][5*64+64+64][K]):
 // one block per (sample, KV group); a.out = attention output bf16 [M, D]; a.N = Hkv * 448.
@@ -146,6 +152,10 @@ hipError_t launch_gather_cast_rows(const float* in, int64_t in_stride, bf16_t* o
 // z += ((u + s(c-u)) - z)/(1-t+1e-5)*dt  (or z = x when t >= 0.999)  (infer_test_v3m2.py:161-179)
 hipError_t launch_cfg_euler(const float* xp, float* z, float cfg_scale, float t, float dt, int use_cfg,
                             int64_t n_per_half, hipStream_t s);
+// one stage of a two-stage solver (jat_cfg_euler.h) on z [n_per_half]: save != 0: z_base = z, z += (x - z)/denom * c;
+// else z = a z_base + b z + c (x - z)/denom
+hipError_t launch_cfg_stage(const float* xp, float* z, float* z_base, float cfg_scale, float denom, float a, float b, float c,
+                            int use_cfg, int save, int64_t n_per_half, hipStream_t s);
 // the latent between its two layouts, fp32: zp[(b,tok)][c*4+p] <-> z[b][c][4*tok+p]   (T % 4 == 0)
 hipError_t launch_patch_f32(const float* z, float* zp, int B, int C, int T, hipStream_t s);
 hipError_t launch_unpatch_f32(const float* zp, float* z, int B, int C, int T, hipStream_t s);

@@ -42,6 +42,8 @@ def build_parser():
                    help="Normalization stats file (JSON or PT)")
     p.add_argument("--output-dir", type=str, default="inference_output_v3", help="Output directory")
     p.add_argument("--steps", type=int, default=50, help="Number of sampling steps")
+    p.add_argument("--solver", type=str, default="euler", choices=["euler", "midpoint", "heun"],
+                   help="integration rule: euler (the reference's step), midpoint or heun (two model evaluations per step)")
     p.add_argument("--cfg-scale", type=float, default=1.0, help="CFG guidance scale (1.0 = no CFG)")
     p.add_argument("--total-seconds", type=float, default=None, help="Total output duration in seconds")
     p.add_argument("--device", type=str, default="cuda", help="Device (an AMD GPU; there is no CPU path)")
@@ -114,7 +116,7 @@ def run(args):
     chunk_frames, overlap = jio.frames_for_seconds(16.0), jio.frames_for_seconds(2.0)   # 1378, 172
     plan = chunk_plan(total, chunk_frames, overlap)
     print(f"input {os.path.basename(path)}: {total} frames -> {len(plan)} chunk(s) {[b - a for a, b in plan]}, "
-          f"steps={args.steps}, cfg_scale={args.cfg_scale}")
+          f"steps={args.steps}, cfg_scale={args.cfg_scale}" + (f", solver={args.solver}" if args.solver != "euler" else ""))
     noise = None
     if args.seed is not None:
         g = torch.Generator(device="cpu").manual_seed(args.seed)
@@ -122,7 +124,7 @@ def run(args):
     t0 = time.time()
     gen = sample_long(model, lr[:, :total].to(device), stats["hr_mean"], stats["hr_std"], stats["lr_mean"],
                       stats["lr_std"], num_steps=args.steps, cfg_scale=args.cfg_scale, chunk_frames=chunk_frames,
-                      overlap_frames=overlap, noise=noise)
+                      overlap_frames=overlap, noise=noise, solver=args.solver)
     torch.cuda.synchronize()
     dt = time.time() - t0
     stem = os.path.splitext(os.path.basename(path))[0]

@@ -5,6 +5,10 @@ signature (infer_test_v3m2.py:107-185) and adds an optional `z0` (initial noise;
 with torch.randn at :133).  The whole loop — CFG double batch, 28-block forward, CFG combine, Euler update —
 runs as ONE hipGraph replay inside libjat_hip.so (`jat_sampler_run`); the schedule `linspace(0,1,steps+1)`
 and the `t < 0.999` branch (:173) are evaluated on the host, so no device scalar is ever read back.
+
+`solver` ("euler", the reference's step and the default; "midpoint"; "heun") and `timesteps` (an fp32 grid from 0 to 1, default
+`linspace(0, 1, num_steps + 1)`) choose the integration rule and the time grid (`jat_solver_plan`); the defaults
+run exactly what the reference runs.
 """
 from __future__ import annotations
 
@@ -14,12 +18,50 @@ import torch
 
 from . import _lib as L
 
+SOLVERS = {"euler": 0, "midpoint": 1, "heun": 2}     # JAT_SOLVER_*
+
+
+class SolverEval(C.Structure):
+    """`jat_solver_eval` (include/jat_hip.h): one model evaluation of a run."""
+    _fields_ = [("t", C.c_float), ("time_index", C.c_int32), ("den", C.c_float), ("a", C.c_float), ("b", C.c_float),
+                ("c", C.c_float), ("stage", C.c_int32), ("save", C.c_int32), ("direct", C.c_int32)]
+
+
+def _grid(timesteps):
+    """timesteps -> (ctypes float array or None, tuple of floats or None): the grid as the library reads it, fp32."""
+    if timesteps is None:
+        return None, None
+    vals = [float(v) for v in (timesteps.tolist() if hasattr(timesteps, "tolist") else timesteps)]
+    arr = (C.c_float * len(vals))(*vals)
+    return arr, tuple(arr)
+
+
+def solver_plan(solver="euler", timesteps=None, num_steps=50):
+    """(`jat_solver_eval` list, distinct evaluation times) of `solver` over the grid: `jat_solver_plan`, host code only.
+    An invalid grid or an unknown solver raises ValueError."""
+    if solver not in SOLVERS:
+        raise ValueError(f"solver must be one of {sorted(SOLVERS)}, got {solver!r}")
+    arr, vals = _grid(timesteps)
+    n = len(vals) if vals is not None else int(num_steps) + 1
+    cap = max(2 * (n - 1), 1)
+    evals, distinct = (SolverEval * cap)(), (C.c_float * cap)()
+    ne, nd = C.c_int32(0), C.c_int32(0)
+    L.check(L.lib().jat_solver_plan(arr, n, SOLVERS[solver], evals, cap, C.byref(ne), distinct, C.byref(nd)))
+    return list(evals[:ne.value]), list(distinct[:nd.value])
+
 
 class Sampler:
-    """A captured sampler for one (model, B, T, steps, cfg_scale) bucket: `jat_sampler_create` (include/jat_hip.h)."""
+    """A captured sampler for one (model, B, T, steps, cfg_scale, solver, time grid) bucket: `jat_sampler_create_ex`
+    (include/jat_hip.h).  timesteps: the grid (its length - 1 replaces num_steps); None: linspace(0, 1, num_steps + 1)."""
 
-    def __init__(self, model, B, T, num_steps=50, cfg_scale=1.0):
+    def __init__(self, model, B, T, num_steps=50, cfg_scale=1.0, solver="euler", timesteps=None):
+        if solver not in SOLVERS:
+            raise ValueError(f"solver must be one of {sorted(SOLVERS)}, got {solver!r}")
         self.model = model
+        self.solver = solver
+        self._times, self.timesteps = _grid(timesteps)
+        if self.timesteps is not None:
+            num_steps = len(self.timesteps) - 1
         self.B, self.T, self.steps, self.cfg_scale = int(B), int(T), int(num_steps), float(cfg_scale)
         self.ptr = C.c_void_p()
         self._build()
@@ -32,7 +74,8 @@ class Sampler:
         self._handle = h
         self._version = (h.version, getattr(h, "epoch", 0))   # epoch: bumped by jatsr_amd.train after every weight update
         self._lengths = None                                  # per-row valid frames currently set in the C-side sampler
-        L.check(L.lib().jat_sampler_create(h.ptr, self.B, self.T, self.steps, self.cfg_scale, C.byref(self.ptr)))
+        L.check(L.lib().jat_sampler_create_ex(h.ptr, self.B, self.T, self._times, self.steps + 1, SOLVERS[self.solver],
+                                              self.cfg_scale, C.byref(self.ptr)))
 
     def _destroy(self):
         if self.ptr:
@@ -51,6 +94,11 @@ class Sampler:
         f, a, n = C.c_int32(0), C.c_int32(0), C.c_int64(0)
         L.check(L.lib().jat_sampler_info(self.ptr, C.byref(f), C.byref(a), C.byref(n)))
         return {"folded": bool(f.value), "fused_attn": bool(a.value), "fold_bytes": int(n.value)}
+
+    def evaluations(self):
+        """Model evaluations of one run (each a CFG double batch when cfg_scale != 1): steps for "euler", 2 per step for
+        "midpoint" and "heun", less one for every step that ends at t >= 0.999 and is taken as an Euler step."""
+        return len(solver_plan(self.solver, self.timesteps, self.steps)[0])
 
     def tail_fused(self):
         """True when the steps run the fused tail (`jat_sampler_tail_fused`): CFG combine + Euler update inside the final Linear,
@@ -84,23 +132,26 @@ class Sampler:
         return out
 
 
-def _cached_sampler(model, B, T, num_steps, cfg_scale):
+def _cached_sampler(model, B, T, num_steps, cfg_scale, solver="euler", timesteps=None):
     cache = model.__dict__.setdefault("_jat_samplers", {})
-    key = (B, T, num_steps, float(cfg_scale))
+    key = (B, T, num_steps, float(cfg_scale))             # the reference's sampler keeps the key it always had
+    if solver != "euler" or timesteps is not None:
+        key += (solver, _grid(timesteps)[1])
     s = cache.get(key)
     h = model._get_handle()  # repacks if the weights changed
     if s is None or s._version != (h.version, getattr(h, "epoch", 0)):
-        s = Sampler(model, B, T, num_steps, cfg_scale)
+        s = Sampler(model, B, T, num_steps, cfg_scale, solver, timesteps)
         cache[key] = s
     return s
 
 
 @torch.no_grad()
 def flow_matching_sample(model, lr_latent, num_steps=50, cfg_scale=1.0, device="cuda", verbose=True, z0=None,
-                         use_graph=True, lengths=None):
+                         use_graph=True, lengths=None, solver="euler", timesteps=None):
     """Flow-matching Euler sampling with CFG (x-prediction), reference infer_test_v3m2.py:107-185.
 
     lr_latent: [B, C, T] normalised LR latent.  Returns the generated [B, C, T] latent.
+    solver / timesteps: another integration rule ("midpoint", "heun") or time grid (then num_steps is its length - 1).
     """
     L.require_gpu()
     lr_latent = lr_latent.to(device)
@@ -109,7 +160,9 @@ def flow_matching_sample(model, lr_latent, num_steps=50, cfg_scale=1.0, device="
         z0 = torch.randn(B, Cc, T, device=lr_latent.device)      # :133
     if verbose:
         print(f"  Flow Matching sampling ({num_steps} steps, CFG scale={cfg_scale}) [hipGraph={bool(use_graph)}]")
-    s = _cached_sampler(model, B, T, num_steps, cfg_scale)
+    if timesteps is not None:
+        num_steps = len(timesteps) - 1
+    s = _cached_sampler(model, B, T, num_steps, cfg_scale, solver, timesteps)
     return s.run(lr_latent, z0.to(lr_latent.device), use_graph=use_graph, lengths=lengths)
 
 
@@ -168,7 +221,7 @@ def chunk_groups(lens, pad_short_chunks=True):
 
 @torch.no_grad()
 def sample_long(model, lr_latent, hr_mean, hr_std, lr_mean, lr_std, num_steps=50, cfg_scale=1.0,
-                chunk_frames=1378, overlap_frames=172, noise=None, pad_short_chunks=True):
+                chunk_frames=1378, overlap_frames=172, noise=None, pad_short_chunks=True, solver="euler", timesteps=None):
     """Chunked long-sequence inference == the chunk loop of infer_test_v3m2.py:340-404, with the chunks of a file
     BATCHED into one sampler launch instead of the reference's serial B=1 loop (pad_short_chunks=False: one launch
     per distinct chunk length, the round-1 behaviour).
@@ -206,7 +259,8 @@ def sample_long(model, lr_latent, hr_mean, hr_std, lr_mean, lr_std, num_steps=50
             z0 = torch.cat(noise_rows, 0)
         row_lens = [lens[i] for i in idxs]
         gen = flow_matching_sample(model, batch, num_steps, cfg_scale, device=batch.device, verbose=False, z0=z0,
-                                   lengths=row_lens if any(v != length for v in row_lens) else None)
+                                   lengths=row_lens if any(v != length for v in row_lens) else None, solver=solver,
+                                   timesteps=timesteps)
         gen = channel_affine(gen, hr_mean, hr_std, inverse=True)
         for j, i in enumerate(idxs):
             outs[i] = gen[j:j + 1, :, :lens[i]].contiguous()
