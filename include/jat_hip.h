@@ -234,6 +234,17 @@ int jat_trainer_fwd_bwd(jat_trainer* tr, const float* z_t, const float* t, const
  * non-finite norm leaves parameters and moments untouched (GradScaler.step).  `step` is 1-based (bias correction). */
 int jat_trainer_optim(jat_trainer* tr, float lr, float beta1, float beta2, float eps, float weight_decay,
                       float max_grad_norm, float loss_scale, int32_t step, float* grad_norm_out, void* stream);
+/* Exponential moving average of the parameters (the reference trainers keep none).  ema_flat: a caller-owned device buffer
+ * of `total` floats in the layout of params_flat (16-byte aligned, not params_flat itself), which the caller initialises;
+ * NULL turns the average off (the default).  While one is set, jat_trainer_optim's AdamW pass also does
+ *   ema += (1 - decay) * (p_new - ema)
+ * on the float4 it has just updated; a skipped step (non-finite norm) leaves ema untouched.  decay in [0, 1), else
+ * JAT_E_INVALID; may be called again at any time to change the decay (a warm-up schedule sets it before every step). */
+int jat_trainer_set_ema(jat_trainer* tr, float* ema_flat, float decay);
+/* Exchange the contents of params_flat and ema_flat in place (no temporary), then re-derive every operand copy as
+ * jat_trainer_repack does: forwards and samplers created afterwards run on the average; a second call restores the training
+ * weights bit for bit.  JAT_E_STATE when no average is set. */
+int jat_trainer_swap_ema(jat_trainer* tr, void* stream);
 
 /* ---- per-kernel entry points (unit parity tests; bench roofline leg) --------------------------------- */
 /* y_bf16[M,D] = norm(x[M,D]) (* w) * (1 + scale[b]) + shift[b], b = row / rows_per_batch;
@@ -358,6 +369,12 @@ int jat_k_gelu_bwd(const uint16_t* pre, uint16_t* d, int64_t n, uint64_t seed, i
 int jat_k_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                 float weight_decay, float max_grad_norm, float loss_scale, int32_t step, float* grad_norm_out, void* work,
                 size_t work_bytes, void* stream);
+/* The same step with the moving average of jat_trainer_set_ema fused into the AdamW pass: p, m, v get the bits jat_k_adamw
+ * gives, and ema += (1 - ema_decay) * (p_new - ema) (one subtraction, one fma).  ema not NULL and none of p, g, m, v;
+ * 0 <= ema_decay < 1. */
+int jat_k_adamw_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr, float beta1, float beta2,
+                    float eps, float weight_decay, float max_grad_norm, float loss_scale, float ema_decay, int32_t step,
+                    float* grad_norm_out, void* work, size_t work_bytes, void* stream);
 /* Small-batch Linear backward (adaLN modulation, t_embedder): dW [N, K] = dy[B, N]^T x'[B, K] with x' = silu(x) if silu_x,
  * db [N] = column sums of dy (nullable); B <= 64, K % 4 == 0. */
 int jat_k_small_dw(const float* dy, int64_t ldy, const float* x, int64_t ldx, float* dW, float* db, int32_t B, int32_t N,

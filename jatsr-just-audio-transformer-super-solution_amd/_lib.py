@@ -95,6 +95,7 @@ SIGNATURES = {
     "jat_k_gelu": (C.c_int, [_VP, _VP, _I64, C.c_uint64, _I32, _F32, _VP]),
     "jat_k_gelu_bwd": (C.c_int, [_VP, _VP, _I64, C.c_uint64, _I32, _F32, _VP]),
     "jat_k_adamw": (C.c_int, [_VP, _VP, _VP, _VP, _I64] + [_F32] * 7 + [_I32, _VP, _VP, _SZ, _VP]),
+    "jat_k_adamw_ema": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I64] + [_F32] * 8 + [_I32, _VP, _VP, _SZ, _VP]),
     "jat_k_small_dw": (C.c_int, [_VP, _I64, _VP, _I64, _VP, _VP] + [_I32] * 4 + [_VP]),
     "jat_k_small_dx": (C.c_int, [_VP, _I64, _VP, _I32, _VP] + [_I32] * 4 + [_VP, _VP, _SZ, _VP]),
     "jat_k_latent_loss": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I32, _I32] + [C.c_double] * 7 + [_F32, _VP, _SZ, _VP]),
@@ -111,6 +112,8 @@ SIGNATURES = {
     "jat_trainer_loss_terms": (C.c_int, [_VP, _VP, _VP]),
     "jat_trainer_fwd_bwd": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _F32, C.c_uint64, _VP, _VP, _VP]),
     "jat_trainer_optim": (C.c_int, [_VP, _F32, _F32, _F32, _F32, _F32, _F32, _F32, _I32, _VP, _VP]),
+    "jat_trainer_set_ema": (C.c_int, [_VP, _VP, _F32]),
+    "jat_trainer_swap_ema": (C.c_int, [_VP, _VP]),
     "jat_prof_gemm_site": (C.c_int, [_VP, _I32, _I32]),
     "jat_prof_collect": (C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(_I32), C.POINTER(C.c_double), C.POINTER(_I32)]),
     "jat_dac_decoder_create": (C.c_int, [C.c_void_p, C.POINTER(JatTensorRef), _I32, _I32, _I32, _VP, C.POINTER(_VP)]),

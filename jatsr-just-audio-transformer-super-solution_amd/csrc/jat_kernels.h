@@ -207,7 +207,9 @@ hipError_t launch_latent_loss(const float* pred, const float* target, const floa
                               int strict, int soft, float loss_scale, hipStream_t s);
 hipError_t launch_grad_sqsum(const float* g, int64_t n, float* part, float* norm2, hipStream_t s);
 hipError_t launch_adamw(float* p, float* g, float* m, float* v, int64_t n, const float* norm2, float inv_scale,
-                        float max_norm, float lr, float beta1, float beta2, float eps, float wd, int step, hipStream_t s);
+                        float max_norm, float lr, float beta1, float beta2, float eps, float wd, int step, float* ema,
+                        float ema_decay, hipStream_t s);   // ema != nullptr: also ema += (1 - ema_decay) * (p_new - ema), same pass
+hipError_t launch_swap_f32(float* a, float* b, int64_t n, hipStream_t s);   // a <-> b in place, n % 4 == 0
 hipError_t launch_small_dw(const float* dy, int64_t ldy, const float* x, int64_t ldx, float* dW, float* db, int B, int N,
                            int K, int silu_x, hipStream_t s);
 int small_dx_slab(int N);   // rows of W per partial-sum slab

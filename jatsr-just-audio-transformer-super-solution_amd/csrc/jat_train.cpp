@@ -35,6 +35,8 @@ struct jat_trainer {
   jat_model* m = nullptr;
   int B = 0, T = 0, ntok = 0, M = 0, Mpad = 0, npad = 0;
   float *P = nullptr, *G = nullptr, *m1 = nullptr, *m2 = nullptr;
+  float* ema = nullptr;                // caller-owned moving average of P (jat_trainer_set_ema); nullptr: off
+  float ema_decay = 0.f;
   int64_t total = 0;
   std::vector<std::string> names;
   std::vector<jat_tensor_ref> prefs;   // name -> pointer into P (for the re-pack)
@@ -722,8 +724,27 @@ extern "C" int jat_trainer_optim(jat_trainer* tr, float lr, float beta1, float b
   hipStream_t s = (hipStream_t)stream;
   KCHK(launch_grad_sqsum(tr->G, tr->total, tr->red_part, tr->scal + 2, s));
   KCHK(launch_adamw(tr->P, tr->G, tr->m1, tr->m2, tr->total, tr->scal + 2, 1.0f / loss_scale, max_grad_norm, lr, beta1, beta2,
-                    eps, weight_decay, step, s));
+                    eps, weight_decay, step, tr->ema, tr->ema_decay, s));
   if (grad_norm_out) HIPCHK(hipMemcpyAsync(grad_norm_out, tr->scal + 3, 4, hipMemcpyDeviceToDevice, s));
+  return repack(tr, s);
+}
+
+extern "C" int jat_trainer_set_ema(jat_trainer* tr, float* ema_flat, float decay) {
+  if (!tr) return fail(JAT_E_INVALID, "null argument");
+  if (ema_flat) {
+    if (!(decay >= 0.f && decay < 1.f)) return fail(JAT_E_INVALID, "ema decay must be in [0, 1)");
+    if (((uintptr_t)ema_flat & 15u) != 0 || ema_flat == tr->P) return fail(JAT_E_INVALID, "ema_flat must be a 16-B aligned buffer of its own");
+  }
+  tr->ema = ema_flat;
+  tr->ema_decay = ema_flat ? decay : 0.f;
+  return JAT_OK;
+}
+
+extern "C" int jat_trainer_swap_ema(jat_trainer* tr, void* stream) {
+  if (!tr) return fail(JAT_E_INVALID, "null argument");
+  if (!tr->ema) return fail(JAT_E_STATE, "no moving average is set (jat_trainer_set_ema)");
+  hipStream_t s = (hipStream_t)stream;
+  KCHK(launch_swap_f32(tr->P, tr->ema, tr->total, s));
   return repack(tr, s);
 }
 
@@ -891,7 +912,29 @@ extern "C" int jat_k_adamw(float* p, const float* g, float* m, float* v, int64_t
   float* norm2 = part + train_red_blocks();
   // as jat_trainer_optim chains them: sum of squares of the scaled gradients, then clip + AdamW
   KCHK(launch_grad_sqsum(g, n, part, norm2, s));
-  KCHK(launch_adamw(p, (float*)g, m, v, n, norm2, 1.0f / loss_scale, max_grad_norm, lr, beta1, beta2, eps, weight_decay, step, s));
+  KCHK(launch_adamw(p, (float*)g, m, v, n, norm2, 1.0f / loss_scale, max_grad_norm, lr, beta1, beta2, eps, weight_decay, step,
+                    nullptr, 0.f, s));
+  if (grad_norm_out) HIPCHK(hipMemcpyAsync(grad_norm_out, norm2 + 1, 4, hipMemcpyDeviceToDevice, s));
+  return JAT_OK;
+}
+
+extern "C" int jat_k_adamw_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, float lr, float beta1,
+                               float beta2, float eps, float weight_decay, float max_grad_norm, float loss_scale, float ema_decay,
+                               int32_t step, float* grad_norm_out, void* work, size_t work_bytes, void* stream) {
+  if (!p || !g || !m || !v || !ema || !work) return fail(JAT_E_INVALID, "null argument");
+  if (n <= 0 || n % 4 != 0 || !al16(p) || !al16(g) || !al16(m) || !al16(v) || !al16(ema))
+    return fail(JAT_E_INVALID, "n must be a positive multiple of 4, buffers 16-B aligned");
+  if (step < 1 || !(loss_scale > 0.f)) return fail(JAT_E_INVALID, "step must be >= 1 and loss_scale > 0");
+  if (!(ema_decay >= 0.f && ema_decay < 1.f)) return fail(JAT_E_INVALID, "ema decay must be in [0, 1)");
+  if (ema == p || ema == m || ema == v || ema == g) return fail(JAT_E_INVALID, "ema must be a buffer of its own");
+  const size_t need = ((size_t)train_red_blocks() + 2) * 4;
+  if (work_bytes < need) return fail(JAT_E_INVALID, "work needs %zu bytes", need);
+  hipStream_t s = (hipStream_t)stream;
+  float* part = (float*)work;
+  float* norm2 = part + train_red_blocks();
+  KCHK(launch_grad_sqsum(g, n, part, norm2, s));
+  KCHK(launch_adamw(p, (float*)g, m, v, n, norm2, 1.0f / loss_scale, max_grad_norm, lr, beta1, beta2, eps, weight_decay, step, ema,
+                    ema_decay, s));
   if (grad_norm_out) HIPCHK(hipMemcpyAsync(grad_norm_out, norm2 + 1, 4, hipMemcpyDeviceToDevice, s));
   return JAT_OK;
 }

@@ -903,16 +903,22 @@ __global__ void __launch_bounds__(256) sqsum_kernel(const float* __restrict__ g,
 }
 // norm2[0] = sum g^2 of the SCALED gradients, norm2[1] = its square root.  inv_scale undoes the loss scaling.
 // A non-finite norm skips the update (GradScaler.step semantics, train_ddp_v3m2.py:618).
-__global__ void __launch_bounds__(256) adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                    float* __restrict__ v, int64_t n, const float* __restrict__ norm2,
-                                                    float inv_scale, float max_norm, float lr, float beta1, float beta2,
-                                                    float eps, float wd, float bc1, float bc2_sqrt) {
+// EMA: the same float4 also advances an exponential moving average of the parameters, e += (1 - decay) * (p_new - e), as one
+// subtraction and one fma: two roundings, the first relative to the increment (2 more streams on top of AdamW's 7, no second
+// pass over p).  The early return leaves e untouched like p, m and v.
+template <bool EMA>
+__device__ __forceinline__ void adamw_body(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                           float* __restrict__ v, float* __restrict__ ema, int64_t n,
+                                           const float* __restrict__ norm2, float inv_scale, float max_norm, float lr, float beta1,
+                                           float beta2, float eps, float wd, float bc1, float bc2_sqrt, float ema_rate) {
   const float total = norm2[1] * inv_scale;
   if (!(total == total) || total > 3.0e38f) return;
   float coef = inv_scale;
   if (max_norm > 0.f) coef *= fminf(1.0f, max_norm / (total + 1e-6f));
   for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += (int64_t)gridDim.x * 1024) {
     f32x4_t pp = *(const f32x4_t*)(p + i), gg = *(const f32x4_t*)(g + i), mm = *(const f32x4_t*)(m + i), vv = *(const f32x4_t*)(v + i);
+    f32x4_t ee;
+    if constexpr (EMA) ee = *(const f32x4_t*)(ema + i);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const float gr = gg[j] * coef;   // unscaled, clipped gradient (not written back: nothing reads it after the step)
@@ -921,9 +927,39 @@ __global__ void __launch_bounds__(256) adamw_kernel(float* __restrict__ p, const
       vv[j] = beta2 * vv[j] + (1.0f - beta2) * gr * gr;
       const float denom = sqrtf(vv[j]) / bc2_sqrt + eps;
       pp[j] -= (lr / bc1) * (mm[j] / denom);
+      if constexpr (EMA) ee[j] = fmaf(ema_rate, pp[j] - ee[j], ee[j]);
     }
     *(f32x4_t*)(p + i) = pp; *(f32x4_t*)(m + i) = mm; *(f32x4_t*)(v + i) = vv;
+    if constexpr (EMA) *(f32x4_t*)(ema + i) = ee;
   }
+}
+__global__ void __launch_bounds__(256) adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                    float* __restrict__ v, int64_t n, const float* __restrict__ norm2,
+                                                    float inv_scale, float max_norm, float lr, float beta1, float beta2,
+                                                    float eps, float wd, float bc1, float bc2_sqrt) {
+  adamw_body<false>(p, g, m, v, nullptr, n, norm2, inv_scale, max_norm, lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, 0.f);
+}
+__global__ void __launch_bounds__(256) adamw_ema_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                        float* __restrict__ v, float* __restrict__ ema, int64_t n,
+                                                        const float* __restrict__ norm2, float inv_scale, float max_norm, float lr,
+                                                        float beta1, float beta2, float eps, float wd, float bc1, float bc2_sqrt,
+                                                        float ema_decay) {
+  // 1 - decay is exact in fp32 for decay in [0.5, 1) and for 0
+  adamw_body<true>(p, g, m, v, ema, n, norm2, inv_scale, max_norm, lr, beta1, beta2, eps, wd, bc1, bc2_sqrt, 1.0f - ema_decay);
+}
+// a <-> b, one float4 of each per thread (n % 4 == 0): the trainer's parameters against their moving average, in place
+__global__ void __launch_bounds__(256) swap_f32_kernel(float* __restrict__ a, float* __restrict__ b, int64_t n) {
+  const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (i >= n) return;
+  const f32x4_t x = *(const f32x4_t*)(a + i), y = *(const f32x4_t*)(b + i);
+  *(f32x4_t*)(a + i) = y; *(f32x4_t*)(b + i) = x;
+}
+hipError_t launch_swap_f32(float* a, float* b, int64_t n, hipStream_t s) {
+  if (n <= 0 || n % 4 != 0 || a == b) return hipErrorInvalidValue;
+  const int64_t blocks = (n / 4 + 255) / 256;
+  if (blocks > 0x7fffffff) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(swap_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, s, a, b, n);
+  return hipGetLastError();
 }
 hipError_t launch_grad_sqsum(const float* g, int64_t n, float* part, float* norm2, hipStream_t s) {
   if (n % 4 != 0) return hipErrorInvalidValue;
@@ -932,16 +968,22 @@ hipError_t launch_grad_sqsum(const float* g, int64_t n, float* part, float* norm
   return hipGetLastError();
 }
 hipError_t launch_adamw(float* p, float* g, float* m, float* v, int64_t n, const float* norm2, float inv_scale,
-                        float max_norm, float lr, float beta1, float beta2, float eps, float wd, int step, hipStream_t s) {
+                        float max_norm, float lr, float beta1, float beta2, float eps, float wd, int step, float* ema,
+                        float ema_decay, hipStream_t s) {
   if (n % 4 != 0 || step < 1) return hipErrorInvalidValue;
+  if (ema && !(ema_decay >= 0.f && ema_decay < 1.f)) return hipErrorInvalidValue;
   const double bc1 = 1.0 - pow((double)beta1, step), bc2 = 1.0 - pow((double)beta2, step);
   // one float4 of each of the four streams per thread, no grid-stride loop: 2048 looping blocks ran this 21 GB pass at 4.7 TB/s,
   // the one-pass grid is 0.4-0.9 ms faster per step on the boxes measured (profiles/r03/adamw_grid_sweep.log); JAT_ADAMW_BLOCKS: A/B
   static const int blocks_env = getenv("JAT_ADAMW_BLOCKS") ? atoi(getenv("JAT_ADAMW_BLOCKS")) : 0;
   const int64_t full = (n / 4 + 255) / 256;
   const unsigned blocks = blocks_env > 0 ? (unsigned)blocks_env : (unsigned)(full < 1 ? 1 : full);
-  hipLaunchKernelGGL(adamw_kernel, dim3(blocks), dim3(256), 0, s, p, g, m, v, n, norm2, inv_scale, max_norm, lr, beta1, beta2,
-                     eps, wd, (float)bc1, (float)sqrt(bc2));
+  if (ema)     // ema == nullptr: the launch without the moving average, unchanged
+    hipLaunchKernelGGL(adamw_ema_kernel, dim3(blocks), dim3(256), 0, s, p, g, m, v, ema, n, norm2, inv_scale, max_norm, lr, beta1,
+                       beta2, eps, wd, (float)bc1, (float)sqrt(bc2), ema_decay);
+  else
+    hipLaunchKernelGGL(adamw_kernel, dim3(blocks), dim3(256), 0, s, p, g, m, v, n, norm2, inv_scale, max_norm, lr, beta1, beta2,
+                       eps, wd, (float)bc1, (float)sqrt(bc2));
   return hipGetLastError();
 }
 

@@ -29,6 +29,8 @@ DEFAULTS = dict(seed=42, data_dir="data_processed_v13_final", stats_file="global
 MODEL_DIMS = ("input_channels", "patch_len", "hidden_size", "depth", "num_q_heads", "num_kv_heads", "bottleneck_dim", "mlp_ratio")
 TRAIN_TAGS = {"mse": "Train/MSE_Loss", "freq": "Train/LatentPerc_FreqLoss", "ms": "Train/LatentPerc_MSLoss",
               "consistency": "Train/LatentPerc_ConsistencyLoss", "latent": "Train/LatentPerc_TotalLoss"}
+EMA_VAL_TAGS = {"mse_loss": "Val/EMA_MSE_Loss", "freq_loss": "Val/EMA_LatentPerc_FreqLoss", "ms_loss": "Val/EMA_LatentPerc_MSLoss",
+                "consistency_loss": "Val/EMA_LatentPerc_ConsistencyLoss", "total_latent_loss": "Val/EMA_LatentPerc_TotalLoss"}
 VAL_TAGS = {"mse_loss": "Val/MSE_Loss", "freq_loss": "Val/LatentPerc_FreqLoss", "ms_loss": "Val/LatentPerc_MSLoss",
             "consistency_loss": "Val/LatentPerc_ConsistencyLoss", "total_latent_loss": "Val/LatentPerc_TotalLoss"}
 
@@ -58,6 +60,11 @@ def build_parser():
     p.add_argument("--no-adaptive-noise", dest="use_adaptive_noise", action="store_false")
     p.add_argument("--latent-loss-weight", type=float, default=d["latent_loss_weight"], help="0: MSE only (train_ddp_v3m2.py)")
     p.add_argument("--loss", default="mse", help="mse or charbonnier (train_ddp_v3m2mod1.py; needs --latent-loss-weight 0)")
+    p.add_argument("--ema-decay", type=float, default=None,
+                   help="keep an exponential moving average of the weights with this decay (e.g. 0.9999): validated beside the "
+                        "raw weights, stored in every checkpoint (infer --ema samples from it); default: none")
+    p.add_argument("--no-ema-warmup", dest="ema_warmup", action="store_false",
+                   help="with --ema-decay: the constant decay from the first step instead of min(decay, (1 + n) / (10 + n))")
     p.add_argument("--amp-dtype", default=None, choices=["bf16", "fp16"], help="must match the loaded library (JAT_OPERAND_DTYPE)")
     p.add_argument("--samples-per-epoch-multiplier", type=int, default=d["samples_per_epoch_multiplier"])
     p.add_argument("--max-resident-gb", type=float, default=None, help="device memory for the data set; default half of what is free")
@@ -133,7 +140,7 @@ def build_trainer(args, model, total_steps, process_group=None, rank=0, distribu
                    condition_noise_ratio=args.condition_noise_ratio, use_adaptive_noise=args.use_adaptive_noise,
                    warmup_steps=args.warmup_steps, total_steps=total_steps, process_group=process_group,
                    seed=args.seed + rank, latent_loss_weight=args.latent_loss_weight, distributed=distributed,
-                   amp_dtype=args.amp_dtype, loss=args.loss)
+                   amp_dtype=args.amp_dtype, loss=args.loss, ema_decay=args.ema_decay, ema_warmup=args.ema_warmup)
 
 
 def loop_step(trainer, store, plans, i, stats, lr, monitor):
@@ -234,7 +241,8 @@ def run(args):
         if state is not None:
             trainer.gen.set_state(state.cpu())
         if master:
-            print(f"resumed at epoch {start_epoch}, step {trainer.global_step}")
+            print(f"resumed at epoch {start_epoch}, step {trainer.global_step}" +
+                  (f", moving average after {trainer.ema_updates} updates" if trainer.ema is not None else ""))
     flags = {k: v for k, v in vars(args).items() if isinstance(v, (int, float, str, bool, type(None)))}
 
     def save(name, epoch):
@@ -294,14 +302,22 @@ def run(args):
             def val_iter():
                 for vb in vbatches:
                     yield val_store.batch(*val_batch_plan(val_store.lengths, T, vb, mult), stats)
-            val_loss, val_std, metrics = trainer.validate(val_iter(), normalised=True,
-                                                          t=_ValDraws(args.seed, B, C, T, device, "t", rank),
-                                                          noise=_ValDraws(args.seed, B, C, T, device, "noise", rank))
+            def validate():
+                return trainer.validate(val_iter(), normalised=True, t=_ValDraws(args.seed, B, C, T, device, "t", rank),
+                                        noise=_ValDraws(args.seed, B, C, T, device, "noise", rank))
+            val_loss, val_std, metrics = validate()
             rec = {"epoch": epoch, "Val/Loss": val_loss, "Val/Loss_Std": val_std}
             rec.update({VAL_TAGS[k]: v for k, v in metrics.items() if k in VAL_TAGS})
+            if trainer.ema is not None:
+                # the same batches, t and noise on the moving average: a paired comparison.  best.pt stays chosen by the raw loss
+                with trainer.ema_weights():
+                    ema_loss, ema_std, ema_metrics = validate()
+                rec.update({"Val/EMA_Loss": ema_loss, "Val/EMA_Loss_Std": ema_std})
+                rec.update({EMA_VAL_TAGS[k]: v for k, v in ema_metrics.items() if k in EMA_VAL_TAGS})
             log(rec)
             if master:
-                print(f"validation loss {val_loss:.5f} +- {val_std:.5f} (best {best_val:.5f})")
+                print(f"validation loss {val_loss:.5f} +- {val_std:.5f} (best {best_val:.5f})" +
+                      (f", on the moving average {ema_loss:.5f} +- {ema_std:.5f}" if trainer.ema is not None else ""))
             if val_loss < best_val:
                 best_val = val_loss
                 save("best.pt", epoch)

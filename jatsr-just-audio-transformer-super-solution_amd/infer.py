@@ -50,6 +50,9 @@ def build_parser():
     p.add_argument("--input-file", type=str, default=None, help="Specific input file; default: first file in val-dir")
     p.add_argument("--layernorm", action="store_true", help="checkpoint is a v3mod2 (LayerNorm, JaT_AudioSR_V2) model")
     p.add_argument("--seed", type=int, default=None, help="seed for the initial noise")
+    p.add_argument("--ema", action="store_true",
+                   help="sample from the checkpoint's moving average of the weights (written by fit --ema-decay) instead of the "
+                        "last iterate")
     p.add_argument("--dac-weights", type=str, default=None,
                    help="DAC 44.1 kHz weight file (.safetensors/.pt/.bin/.pth); decode to WAV when given")
     p.add_argument("--dac-precision", type=str, default="bf16x3", choices=["bf16x3", "bf16"],
@@ -92,7 +95,8 @@ def run(args):
         raise SystemExit("--metrics needs --dac-weights and an HR ground truth (--simulate-lr, or a latent file with hr_latent)")
     device = torch.device(args.device)
     os.makedirs(args.output_dir, exist_ok=True)
-    model = load_model(args.checkpoint, device=device, cls=JaT_AudioSR_V2 if args.layernorm else JaT_AudioSR_V3)
+    model = load_model(args.checkpoint, device=device, cls=JaT_AudioSR_V2 if args.layernorm else JaT_AudioSR_V3,
+                       use_ema=args.ema)
     codec = source = None
     if args.input_audio:
         path = args.input_audio

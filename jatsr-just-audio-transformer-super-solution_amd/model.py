@@ -387,16 +387,28 @@ class JaT_AudioSR_V2(JaT_AudioSR_V3):
     _NORM = "ln"
 
 
-def load_model(checkpoint, device="cuda", cls=None):
+def select_state_dict(checkpoint, use_ema=False):
+    """-> (state dict, "ema" | "raw"): the weights `load_model` takes from a checkpoint dict — `model_state_dict`, or with
+    use_ema the moving average a `Trainer(ema_decay=...)` stores beside it (`ema_state_dict`)."""
+    if not use_ema:
+        return checkpoint["model_state_dict"], "raw"
+    if checkpoint.get("ema_state_dict") is None:
+        raise KeyError("use_ema=True, but the checkpoint holds no 'ema_state_dict': it was written by a run without a moving "
+                       "average (fit --ema-decay / Trainer(ema_decay=...))")
+    return checkpoint["ema_state_dict"], "ema"
+
+
+def load_model(checkpoint, device="cuda", cls=None, use_ema=False):
     """== load_model (infer_test_v3m2.py:33-94): checkpoint dict (or path) -> eval-mode model on `device`.
     Takes 'config' from the checkpoint when present (defaults :41-53), strips '_orig_mod.' / 'module.'
-    prefixes (:64-71), loads with strict=False (:74)."""
+    prefixes (:64-71), loads with strict=False (:74).  use_ema: load the moving average of the weights instead
+    (`select_state_dict`; KeyError when the checkpoint has none); load_info["weights"] says which were taken."""
     if isinstance(checkpoint, (str, bytes)) or hasattr(checkpoint, "__fspath__"):
         checkpoint = torch.load(checkpoint, map_location="cpu", weights_only=False)
     cfg = dict(checkpoint.get("config", dict(input_channels=1024, cond_channels=1024, patch_len=4, hidden_size=1280,
                                              depth=28, num_q_heads=20, num_kv_heads=4, bottleneck_dim=512,
                                              mlp_ratio=4.0, dropout=0.1, drop_path_rate=0.05)))
-    sd = checkpoint["model_state_dict"]
+    sd, which = select_state_dict(checkpoint, use_ema)
     if any(k.startswith("_orig_mod.") for k in sd):
         sd = {k.replace("_orig_mod.", ""): v for k, v in sd.items()}
     if any(k.startswith("module.") for k in sd):
@@ -406,5 +418,5 @@ def load_model(checkpoint, device="cuda", cls=None):
     model = cls(**cfg)
     missing, unexpected = model.load_state_dict({k: torch.as_tensor(v).float() for k, v in sd.items()}, strict=False)
     model.load_info = dict(missing=list(missing), unexpected=list(unexpected), epoch=checkpoint.get("epoch", 0),
-                           global_step=checkpoint.get("global_step", 0))
+                           global_step=checkpoint.get("global_step", 0), weights=which)
     return model.to(device).eval()

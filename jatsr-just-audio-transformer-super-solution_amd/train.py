@@ -15,8 +15,10 @@ layer, site, element) inside the kernels — nn.Dropout / drop_path semantics, n
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import math
+import warnings
 import weakref
 
 import torch
@@ -39,6 +41,14 @@ def get_lr(step, total_steps, warmup_steps, base_lr):
         return base_lr * (step / max(1, warmup_steps))
     progress = (step - warmup_steps) / max(1, total_steps - warmup_steps)
     return base_lr * 0.5 * (1.0 + math.cos(math.pi * progress))
+
+
+def ema_decay_at(n, decay, warmup=True):
+    """Decay of EMA update number n (1-based: `ema_updates + 1`, the update about to happen; equal to the optimiser step
+    except after a resume from a checkpoint without an average, where the average starts again at n = 1).  With warm-up min(decay, (1 + n) / (10 + n)):
+    2/11, 3/12, ... so that the average forgets its starting point (the initial weights) in tens of steps instead of
+    1 / (1 - decay); without, `decay` throughout."""
+    return min(float(decay), (1.0 + n) / (10.0 + n)) if warmup else float(decay)
 
 
 def flat_layout(named_shapes):
@@ -153,7 +163,7 @@ class Trainer:
                  warmup_steps=1000, total_steps=None, use_grad_scaler=True, process_group=None, seed=None,
                  latent_loss_weight=0.0, freq_loss_weight=0.5, ms_loss_weight=0.5, consistency_weight=0.1,
                  low_freq_phase_ratio=0.3, strict_cutoff=0.30, soft_cutoff=0.36, overlap_grad_allreduce=True,
-                 distributed=True, amp_dtype=None, loss="mse", charbonnier_eps=1e-6):
+                 distributed=True, amp_dtype=None, loss="mse", charbonnier_eps=1e-6, ema_decay=None, ema_warmup=True):
         """latent_loss_weight > 0 selects the v3mod2 trainer's loss, MSE + latent perceptual loss
         (train_ddp_v3mod2.py:53-321,362-372,889-896; its TrainConfig uses 0.3 with the other defaults given here, no CFG
         dropout and condition_noise_ratio 0.05); 0 is the MSE-only loss of train_ddp_v3m2.py:585.
@@ -161,6 +171,9 @@ class Trainer:
         mean(sqrt((pred - target)^2 + charbonnier_eps)) (train_ddp_v3m2mod1.py:72-101, `use_charbonnier_loss` / `charbonnier_eps`
         :150-151), used for the training step and for validation (:817-819); not combinable with the latent perceptual loss.
         distributed=False: never issue a collective even if a process group exists (a single rank timing a local step).
+        ema_decay: keep an exponential moving average of the weights (the reference keeps none), updated inside the AdamW
+        pass: `ema`, a fifth flat buffer, `ema_weights()` to run on it, `ema_state_dict()` to read it.  ema_warmup: the
+        schedule of `ema_decay_at`.  None: no buffer, no extra work.
         amp_dtype: "bf16" (train_ddp_v3m2.py:545) or "fp16" (`torch.amp.autocast('cuda')` of train_ddp_v3mod2.py:854, with
         the dynamic loss scale of :745); must match the operand dtype of the loaded library, which is a process-level
         choice (JAT_OPERAND_DTYPE=fp16 loads libjat_hip_fp16.so).  None: whatever the library is."""
@@ -171,6 +184,8 @@ class Trainer:
         if loss == "charbonnier" and float(latent_loss_weight) != 0.0:
             raise ValueError("the latent perceptual loss is defined on top of the MSE loss (train_ddp_v3mod2.py:889-896); "
                              "the Charbonnier trainer (train_ddp_v3m2mod1.py) has no latent term")
+        if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError(f"ema_decay must be in [0, 1), got {ema_decay!r}")
         L.require_gpu()
         have = L.operand_dtype()
         want = {None: have, "bf16": "bf16", "bfloat16": "bf16", "fp16": "fp16", "float16": "fp16"}[amp_dtype]
@@ -250,6 +265,14 @@ class Trainer:
         L.check(L.lib().jat_trainer_set_latent_loss(self.ptr, *self.latent_loss.values()))
         L.check(L.lib().jat_trainer_set_charbonnier(self.ptr, self.charbonnier_eps if loss == "charbonnier" else 0.0))
         self._terms = torch.zeros(6, dtype=torch.float32, device=dev)
+        # moving average of the weights: taken after the broadcast above, so every rank starts from the same copy and, as all
+        # ranks apply the same all-reduced step, stays equal without a collective of its own
+        self.ema_decay, self.ema_warmup = (None if ema_decay is None else float(ema_decay)), bool(ema_warmup)
+        self.ema = self.params.clone() if ema_decay is not None else None
+        self.ema_updates = 0
+        self._in_ema = False
+        if self.ema is not None:
+            L.check(L.lib().jat_trainer_set_ema(self.ptr, L.ptr(self.ema), ema_decay_at(1, self.ema_decay, self.ema_warmup)))
         # gradient all-reduce overlapped with the backward: one async all-reduce per parameter slice as soon as its
         # last gradient kernel is enqueued (jat_trainer_set_grad_hook), on a side stream ordered by an event
         self.overlap = overlap_grad_allreduce      # True: when world_size > 1; "force": also with one rank (tests)
@@ -262,6 +285,11 @@ class Trainer:
         if self._detached:
             raise L.JatError("this Trainer was superseded: a newer Trainer owns the model's parameters (they are views of "
                              "the newer trainer's flat buffer)")
+
+    def _check_not_in_ema(self, what):
+        if self._in_ema:
+            raise L.JatError(f"{what} inside ema_weights(): the parameters and their moving average are exchanged; leave the "
+                             "context first")
 
     def _dist_on(self):
         import torch.distributed as dist
@@ -372,6 +400,7 @@ class Trainer:
                 raise ValueError(f"expected fp32 CUDA [{self.B}, {self.model.input_channels}, {self.T}], got "
                                  f"{tuple(x.shape)} {x.dtype} on {x.device}")
         self._check_attached()
+        self._check_not_in_ema("forward_backward")
         self.model._get_handle()     # parameters overwritten through PyTorch (load_state_dict)? re-pack, incl. this trainer's copies
         pred = torch.empty_like(z_t) if want_pred else None
         self._pending, self._covered = [], 0
@@ -388,6 +417,7 @@ class Trainer:
         """All-reduce, unscale, clip_grad_norm_(grad_clip), AdamW, re-pack.  Returns (loss, grad_norm) as floats —
         the one host synchronisation of the step, like the reference's `.item()` calls (train_ddp_v3m2.py:615,622)."""
         self._check_attached()
+        self._check_not_in_ema("optimizer_step")
         if self._pending:          # slices were reduced under the backward: the step's stream waits for the last of them
             for w in self._pending:
                 w.wait()
@@ -399,6 +429,9 @@ class Trainer:
         if lr is None:
             lr = get_lr(self.global_step, self.total_steps, self.warmup_steps, self.base_lr) if self.total_steps else self.base_lr
         scale = self.scaler.scale * world
+        if self.ema is not None:
+            L.check(L.lib().jat_trainer_set_ema(self.ptr, L.ptr(self.ema),
+                                                ema_decay_at(self.ema_updates + 1, self.ema_decay, self.ema_warmup)))
         L.check(L.lib().jat_trainer_optim(self.ptr, float(lr), float(self.betas[0]), float(self.betas[1]), float(self.eps),
                                           float(self.weight_decay), float(self.grad_clip or 0.0), float(scale),
                                           self.opt_step + 1, C.c_void_p(self._scal.data_ptr() + 4), L.stream_ptr()))
@@ -409,6 +442,8 @@ class Trainer:
         self.global_step += 1                   # counts batches, skipped or not (train_ddp_v3m2.py:634)
         if not found_inf:
             self.opt_step += 1
+            if self.ema is not None:
+                self.ema_updates += 1
             self._handle.epoch += 1      # the weights changed under the model: cached samplers (mod tables, graphs) are stale
         self.last_lr = lr
         return loss, gnorm
@@ -514,12 +549,67 @@ class Trainer:
             self.exp_avg_sq[off:off + n].view(shape).copy_(st["exp_avg_sq"].to(self.device, torch.float32))
             self.opt_step = int(float(st["step"]))       # AdamW's own counter: bias correction resumes where it stopped
 
+    # -- moving average of the weights ---------------------------------------------------------------------------------------
+    def _swap_ema(self):
+        # Only the current stream is waited for.  The re-pack's transposed copies may still be reading `params` on the trainer's
+        # second stream when the next swap writes it; that is harmless: that stream runs in order, the next re-pack rebuilds
+        # those copies behind an event recorded after the swap, and nothing reads them in between (forward_backward is barred
+        # inside ema_weights(), the model's forward does not use them).
+        L.check(L.lib().jat_trainer_swap_ema(self.ptr, L.stream_ptr()))
+        torch.cuda.current_stream().synchronize()
+        self._handle.epoch += 1
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Run on the moving average: inside, the model's parameters (views of `params`) hold the average and `ema` holds the
+        training weights — exchanged in place, no third copy — so `model(...)`, `validate`, samplers and `model.state_dict()`
+        see the average; on exit they are exchanged back, bit for bit.  Samplers cached on either side become stale.  Stepping,
+        `forward_backward`, `save_checkpoint` and `load_checkpoint` raise inside."""
+        self._check_attached()
+        if self.ema is None:
+            raise L.JatError("this Trainer keeps no moving average (ema_decay=None)")
+        self._check_not_in_ema("ema_weights()")
+        self.model._get_handle()     # a pending re-pack (load_state_dict) happens on the training weights, not in between
+        self._swap_ema()
+        self._in_ema = True
+        try:
+            yield self
+        finally:
+            self._in_ema = False
+            self._swap_ema()
+
+    def ema_state_dict(self):
+        """The moving average under the keys and shapes of `model.state_dict()`, fp32 on the CPU; read from the `ema` buffer
+        (inside `ema_weights()`: from where the average then is), without exchanging anything."""
+        if self.ema is None:
+            raise L.JatError("this Trainer keeps no moving average (ema_decay=None)")
+        src = self.params if self._in_ema else self.ema
+        by_name = {k: src[off:off + n].view(shape) for k, off, n, shape in self.layout}
+        return {k: (by_name[k] if k in by_name else v).detach().to("cpu", torch.float32).clone()
+                for k, v in self.model.state_dict().items()}
+
+    def _load_ema(self, sd):
+        """sd: a state dict (None: start the average from the current weights)."""
+        if sd is None:
+            self.ema.copy_(self.params)
+            return
+        sd = {k.replace("_orig_mod.", "").replace("module.", ""): v for k, v in sd.items()}
+        self.ema.copy_(self.params)        # tensors the dict does not name, and the zero gaps, as in the weights
+        for k, off, n, shape in self.layout:
+            if k in sd:
+                self.ema[off:off + n].view(shape).copy_(torch.as_tensor(sd[k]).to(self.device, torch.float32))
+
     def save_checkpoint(self, path, epoch=0, best_val_loss=float("inf"), extra=None):
-        """The reference's checkpoint dict (train_ddp_v3mod2.py:1137-1146); `extra`: further entries merged into it."""
+        """The reference's checkpoint dict (train_ddp_v3mod2.py:1137-1146); `extra`: further entries merged into it.  With a
+        moving average also ema_state_dict, ema_decay, ema_warmup, ema_updates (the reference's loader ignores them)."""
+        self._check_not_in_ema("save_checkpoint")
         ck = dict(epoch=epoch, global_step=self.global_step, best_val_loss=best_val_loss,
                   model_state_dict={k: v.detach().cpu().clone() for k, v in self.model.state_dict().items()},
                   optimizer_state_dict=self.optimizer_state_dict(), scaler_state_dict=self.scaler.state_dict(),
                   config=dict(self.model.config(), dropout=max(self.dropout), drop_path_rate=max(self.drop_path)))
+        if self.ema is not None:
+            ck.update(ema_state_dict=self.ema_state_dict(), ema_decay=self.ema_decay, ema_warmup=self.ema_warmup,
+                      ema_updates=self.ema_updates)
         if extra:
             ck.update(extra)
         torch.save(ck, path)
@@ -527,7 +617,11 @@ class Trainer:
 
     def load_checkpoint(self, checkpoint):
         """Resume (train_ddp_v3m2.py:443-500): model weights (prefixes stripped, strict=False), AdamW moments, step
-        counter and loss scale from a checkpoint dict or path in the reference's layout."""
+        counter and loss scale from a checkpoint dict or path in the reference's layout.  A trainer with a moving average
+        takes ema_state_dict, ema_decay, ema_warmup and ema_updates when the checkpoint has them (the stored decay and warm-up
+        replace the constructor's: the resumed run continues the run that was saved), else starts the average from the loaded
+        weights with ema_updates = 0; one without ignores them, with a warning that the average is dropped."""
+        self._check_not_in_ema("load_checkpoint")
         if isinstance(checkpoint, (str, bytes)) or hasattr(checkpoint, "__fspath__"):
             checkpoint = torch.load(checkpoint, map_location="cpu", weights_only=False)
         sd = checkpoint["model_state_dict"]
@@ -541,6 +635,18 @@ class Trainer:
         if checkpoint.get("scaler_state_dict") and self.scaler.enabled:
             self.scaler.load_state_dict(checkpoint["scaler_state_dict"])
         self.global_step = int(checkpoint.get("global_step", self.opt_step))
+        if self.ema is not None:
+            have = checkpoint.get("ema_state_dict")
+            self._load_ema(have)
+            self.ema_updates = int(checkpoint.get("ema_updates", 0)) if have is not None else 0
+            if have is not None:
+                if checkpoint.get("ema_decay") is not None:
+                    self.ema_decay = float(checkpoint["ema_decay"])
+                if checkpoint.get("ema_warmup") is not None:
+                    self.ema_warmup = bool(checkpoint["ema_warmup"])
+        elif checkpoint.get("ema_state_dict") is not None:
+            warnings.warn("the checkpoint holds a moving average of the weights (ema_state_dict), but this Trainer keeps none "
+                          "(ema_decay=None; fit: --ema-decay): the average is not loaded and later checkpoints will not carry it")
         self._weights_replaced()
         return checkpoint.get("epoch", 0)
 
