@@ -317,12 +317,18 @@ int jat_k_weight_grad(const uint16_t* dY, const uint16_t* X, float* dW, float* d
 int jat_k_attention(const uint16_t* q, const uint16_t* k, const uint16_t* vt, uint16_t* o, int32_t B,
                     int32_t N, int32_t Hq, int32_t Hkv, int32_t Npad, void* stream);
 /* The v3mod2 loss (see jat_trainer_set_latent_loss) on pred / target / clean-LR tensors [rows, T]: dpred = d(total *
- * loss_scale)/d pred, out6 = {total, mse, freq, ms, consistency, weighted latent sum}; work: T*8 (rounded up to 256)
- * + rows*32 bytes of device scratch. */
+ * loss_scale)/d pred, out6 = {total, mse, freq, ms, consistency, weighted latent sum}; work: align_up(T*8, 256) + rows*32
+ * bytes of device scratch. */
 int jat_k_latent_loss(const float* pred, const float* target, const float* lr, float* dpred, float* out6,
                       int32_t rows, int32_t T, double latent_weight, double freq_weight, double ms_weight,
                       double consistency_weight, double low_freq_phase_ratio, double strict_cutoff, double soft_cutoff,
                       float loss_scale, void* work, size_t work_bytes, void* stream);
+/* The code path the v3mod2 loss takes at sequence length T, which depends on T alone: kind 0 = rejected (T too long for the
+ * kernels' LDS image; jat_k_latent_loss and the trainer fail), 1 = direct DFT kernel with (a, b) = (bins, samples) per thread
+ * (1, 2), (2, 4) or (3, 6), the last looping in chunks beyond 768 bins / 1536 samples, 2 = DFT factored T = a * b with a the
+ * largest divisor of T not above sqrt(T).  lds_bytes = dynamic LDS of that launch (kind 0: what the direct kernel would need).
+ * Host arithmetic only: launches nothing and needs no GPU. */
+int jat_k_latent_loss_plan(int32_t T, int32_t* kind, int32_t* a, int32_t* b, int64_t* lds_bytes);
 /* Reconstruction loss on n elements: eps == 0: F.mse_loss (train_ddp_v3m2.py:585), eps > 0: charbonnier_loss
  * (train_ddp_v3m2mod1.py:72-101); dpred = d(loss * loss_scale)/d pred, loss_out: 1 float; work: >= 4104 bytes. */
 int jat_k_recon_loss(const float* pred, const float* target, float* dpred, float* loss_out, int64_t n, double eps,

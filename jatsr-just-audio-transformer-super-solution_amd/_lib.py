@@ -99,6 +99,7 @@ SIGNATURES = {
     "jat_k_small_dw": (C.c_int, [_VP, _I64, _VP, _I64, _VP, _VP] + [_I32] * 4 + [_VP]),
     "jat_k_small_dx": (C.c_int, [_VP, _I64, _VP, _I32, _VP] + [_I32] * 4 + [_VP, _VP, _SZ, _VP]),
     "jat_k_latent_loss": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I32, _I32] + [C.c_double] * 7 + [_F32, _VP, _SZ, _VP]),
+    "jat_k_latent_loss_plan": (C.c_int, [_I32, _VP, _VP, _VP, _VP]),
     "jat_trainer_create": (C.c_int, [_VP, C.POINTER(JatTensorRef), _I32, _VP, _VP, _VP, _VP, _I64, _I32, _I32, _VP,
                                      C.POINTER(_VP)]),
     "jat_trainer_destroy": (None, [_VP]),

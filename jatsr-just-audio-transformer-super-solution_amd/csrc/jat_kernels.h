@@ -202,6 +202,11 @@ hipError_t launch_charbonnier_grad(const float* pred, const float* target, float
 // v3mod2 loss (MSE + lw * (fw*freq + mw*ms + cw*cons)): dpred = d(loss * loss_scale)/d pred, out6 = {total, mse, freq, ms,
 // cons, fw*freq + mw*ms + cw*cons}; part: rows*8 floats; tw: [T] (cos, sin)(2 pi m / T); lr may be null when cw == 0.
 // low / strict / soft band edges (in rfft bins) are computed by the caller exactly as the reference does (int(F * ratio)).
+// The path launch_latent_loss takes at sequence length T (the one place that decides it): kind 0 = rejected (the direct LDS
+// image does not fit), 1 = direct DFT on latent_loss_kernel<a, b> = <FB, NB>, 2 = factored T = a * b = N1 * N2; lds = the
+// dynamic LDS bytes of that launch (kind 0: what the direct kernel would have needed).  Host arithmetic only.
+struct LatentLossPlan { int kind, a, b; size_t lds; };
+LatentLossPlan plan_latent_loss(int T);
 hipError_t launch_latent_loss(const float* pred, const float* target, const float* lr, const float2* tw, float* dpred,
                               float* part, float* out6, int rows, int T, float lw, float fw, float mw, float cw, int low,
                               int strict, int soft, float loss_scale, hipStream_t s);

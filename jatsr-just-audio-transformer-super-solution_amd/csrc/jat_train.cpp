@@ -764,12 +764,26 @@ extern "C" int jat_k_recon_loss(const float* pred, const float* target, float* d
   return JAT_OK;
 }
 
-// per-kernel entry point (unit parity): the v3mod2 loss on [rows, T] tensors; `work` holds T*8 + rows*32 bytes
+// which path launch_latent_loss takes at length T (csrc/train.hip plan_latent_loss); host only, launches nothing
+extern "C" int jat_k_latent_loss_plan(int32_t T, int32_t* kind, int32_t* a, int32_t* b, int64_t* lds_bytes) {
+  if (!kind || !a || !b || !lds_bytes || T <= 0) return fail(JAT_E_INVALID, "bad argument");
+  const LatentLossPlan pl = plan_latent_loss(T);
+  *kind = pl.kind; *a = pl.a; *b = pl.b; *lds_bytes = (int64_t)pl.lds;
+  return JAT_OK;
+}
+
+// per-kernel entry point (unit parity): the v3mod2 loss on [rows, T] tensors; `work` holds align_up(T*8, 256) + rows*32 bytes
 extern "C" int jat_k_latent_loss(const float* pred, const float* target, const float* lr, float* dpred, float* out6,
                                  int32_t rows, int32_t T, double latent_weight, double freq_weight, double ms_weight,
                                  double consistency_weight, double low_freq_phase_ratio, double strict_cutoff,
                                  double soft_cutoff, float loss_scale, void* work, size_t work_bytes, void* stream) {
   if (!pred || !target || !dpred || !out6 || !work || rows <= 0 || T <= 0) return fail(JAT_E_INVALID, "bad argument");
+  // what launch_latent_loss would reject, before anything is copied or launched
+  if (!(low_freq_phase_ratio >= 0 && low_freq_phase_ratio <= 1 && strict_cutoff >= 0 && soft_cutoff >= strict_cutoff &&
+        soft_cutoff <= 1))
+    return fail(JAT_E_INVALID, "band ratios must satisfy 0 <= strict <= soft <= 1 and 0 <= phase ratio <= 1");
+  if (plan_latent_loss(T).kind == 0)
+    return fail(JAT_E_INVALID, "T %d is too long for the loss kernels: their LDS image needs %zu bytes", T, plan_latent_loss(T).lds);
   const size_t need = align_up((size_t)T * sizeof(float2), 256) + (size_t)rows * 8 * 4;
   if (work_bytes < need) return fail(JAT_E_STATE, "work buffer too small: %zu < %zu bytes", work_bytes, need);
   hipStream_t s = (hipStream_t)stream;

@@ -1621,6 +1621,38 @@ __global__ void __launch_bounds__(256) latent_loss_finish_kernel(const float* __
     out[4] = (float)cons; out[5] = (float)lat;
   }
 }
+// Which code path launch_latent_loss takes for a sequence length, decided from T alone (host arithmetic; jat_k_latent_loss_plan
+// reports it).  Factored when T = N1 * N2 with N1 the largest divisor not above sqrt(T) and the factored LDS image fits;
+// else the direct DFT on the smallest (FB, NB) instance that covers F bins / T samples in one chunk, (3, 6) looping beyond
+// that; rejected when even the direct image does not fit.  JAT_LOSS_DIRECT_DFT=1 forces the direct kernel (A/B).
+LatentLossPlan plan_latent_loss(int T) {
+  LatentLossPlan pl{0, 0, 0, 0};
+  if (T <= 0) return pl;
+  const int F = T / 2 + 1;
+  const size_t lds_limit = 160 * 1024;
+  const size_t lds = (size_t)3 * T * 4 + ((size_t)T + F) * 8 + 32 * 4;
+  pl.lds = lds;
+  if (lds > lds_limit) return pl;
+  int N1 = 1;                       // largest divisor of T not above sqrt(T)
+  for (int d = 2; d * d <= T; ++d)
+    if (T % d == 0) N1 = d;
+  static const int direct_env = getenv("JAT_LOSS_DIRECT_DFT") ? atoi(getenv("JAT_LOSS_DIRECT_DFT")) : 0;   // A/B
+  if (N1 >= 2 && !direct_env) {
+    const int N2 = T / N1, N1h = N1 / 2 + 1;
+    const int ybuf = 3 * N1h * N2 > T ? 3 * N1h * N2 : T;
+    const size_t lds2 = (size_t)(3 * T) * 4 + (size_t)(T + F + ybuf) * 8 + 32 * 4;
+    if (lds2 <= lds_limit) {
+      pl.kind = 2; pl.a = N1; pl.b = N2; pl.lds = lds2;
+      return pl;
+    }
+  }
+  const int fb = (F + 255) / 256, nb = (T + 255) / 256;
+  pl.kind = 1;
+  if (fb <= 1 && nb <= 2) { pl.a = 1; pl.b = 2; }
+  else if (fb <= 2 && nb <= 4) { pl.a = 2; pl.b = 4; }
+  else { pl.a = 3; pl.b = 6; }
+  return pl;
+}
 hipError_t launch_latent_loss(const float* pred, const float* target, const float* lr, const float2* tw, float* dpred,
                               float* part, float* out6, int rows, int T, float lw, float fw, float mw, float cw, int low,
                               int strict, int soft, float loss_scale, hipStream_t s) {
@@ -1631,29 +1663,22 @@ hipError_t launch_latent_loss(const float* pred, const float* target, const floa
   if (low < 0 || low > a.F || strict < 0 || soft < strict || soft > a.F) return hipErrorInvalidValue;
   a.lw = lw; a.fw = fw; a.mw = mw; a.cw = cw; a.gscale = loss_scale;
   a.inv_n = 1.0f / ((float)rows * (float)T);
-  const size_t lds = (size_t)(3 * T) * 4 + (size_t)(T + a.F) * 8 + 32 * 4;
-  if (lds > 160 * 1024) return hipErrorInvalidValue;
-  int N1 = 1;                       // largest divisor of T not above sqrt(T)
-  for (int d = 2; d * d <= T; ++d)
-    if (T % d == 0) N1 = d;
-  static const int direct_env = getenv("JAT_LOSS_DIRECT_DFT") ? atoi(getenv("JAT_LOSS_DIRECT_DFT")) : 0;   // A/B
-  if (N1 >= 2 && !direct_env) {
-    const int N2 = T / N1, N1h = N1 / 2 + 1;
-    const int ybuf = 3 * N1h * N2 > T ? 3 * N1h * N2 : T;
-    const size_t lds2 = (size_t)(3 * T) * 4 + (size_t)(T + a.F + ybuf) * 8 + 32 * 4;
-    if (lds2 <= 160 * 1024) {
-      static size_t attr2 = 0;
-      if (lds2 > attr2) {
-        hipError_t e = hipFuncSetAttribute((const void*)latent_loss_fft_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
-        if (e != hipSuccess) return e;
-        attr2 = lds2;
-      }
-      hipLaunchKernelGGL(latent_loss_fft_kernel, dim3(rows), dim3(256), lds2, s, a, N1, N2);
-      hipLaunchKernelGGL(latent_loss_finish_kernel, dim3(1), dim3(256), 0, s, part, a, out6);
-      return hipGetLastError();
+  const LatentLossPlan pl = plan_latent_loss(T);
+  if (pl.kind == 0) return hipErrorInvalidValue;
+  if (pl.kind == 2) {
+    const int N1 = pl.a, N2 = pl.b;
+    const size_t lds2 = pl.lds;
+    static size_t attr2 = 0;
+    if (lds2 > attr2) {
+      hipError_t e = hipFuncSetAttribute((const void*)latent_loss_fft_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
+      if (e != hipSuccess) return e;
+      attr2 = lds2;
     }
+    hipLaunchKernelGGL(latent_loss_fft_kernel, dim3(rows), dim3(256), lds2, s, a, N1, N2);
+    hipLaunchKernelGGL(latent_loss_finish_kernel, dim3(1), dim3(256), 0, s, part, a, out6);
+    return hipGetLastError();
   }
-  const int fb = (a.F + 255) / 256, nb = (T + 255) / 256;
+  const size_t lds = pl.lds;
 #define LL_CASE(FBv, NBv)                                                                                              \
   {                                                                                                                    \
     static size_t attr_set = 0;                                                                                        \
@@ -1665,8 +1690,8 @@ hipError_t launch_latent_loss(const float* pred, const float* target, const floa
     }                                                                                                                  \
     hipLaunchKernelGGL((latent_loss_kernel<FBv, NBv>), dim3(rows), dim3(256), lds, s, a);                              \
   }
-  if (fb <= 1 && nb <= 2) LL_CASE(1, 2)
-  else if (fb <= 2 && nb <= 4) LL_CASE(2, 4)
+  if (pl.a == 1) LL_CASE(1, 2)
+  else if (pl.a == 2) LL_CASE(2, 4)
   else LL_CASE(3, 6)   // larger T: the kernel loops in chunks of 256 * FB bins / 256 * NB samples
 #undef LL_CASE
   hipLaunchKernelGGL(latent_loss_finish_kernel, dim3(1), dim3(256), 0, s, part, a, out6);

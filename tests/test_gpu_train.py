@@ -7,6 +7,7 @@ train_ddp_v3m2.py:545), accumulation and everything element-wise is fp32.  A gra
 relative error of order 2^-8 per bf16 rounding on its path; per-tensor rel-L2 against the fp64 reference is gated at
 GRAD_TOL, and the global quantities (loss, gradient norm) much tighter.
 """
+import ctypes
 import json
 import math
 
@@ -414,6 +415,52 @@ def test_train_step_vs_numpy_oracle(cfg_name, B, T, norm, salt):
         worst = max(worst, r / tol)
         assert r <= tol, f"{k}: {r:.3e}"
     print(f"{cfg_name} B={B} T={T} {norm}: loss {loss:.5f}, worst gradient at {worst:.2f} of tolerance")
+
+
+def test_latent_step_at_a_direct_dft_length_vs_numpy_oracle():
+    """The trainer with the latent perceptual loss at a PRIME length (T = 521: `launch_latent_loss` takes the direct DFT
+    kernel <2,4>, tests/test_loss_paths_cpu.py), on the trainer's own twiddle table, band edges and partial-sum buffer.
+    Loss terms vs the fp64 loss oracle evaluated at the HIP prediction (the same prediction on both sides, so the gate is the
+    loss kernel's 2e-5); gradients vs the fp64 oracle backward driven by the same d loss / d pred, as in
+    test_v3mod2_step_vs_reference_golden."""
+    from oracle import jat_oracle_train as OT
+    from oracle import latent_loss_oracle as LO
+    cfg_name, B, T, salt = "micro", 3, 521, 31
+    cfg = recipe.CONFIGS[cfg_name]
+    C = cfg["input_channels"]
+    kind, a, b, lds = (ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int64())
+    L.check(L.lib().jat_k_latent_loss_plan(T, ctypes.byref(kind), ctypes.byref(a), ctypes.byref(b), ctypes.byref(lds)))
+    assert (kind.value, a.value, b.value) == (1, 2, 4)
+    kw = dict(latent_weight=0.3, freq_weight=0.5, ms_weight=0.5, consistency_weight=0.1)
+    m, tr = make_trainer(dict(cfg=cfg_name, norm="ln", salt=salt, B=B, T=T, lr=5e-5, wd=0.1, clip=1.0), use_grad_scaler=False,
+                         condition_noise_ratio=0.0, latent_loss_weight=kw["latent_weight"], freq_loss_weight=kw["freq_weight"],
+                         ms_loss_weight=kw["ms_weight"], consistency_weight=kw["consistency_weight"])
+    hr = cuda(recipe.gaussian("train_hr", (B, C, T), salt + 300))
+    lr = cuda(recipe.gaussian("train_lr", (B, C, T), salt + 301))
+    noise = cuda(recipe.gaussian("train_noise", (B, C, T), salt + 302))
+    cn = cuda((0.05 * recipe.gaussian("train_cnoise", (B, C, T), salt + 303)).astype(np.float32))
+    t = cuda(np.linspace(0.1, 0.9, B).astype(np.float32))
+    z_t, t2, _ = tr.prepare(hr, lr, noise=noise, cfg_mask=torch.zeros(B, dtype=torch.bool), t=t)
+    cond_in = lr + cn
+    pred = tr.forward_backward(z_t, t2, cond_in, hr, cond_clean=lr, want_pred=True)
+    terms = tr.loss_terms()
+    ref_terms, dp_hip = LO.latent_loss(pred.cpu().numpy(), hr.cpu().numpy(), lr.cpu().numpy(), **kw)
+    err = {k: abs(terms[k] - ref_terms[k]) / abs(ref_terms[k]) for k in ref_terms}
+    print(f"micro ln B={B} T={T}: terms {terms}; relative to the oracle at the HIP prediction {err}")
+    for k, v in err.items():
+        assert v <= 2e-5, (k, terms[k], ref_terms[k])
+    orc = OT.TrainOracle(cfg, recipe.make_state_dict(cfg, "ln", salt), "ln")
+    orc.forward(z_t.cpu().numpy(), t2.cpu().numpy(), cond_in.cpu().numpy())
+    grads = orc.backward(dp_hip)
+    gn = math.sqrt(sum(float((g * g).sum()) for g in grads.values()))
+    worst = ("", 0.0)
+    for k, g in grads.items():
+        r = rel_l2((tr.grad(k) / tr.scaler.scale).cpu().numpy(), g)
+        tol = GRAD_TOL if np.linalg.norm(g) >= 1e-3 * gn else GRAD_TOL_SMALL
+        if r / tol > worst[1]:
+            worst = (k, r / tol)
+        assert r <= tol, f"{k}: grad rel-L2 {r:.3e}"
+    print(f"micro ln B={B} T={T}: worst tensor {worst[0]} at {worst[1]:.2f} of tolerance")
 
 
 @pytest.mark.parametrize("name", ["train_micro_drop_T24", "train_tiny_drop_T128"])
