@@ -229,6 +229,23 @@ int jat_trainer_prepare(jat_trainer* tr, const float* hr_norm, float* cond, cons
 int jat_trainer_fwd_bwd(jat_trainer* tr, const float* z_t, const float* t, const float* x_cond, const float* target,
                         const float* cond_clean, float loss_scale, uint64_t rng_seed, float* loss_out, float* x_pred_out,
                         void* stream);
+/* Gradient accumulation over the micro-batches of one optimiser step: jat_trainer_fwd_bwd with `flags` (0 = that call).
+ *   JAT_FB_ACCUMULATE: every kernel that writes a parameter gradient computes the fp32 value it would have stored and adds it
+ *     to the resident one, grads_flat = grads_flat + d(loss * loss_scale)/d(param): one rounded add per element, no atomics (a
+ *     step stays bit-reproducible), no extra buffer, no pass of its own over grads_flat.  loss_out and the six terms behind
+ *     jat_trainer_loss_terms add to their previous values as well: after k calls (the first without the flag) they hold the
+ *     sums over the k micro-batches, and the host divides by k after its one read-back.  The 1/k of the gradients rides on
+ *     jat_trainer_optim's un-scale factor: pass loss_scale * k there.  A trainer one of whose weight-gradient paths cannot
+ *     accumulate fails with JAT_E_STATE before anything is queued; nothing ever overwrites silently.
+ *   JAT_FB_NO_HOOK: the gradient-ready hook (jat_trainer_set_grad_hook) is not called: this is not the last micro-batch, so
+ *     an overlapped gradient exchange runs once per optimiser step, on the summed gradients.
+ * With the second (weight-gradient) stream, an accumulating call reads what the previous call's second stream wrote; every
+ * call, failed ones included, ends with that stream joined into `stream`.  Other flag bits: JAT_E_INVALID. */
+#define JAT_FB_ACCUMULATE 1   /* add d(loss*loss_scale)/d(param) to grads_flat instead of overwriting it */
+#define JAT_FB_NO_HOOK    2   /* do not call the gradient-ready hook: this is not the last micro-batch */
+int jat_trainer_fwd_bwd_ex(jat_trainer* tr, const float* z_t, const float* t, const float* x_cond, const float* target,
+                           const float* cond_clean, float loss_scale, uint64_t rng_seed, float* loss_out, float* x_pred_out,
+                           int32_t flags, void* stream);
 /* grads_flat is read, not modified (clip_grad_norm_'s in-place scaling of .grad is not reproduced: nothing reads it).
  * grad_norm_out (device, 1 float, nullable) = L2 norm of the loss-SCALED gradients (divide by loss_scale).  A
  * non-finite norm leaves parameters and moments untouched (GradScaler.step).  `step` is 1-based (bias correction). */
@@ -313,6 +330,11 @@ int jat_k_gemm_plan(const jat_model* m, int32_t site, int32_t M, int32_t N, int3
  * models/JaT_V3.py under train_ddp_v3m2.py:601.) */
 int jat_k_weight_grad(const uint16_t* dY, const uint16_t* X, float* dW, float* db, int32_t tokens, int32_t out, int32_t in,
                       int32_t ksplit, void* work, size_t work_bytes, void* stream);
+/* The same with the accumulate mode of JAT_FB_ACCUMULATE: accumulate != 0 adds the result to what dW (and db) hold, dW = dW +
+ * dY^T X — in the GEMM's epilogue when ksplit == 1, else in the ordered sum of the slices; bit for bit the overwrite result
+ * added to the old contents.  accumulate == 0 is jat_k_weight_grad. */
+int jat_k_weight_grad_ex(const uint16_t* dY, const uint16_t* X, float* dW, float* db, int32_t tokens, int32_t out, int32_t in,
+                         int32_t ksplit, void* work, size_t work_bytes, int32_t accumulate, void* stream);
 /* GQA attention on bf16 q[M,Hq*64], k[M,Hkv*64], vt[B,Hkv,64,Npad] -> o[M,Hq*64]; softmax(q k^T / 8) v. */
 int jat_k_attention(const uint16_t* q, const uint16_t* k, const uint16_t* vt, uint16_t* o, int32_t B,
                     int32_t N, int32_t Hq, int32_t Hkv, int32_t Npad, void* stream);

@@ -23,6 +23,7 @@ LIB_PATH = os.environ.get("JAT_LIB_PATH") or os.path.join(
 
 JAT_OK, JAT_E_INVALID, JAT_E_HIP, JAT_E_STATE, JAT_E_SEQLEN = 0, -1, -2, -3, -4
 NORM_RMS_W, NORM_LN_NOAFFINE = 0, 1
+FB_ACCUMULATE, FB_NO_HOOK = 1, 2   # JAT_FB_* flags of jat_trainer_fwd_bwd_ex
 
 
 class JatConfig(C.Structure):
@@ -83,6 +84,7 @@ SIGNATURES = {
     "jat_k_gemm_plan": (C.c_int, [_VP, _I32, _I32, _I32, _I32, _I32, _VP, _VP]),
     "jat_k_qkv_attn": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _VP, _VP, _I32, _VP]),
     "jat_k_weight_grad": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _VP, _SZ, _VP]),
+    "jat_k_weight_grad_ex": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _VP, _SZ, _I32, _VP]),
     "jat_k_attention": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP]),
     "jat_k_recon_loss": (C.c_int, [_VP, _VP, _VP, _VP, _I64, C.c_double, _F32, _VP, _SZ, _VP]),
     "jat_k_cast_bf16": (C.c_int, [_VP, _VP, _I64, _VP]),
@@ -112,6 +114,7 @@ SIGNATURES = {
     "jat_trainer_set_charbonnier": (C.c_int, [_VP, C.c_double]),
     "jat_trainer_loss_terms": (C.c_int, [_VP, _VP, _VP]),
     "jat_trainer_fwd_bwd": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _F32, C.c_uint64, _VP, _VP, _VP]),
+    "jat_trainer_fwd_bwd_ex": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _F32, C.c_uint64, _VP, _VP, _I32, _VP]),
     "jat_trainer_optim": (C.c_int, [_VP, _F32, _F32, _F32, _F32, _F32, _F32, _F32, _I32, _VP, _VP]),
     "jat_trainer_set_ema": (C.c_int, [_VP, _VP, _F32]),
     "jat_trainer_swap_ema": (C.c_int, [_VP, _VP]),

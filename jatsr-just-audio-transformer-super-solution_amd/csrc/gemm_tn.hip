@@ -49,6 +49,14 @@ constexpr int TBM = 128, TBN = 128, TBK = 64;
 constexpr int IMG = TBK * 256;     // one operand image: 64 token rows x 256 B
 constexpr int STAGE = 2 * IMG;     // dY image, then X image
 
+// Accumulate mode of the epilogues (gradient accumulation over micro-batches): dst = dst + v, the resident value first, one
+// rounded fp32 add per element that never contracts into an FMA with whatever produced v.
+__device__ __forceinline__ void add_into(f32x4* dst, const f32x4 v) {
+#pragma clang fp contract(off)
+  const f32x4 old = *dst;
+  *dst = f32x4{old[0] + v[0], old[1] + v[1], old[2] + v[2], old[3] + v[3]};
+}
+
 __device__ __forceinline__ opx8 tr_pair(const unsigned char* img, int off_lo, int off_hi) {
   const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(img + off_lo));
   const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(img + off_hi));
@@ -57,6 +65,9 @@ __device__ __forceinline__ opx8 tr_pair(const unsigned char* img, int off_lo, in
 }
 }  // namespace
 
+// ACC: the epilogue adds the tile into dW instead of overwriting it (direct-store launches only, ksplit == 1; split-K launches
+// write partial slices and sum_partials_kernel<true> does the add).  ACC = false is the kernel as it always was.
+template <bool ACC>
 __global__ void __launch_bounds__(256, 2) gemm_tn_kernel(GemmTnArgs p) {
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem_tn[];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -193,7 +204,8 @@ __global__ void __launch_bounds__(256, 2) gemm_tn_kernel(GemmTnArgs p) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int n = n0 + wn * 64 + j * 16 + 4 * fg;
-      *(f32x4*)(out + (int64_t)o * p.ldo + n) = acc[i][j];
+      if constexpr (ACC) add_into((f32x4*)(out + (int64_t)o * p.ldo + n), acc[i][j]);
+      else *(f32x4*)(out + (int64_t)o * p.ldo + n) = acc[i][j];
     }
   }
 }
@@ -221,6 +233,7 @@ constexpr int NPIECE = STAGE2 / 1024, HPIECE = NPIECE / 2, PPH = (HPIECE + 7) / 
 static_assert(IMG2 % 2048 == 0, "no DMA piece may straddle the two operand images");
 }  // namespace tn256
 
+template <bool ACC>
 __global__ void __launch_bounds__(512, 1) gemm_tn256_kernel(GemmTnArgs p) {
   using namespace tn256;
   extern __shared__ __attribute__((aligned(1024))) unsigned char smem_tn[];
@@ -360,7 +373,8 @@ __global__ void __launch_bounds__(512, 1) gemm_tn256_kernel(GemmTnArgs p) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int n = n0 + wn * 64 + j * 16 + 4 * fg;
-      *(f32x4*)(out + (int64_t)o * p.ldo + n) = acc[i][j];
+      if constexpr (ACC) add_into((f32x4*)(out + (int64_t)o * p.ldo + n), acc[i][j]);
+      else *(f32x4*)(out + (int64_t)o * p.ldo + n) = acc[i][j];
     }
   }
 }
@@ -377,13 +391,16 @@ int gemm_tn_ksplit(int M, int N, int K) {
 }
 
 hipError_t launch_gemm_tn(const bf16_t* dY, int64_t ldy, const bf16_t* X, int64_t ldx, float* dW, int64_t ldo, int M, int N, int K,
-                          int ksplit, int64_t split_stride, const void* zeros, hipStream_t s) {
+                          int ksplit, int64_t split_stride, const void* zeros, int accumulate, hipStream_t s) {
   if (!gemm_tn_supports(M, N) || K <= 0 || ldy % 8 != 0 || ldx % 8 != 0 || ldo % 4 != 0) return hipErrorInvalidValue;
   if (ksplit < 1 || ksplit > (K + TBK - 1) / TBK) return hipErrorInvalidValue;
+  if (accumulate && ksplit > 1) return hipErrorInvalidValue;   // partial slices are overwritten; their sum is what accumulates
   static bool attr_set = false;
   if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)gemm_tn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE);
-    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm_tn256_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * tn256::STAGE2);
+    hipError_t e = hipFuncSetAttribute((const void*)gemm_tn_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm_tn256_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * tn256::STAGE2);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm_tn_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void*)gemm_tn256_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * tn256::STAGE2);
     if (e != hipSuccess) return e;
     attr_set = true;
   }
@@ -392,10 +409,14 @@ hipError_t launch_gemm_tn(const bf16_t* dY, int64_t ldy, const bf16_t* X, int64_
   a.ksplit = ksplit; a.split_stride = split_stride; a.zeros = zeros;
   static const int force = getenv("JAT_TN_TILE") ? atoi(getenv("JAT_TN_TILE")) : 0;   // 128 / 256: tests and tools
   const bool big = M % 256 == 0 && N % 256 == 0 && zeros && (force ? force == 256 : (int64_t)M * N >= 1024 * 1024);
-  if (big)
-    hipLaunchKernelGGL(gemm_tn256_kernel, dim3((M / 256) * (N / 256), ksplit), dim3(512), 2 * tn256::STAGE2, s, a);
+  if (big && accumulate)
+    hipLaunchKernelGGL(gemm_tn256_kernel<true>, dim3((M / 256) * (N / 256), ksplit), dim3(512), 2 * tn256::STAGE2, s, a);
+  else if (big)
+    hipLaunchKernelGGL(gemm_tn256_kernel<false>, dim3((M / 256) * (N / 256), ksplit), dim3(512), 2 * tn256::STAGE2, s, a);
+  else if (accumulate)
+    hipLaunchKernelGGL(gemm_tn_kernel<true>, dim3((M / TBM) * (N / TBN), ksplit), dim3(256), 2 * STAGE, s, a);
   else
-    hipLaunchKernelGGL(gemm_tn_kernel, dim3((M / TBM) * (N / TBN), ksplit), dim3(256), 2 * STAGE, s, a);
+    hipLaunchKernelGGL(gemm_tn_kernel<false>, dim3((M / TBM) * (N / TBN), ksplit), dim3(256), 2 * STAGE, s, a);
   return hipGetLastError();
 }
 
@@ -425,19 +446,21 @@ __global__ void __launch_bounds__(256) colsum_bf16_kernel(const bf16_t* __restri
     part[(int64_t)blockIdx.y * C + blockIdx.x * 128 + threadIdx.x] = s;
   }
 }
+template <bool ACC>   // ACC: out[c] = out[c] + (sum of the slices), the slices summed first
 __global__ void __launch_bounds__(256) colsum_finish_kernel(const float* __restrict__ part, int nslice, int C, float* __restrict__ out) {
   const int c = blockIdx.x * 256 + threadIdx.x;
   if (c >= C) return;
   float s = 0.f;
   for (int k = 0; k < nslice; ++k) s += part[(int64_t)k * C + c];
-  out[c] = s;
+  out[c] = ACC ? out[c] + s : s;
 }
 int colsum_slices(int R) { return R >= 2048 ? 32 : (R >= 256 ? 8 : 1); }
 // part: colsum_slices(R) * C floats of scratch
-hipError_t launch_colsum_bf16(const bf16_t* x, int64_t ld, int R, int C, float* part, float* out, hipStream_t s) {
+hipError_t launch_colsum_bf16(const bf16_t* x, int64_t ld, int R, int C, float* part, float* out, int accumulate, hipStream_t s) {
   if (C % 128 != 0 || ld % 8 != 0 || R <= 0) return hipErrorInvalidValue;
   const int ns = colsum_slices(R);
   hipLaunchKernelGGL(colsum_bf16_kernel, dim3(C / 128, ns), dim3(256), 0, s, x, ld, R, part, C);
-  hipLaunchKernelGGL(colsum_finish_kernel, dim3((C + 255) / 256), dim3(256), 0, s, part, ns, C, out);
+  if (accumulate) hipLaunchKernelGGL(colsum_finish_kernel<true>, dim3((C + 255) / 256), dim3(256), 0, s, part, ns, C, out);
+  else hipLaunchKernelGGL(colsum_finish_kernel<false>, dim3((C + 255) / 256), dim3(256), 0, s, part, ns, C, out);
   return hipGetLastError();
 }

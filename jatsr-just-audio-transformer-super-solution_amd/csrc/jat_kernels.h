@@ -165,19 +165,23 @@ hipError_t launch_crossfade_pair(const float* prev, int Tp, const float* cur, in
                                  float* out, int rows, hipStream_t s);
 
 // ---- training step (train.hip): backward, loss, optimiser, data preparation -------------------------------------------
-hipError_t launch_sum_partials(const float* part, int nsplit, int64_t stride, float* out, int64_t n, hipStream_t s);
+// `accumulate` / `dw_accumulate` of the gradient writers below (gradient accumulation over micro-batches): the launch computes the
+// fp32 value it would store and adds it to the resident one, G = G_old + g, one rounded add per element, no atomics; 0 launches
+// the kernel as it is without the mode (a separate instantiation, not a run-time branch).
+hipError_t launch_sum_partials(const float* part, int nsplit, int64_t stride, float* out, int64_t n, int accumulate, hipStream_t s);
 hipError_t launch_transpose_bf16(const bf16_t* in, int64_t ld_in, int M, int C, bf16_t* out, int Mpad, hipStream_t s);
-hipError_t launch_rowsum_bf16(const bf16_t* x, int64_t ld, int R, int n, float* out, hipStream_t s);
+hipError_t launch_rowsum_bf16(const bf16_t* x, int64_t ld, int R, int n, float* out, int accumulate, hipStream_t s);
 // gemm_tn.hip: dW[M,N] fp32 = dY[K,M]^T X[K,N] straight from the token-major operands (no transposed copies), optional
 // split-K partial slices; column sums of a token-major matrix (bias gradients) with colsum_slices(R) * C floats of scratch
 bool gemm_tn_supports(int M, int N);
 // zeros: >= 16 zero bytes of device memory (needed by the 256 x 256 form; nullptr keeps the 128 x 128 kernel);
-// gemm_tn_ksplit: the slice count that fills the chip for this shape
+// gemm_tn_ksplit: the slice count that fills the chip for this shape; accumulate: ksplit == 1 only (partial slices are always
+// overwritten: launch_sum_partials adds their sum)
 int gemm_tn_ksplit(int M, int N, int K);
 hipError_t launch_gemm_tn(const bf16_t* dY, int64_t ldy, const bf16_t* X, int64_t ldx, float* dW, int64_t ldo, int M, int N, int K,
-                          int ksplit, int64_t split_stride, const void* zeros, hipStream_t s);
+                          int ksplit, int64_t split_stride, const void* zeros, int accumulate, hipStream_t s);
 int colsum_slices(int R);
-hipError_t launch_colsum_bf16(const bf16_t* x, int64_t ld, int R, int C, float* part, float* out, hipStream_t s);
+hipError_t launch_colsum_bf16(const bf16_t* x, int64_t ld, int R, int C, float* part, float* out, int accumulate, hipStream_t s);
 hipError_t launch_gelu_bf16(const bf16_t* in, bf16_t* out, int64_t n, DropSpec drop, hipStream_t s);
 hipError_t launch_gelu_bwd(const bf16_t* pre, bf16_t* d, int64_t n, DropSpec drop, hipStream_t s);
 hipError_t launch_resid_gate(const float* x_in, const bf16_t* y, const float* gate, int64_t gate_bstride, float* x_out,
@@ -189,7 +193,7 @@ hipError_t launch_gate_bwd(const float* dx, const bf16_t* y, const float* gate, 
                            DropSpec elem, hipStream_t s);
 hipError_t launch_norm_bwd(const float* x, const bf16_t* dy, const float* w, const float* scale, int64_t mod_bstride,
                            float* dx, int accumulate, float* part, float* dw_part, float* dshift, float* dscale,
-                           int64_t dmod_bstride, float* dw, int B, int D, int ntok, int mode, hipStream_t s);
+                           int64_t dmod_bstride, float* dw, int dw_accumulate, int B, int D, int ntok, int mode, hipStream_t s);
 hipError_t launch_attention_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* vt, const bf16_t* o, const bf16_t* dout,
                                 const float* lse, float* delta, bf16_t* dqkv, const float* rope_cos, const float* rope_sin,
                                 int B, int N, int Hq, int Hkv, int npad, DropSpec drop, float* dkv_part, hipStream_t s);
@@ -216,7 +220,7 @@ hipError_t launch_adamw(float* p, float* g, float* m, float* v, int64_t n, const
                         float ema_decay, hipStream_t s);   // ema != nullptr: also ema += (1 - ema_decay) * (p_new - ema), same pass
 hipError_t launch_swap_f32(float* a, float* b, int64_t n, hipStream_t s);   // a <-> b in place, n % 4 == 0
 hipError_t launch_small_dw(const float* dy, int64_t ldy, const float* x, int64_t ldx, float* dW, float* db, int B, int N,
-                           int K, int silu_x, hipStream_t s);
+                           int K, int silu_x, int accumulate, hipStream_t s);
 int small_dx_slab(int N);   // rows of W per partial-sum slab
 hipError_t launch_small_dx(const float* dy, int64_t ldy, const void* W, int w_is_bf16, float* part, float* dx, int B, int N,
                            int K, int accumulate, const float* silu_pre, hipStream_t s);
@@ -224,7 +228,11 @@ hipError_t launch_small_dx(const float* dy, int64_t ldy, const void* W, int w_is
 struct CopyJob { const float* src; float* dst; int64_t n; };
 hipError_t launch_multi_copy(const CopyJob* jobs_dev, int njobs, hipStream_t s);
 hipError_t launch_silu_f32(const float* in, float* out, int64_t n, hipStream_t s);
-hipError_t launch_unpack_qkv_grad(const float* fused, float* gq, float* gk, float* gv, int D, int kvD, int K, hipStream_t s);
+hipError_t launch_unpack_qkv_grad(const float* fused, float* gq, float* gk, float* gv, int D, int kvD, int K, int accumulate,
+                                  hipStream_t s);
+// the loss cells over the micro-batches of one optimiser step: phase 0 keeps them aside before the loss kernels overwrite them,
+// phase 1 adds the kept values back in (terms / terms_keep: the six terms of the latent loss, or nullptr)
+hipError_t launch_loss_carry(float* loss, float* loss_keep, float* terms, float* terms_keep, int phase, hipStream_t s);
 hipError_t launch_flow_mix(const float* x, const float* noise, const float* t, float* z, int B, int64_t per_sample, hipStream_t s);
 hipError_t launch_cond_augment(float* cond, const float* noise, const float* std2, float ratio, const float* keep, int B,
                                int64_t per_sample, hipStream_t s);

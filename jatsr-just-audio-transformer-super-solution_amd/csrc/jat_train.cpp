@@ -83,6 +83,10 @@ struct jat_trainer {
   hipEvent_t ev_ready[4][2] = {}, ev_done[4][2] = {}, ev_mod[2] = {}, ev_join = nullptr, ev_wt = nullptr;
   std::vector<hipEvent_t> ev_layer;    // block l's weight gradients are complete (gates the gradient-ready hook)
   bf16_t *dy_m[2] = {}, *dh_b[2] = {}, *dy_a[2] = {}, *dq_b[2] = {};
+  // the call in flight (jat_trainer_fwd_bwd_ex flags): accum: every writer of grads_flat, and the loss cells, add to what is there;
+  // no_hook: the gradient-ready hook stays silent (not the last micro-batch of the optimiser step)
+  bool accum = false, no_hook = false;
+  int64_t dw_split_floats = 0;         // capacity of dw_split
 };
 
 namespace {
@@ -140,31 +144,54 @@ int repack(jat_trainer* tr, hipStream_t s) {
   return build_transposes(tr, s);
 }
 
-// dW[out,in] = dY^T X and (optionally) db[out] = column sums of dY, from dY bf16 [M,out] and X bf16 [M,in]
-int weight_grad(jat_trainer* tr, const bf16_t* dY, int out, const bf16_t* X, int in, float* dW, float* db, hipStream_t s) {
+// dW[out,in] = dY^T X and (optionally) db[out] = column sums of dY, from dY bf16 [M,out] and X bf16 [M,in]; acc: added into
+// dW / db (G = G_old + g) instead of overwriting them
+int weight_grad(jat_trainer* tr, const bf16_t* dY, int out, const bf16_t* X, int in, float* dW, float* db, bool acc, hipStream_t s) {
   // M x N tiles of a small weight do not fill 256 CUs while K = all tokens is long: split K, sum the partials in order
   const int64_t area = (int64_t)out * in;
   const int split = area <= tr->split4_area ? 4 : (area <= tr->split2_area ? 2 : 1);
   if (tr->tn_dw && gemm_tn_supports(out, in)) {   // straight from the token-major operands (gemm_tn.hip)
     const int ks = gemm_tn_ksplit(out, in, tr->M);
-    KCHK(launch_gemm_tn(dY, out, X, in, ks > 1 ? tr->dw_split : dW, in, out, in, tr->M, ks, area, tr->zero_cell, s));
-    if (ks > 1) KCHK(launch_sum_partials(tr->dw_split, ks, area, dW, area, s));
-    if (db) KCHK(launch_colsum_bf16(dY, out, tr->M, out, tr->colsum_part, db, s));
+    // one slice: the add happens in the GEMM's epilogue; several: the slices are overwritten, their ordered sum is added
+    KCHK(launch_gemm_tn(dY, out, X, in, ks > 1 ? tr->dw_split : dW, in, out, in, tr->M, ks, area, tr->zero_cell, acc && ks == 1, s));
+    if (ks > 1) KCHK(launch_sum_partials(tr->dw_split, ks, area, dW, area, acc, s));
+    if (db) KCHK(launch_colsum_bf16(dY, out, tr->M, out, tr->colsum_part, db, acc, s));
     return JAT_OK;
   }
   KCHK(launch_transpose_bf16(dY, out, tr->M, out, tr->tA, tr->Mpad, s));
   KCHK(launch_transpose_bf16(X, in, tr->M, in, tr->tB, tr->Mpad, s));
   GemmArgs e{};
   e.ldo = in; e.ntok = out;
-  if (split > 1) {
-    e.out = tr->dw_split; e.ksplit = split; e.split_stride = area;
+  if (split > 1 || acc) {   // acc: gemm.hip's fp32 epilogue only overwrites, so an unsplit product goes through the scratch as well
+    if ((int64_t)split * area > tr->dw_split_floats)
+      return fail(JAT_E_STATE, "weight gradient [%d, %d] cannot accumulate: %d slice(s) do not fit the split scratch", out, in, split);
+    e.out = tr->dw_split;
+    if (split > 1) { e.ksplit = split; e.split_stride = area; }
     JCHK(jat_gemm(tr->m, G_OTHER, tr->tA, tr->Mpad, tr->tB, tr->Mpad, out, in, tr->Mpad, EPI_F32, e, s));
-    KCHK(launch_sum_partials(tr->dw_split, split, area, dW, area, s));
+    KCHK(launch_sum_partials(tr->dw_split, split, area, dW, area, acc, s));
   } else {
     e.out = dW;
     JCHK(jat_gemm(tr->m, G_OTHER, tr->tA, tr->Mpad, tr->tB, tr->Mpad, out, in, tr->Mpad, EPI_F32, e, s));
   }
-  if (db) KCHK(launch_rowsum_bf16(tr->tA, tr->Mpad, out, tr->Mpad, db, s));
+  if (db) KCHK(launch_rowsum_bf16(tr->tA, tr->Mpad, out, tr->Mpad, db, acc, s));
+  return JAT_OK;
+}
+
+// Can every weight-gradient site of this trainer add into grads_flat?  The only one that may not is the transposed-copy path of
+// weight_grad, whose product has to fit the split scratch.  JAT_E_STATE, never a silent overwrite.
+int accumulate_supported(const jat_trainer* tr) {
+  const jat_model* m = tr->m;
+  const int D = m->D;
+  const int shapes[][2] = {{m->Fout, D}, {D, m->mlp}, {m->mlp, D}, {D, D}, {D, m->bott}, {m->bott, m->Kp}};   // QKV goes to its own scratch
+  for (auto& sh : shapes) {
+    if (tr->tn_dw && gemm_tn_supports(sh[0], sh[1])) continue;
+    const int64_t area = (int64_t)sh[0] * sh[1];
+    const int split = area <= tr->split4_area ? 4 : (area <= tr->split2_area ? 2 : 1);
+    if (split * area > tr->dw_split_floats)
+      return fail(JAT_E_STATE, "JAT_FB_ACCUMULATE: the weight gradient [%d, %d] takes the transposed-copy path and its %d slice(s) do "
+                  "not fit the split scratch (%lld floats): this trainer cannot accumulate", sh[0], sh[1], split,
+                  (long long)tr->dw_split_floats);
+  }
   return JAT_OK;
 }
 
@@ -258,6 +285,10 @@ int backward_train(jat_trainer* tr, const float* target, const float* cond_clean
   const int B = tr->B, T = tr->T, ntok = tr->ntok, M = tr->M, D = m->D, Nqkv = D + 2 * m->kvD, mode = m->cfg.norm_mode;
   const int64_t mstride = (int64_t)m->depth * 6 * D;
   float* G = tr->G;
+  const bool acc = tr->accum;
+  // the loss cells add up as the gradients do: kept aside here, added back in behind the loss kernels
+  float *terms = tr->lw != 0.0 ? tr->terms : nullptr, *terms_keep = tr->lw != 0.0 ? tr->terms + 8 : nullptr;
+  if (acc) KCHK(launch_loss_carry(tr->scal, tr->scal + 12, terms, terms_keep, 0, s));
   if (tr->lw != 0.0) {
     const int F = T / 2 + 1;   // band edges exactly as the reference computes them: int(freq_bins * ratio) in double
     KCHK(launch_latent_loss(tr->pred, target, cond_clean, tr->tw, tr->dpred, tr->ll_part, tr->terms, B * m->Cin, T,
@@ -270,6 +301,7 @@ int backward_train(jat_trainer* tr, const float* target, const float* cond_clean
   } else {
     KCHK(launch_mse_grad(tr->pred, target, tr->dpred, tr->red_part, tr->scal, (int64_t)B * m->Cin * T, loss_scale, s));
   }
+  if (acc) KCHK(launch_loss_carry(tr->scal, tr->scal + 12, terms, terms_keep, 1, s));
   // Where a weight gradient runs: on `s` itself, or (dw_async) on the second stream behind an event of the kernel that
   // finished its gradient operand; `done` is what the next writer of that operand buffer waits for.
   hipStream_t ws = tr->dw_async ? tr->dw_stream : s;
@@ -287,95 +319,104 @@ int backward_train(jat_trainer* tr, const float* target, const float* cond_clean
     if (tr->dw_async) HIPCHK(hipStreamWaitEvent(s, done, 0));
     return JAT_OK;
   };
-  // final layer: Linear (unpatchify^T is a patchify of dpred) and the un-modulated norm
-  KCHK(launch_patchify(tr->dpred, nullptr, tr->dyf, B, B, B, m->Cin, 0, T, ntok, s));
-  if (tr->dw_async) HIPCHK(hipStreamWaitEvent(s, tr->ev_wt, 0));   // the transposed weight copies of the last re-pack (repack())
-  JCHK(input_grad(tr, tr->dyf, m->Fout, tr->wfinalT, D, tr->dxn, s));
-  if (tr->dw_async) { HIPCHK(hipEventRecord(tr->ev_join, s)); HIPCHK(hipStreamWaitEvent(ws, tr->ev_join, 0)); }
-  JCHK(weight_grad(tr, tr->dyf, m->Fout, tr->xnf, D, G + tr->o_wf, G + tr->o_bf, ws));
-  if (tr->dw_async) HIPCHK(hipEventRecord(tr->ev_layer[m->depth], ws));
-  KCHK(launch_norm_bwd(tr->x[m->depth], tr->dxn, m->final_norm, nullptr, 0, tr->dx, 0, tr->part, tr->dw_part, nullptr, nullptr, 0,
-                       tr->rms ? G + tr->o_fn : nullptr, B, D, ntok, mode, s));
   // gradient-ready hook of a block: with the second stream its weight gradients may still be in flight when the chain moves on,
   // so the hook of block l fires one block later, behind an event of the dW stream (the exchange stream orders itself after `s`)
   int pending_hook = -1;
   auto fire_hook = [&](int blk) -> int {
-    if (!tr->hook) return JAT_OK;
+    if (!tr->hook || tr->no_hook) return JAT_OK;
     if (tr->dw_async) HIPCHK(hipStreamWaitEvent(s, tr->ev_layer[blk], 0));
     tr->hook(tr->block_lo[blk], (blk == m->depth ? tr->total : tr->block_lo[blk + 1]) - tr->block_lo[blk], tr->hook_user);
     return JAT_OK;
   };
-  if (tr->dw_async) pending_hook = m->depth; else JCHK(fire_hook(m->depth));
-  for (int l = m->depth - 1; l >= 0; --l) {
-    TLayer& L = tr->L[l];
-    const int par = l & 1;
-    bf16_t *dy_m = tr->dy_m[par], *dh = tr->dh_b[par], *dy_a = tr->dy_a[par], *dq = tr->dq_b[par];
-    const float* mod = tr->mod + (int64_t)l * 6 * D;
-    float* dmod = tr->dmod + (int64_t)l * 6 * D;
-    // x_out = x_mid + gate_mlp * mlp(norm2(x_mid) * (1 + scale_mlp) + shift_mlp)          jat_audiosr_v3.py:303-306
-    JCHK(before_write(tr->ev_done[0][par]));
-    KCHK(launch_gate_bwd(tr->dx, L.y_mlp, mod + 5 * D, mstride, dy_m, tr->part, dmod + 5 * D, mstride, B, D, ntok,
-                         site(tr, l, 4), site(tr, l, 3), s));
-    JCHK(before_write(tr->ev_done[1][par]));
-    JCHK(input_grad(tr, dy_m, D, L.w2T, m->mlp, dh, s));
-    JCHK(dw_begin(tr->ev_ready[0][par]));
-    JCHK(weight_grad(tr, dy_m, D, L.h_post, m->mlp, G + L.o_w2, G + L.o_b2, ws));
-    JCHK(dw_end(tr->ev_done[0][par]));
-    KCHK(launch_gelu_bwd(L.h_pre, dh, (int64_t)M * m->mlp, site(tr, l, 2), s));
-    JCHK(input_grad(tr, dh, m->mlp, L.w1T, D, tr->dxn, s));
-    JCHK(dw_begin(tr->ev_ready[1][par]));
-    JCHK(weight_grad(tr, dh, m->mlp, L.xn2, D, G + L.o_w1, G + L.o_b1, ws));
-    JCHK(dw_end(tr->ev_done[1][par]));
-    KCHK(launch_norm_bwd(L.x_mid, tr->dxn, m->layers[l].norm2, mod + 4 * D, mstride, tr->dx, 1, tr->part, tr->dw_part, dmod + 3 * D,
-                         dmod + 4 * D, mstride, tr->rms ? G + L.o_n2 : nullptr, B, D, ntok, mode, s));
-    // x_mid = x_in + gate_msa * out_proj(attn(norm1(x_in) * (1 + scale_msa) + shift_msa))   :297-300
-    JCHK(before_write(tr->ev_done[2][par]));
-    KCHK(launch_gate_bwd(tr->dx, L.y_attn, mod + 2 * D, mstride, dy_a, tr->part, dmod + 2 * D, mstride, B, D, ntok,
-                         site(tr, l, 1), kNoDrop, s));
-    JCHK(input_grad(tr, dy_a, D, L.woT, D, tr->dao, s));
-    JCHK(dw_begin(tr->ev_ready[2][par]));
-    JCHK(weight_grad(tr, dy_a, D, L.ao, D, G + L.o_o, nullptr, ws));
-    JCHK(dw_end(tr->ev_done[2][par]));
-    JCHK(before_write(tr->ev_done[3][par]));
-    KCHK(launch_attention_bwd(L.q, L.k, L.vt, L.ao, tr->dao, L.lse, tr->delta, dq, m->rope_cos, m->rope_sin, B, ntok,
-                              m->Hq, m->Hkv, tr->npad, site(tr, l, 0), tr->dkv_part, s));
-    JCHK(input_grad(tr, dq, Nqkv, L.wqkvT, D, tr->dxn, s));
-    JCHK(dw_begin(tr->ev_ready[3][par]));
-    JCHK(weight_grad(tr, dq, Nqkv, L.xn1, D, tr->dwqkv, nullptr, ws));
-    KCHK(launch_unpack_qkv_grad(tr->dwqkv, G + L.o_q, G + L.o_k, G + L.o_v, D, m->kvD, D, ws));
-    JCHK(dw_end(tr->ev_done[3][par]));
-    KCHK(launch_norm_bwd(tr->x[l], tr->dxn, m->layers[l].norm1, mod + 1 * D, mstride, tr->dx, 1, tr->part, tr->dw_part, dmod + 0 * D,
-                         dmod + 1 * D, mstride, tr->rms ? G + L.o_n1 : nullptr, B, D, ntok, mode, s));
-    // adaLN modulation Linear(SiLU(t_emb)) of this block (:275-278): its six dmod slices are complete now (a weight gradient
-    // like the others: nothing in the chain reads it)
-    JCHK(dw_begin(tr->ev_mod[par]));
-    KCHK(launch_small_dw(dmod, mstride, tr->t_emb, D, G + L.o_ada_w, G + L.o_ada_b, B, 6 * D, D, 1, ws));
-    if (tr->dw_async) HIPCHK(hipEventRecord(tr->ev_layer[l], ws));
-    if (tr->dw_async) {
-      if (pending_hook >= 0) JCHK(fire_hook(pending_hook));
-      pending_hook = l;
-    } else {
-      JCHK(fire_hook(l));
+  // everything that queues work on the second stream, so that a failure in the middle still reaches the join below
+  auto chain = [&]() -> int {
+    // final layer: Linear (unpatchify^T is a patchify of dpred) and the un-modulated norm
+    KCHK(launch_patchify(tr->dpred, nullptr, tr->dyf, B, B, B, m->Cin, 0, T, ntok, s));
+    if (tr->dw_async) HIPCHK(hipStreamWaitEvent(s, tr->ev_wt, 0));   // the transposed weight copies of the last re-pack (repack())
+    JCHK(input_grad(tr, tr->dyf, m->Fout, tr->wfinalT, D, tr->dxn, s));
+    if (tr->dw_async) { HIPCHK(hipEventRecord(tr->ev_join, s)); HIPCHK(hipStreamWaitEvent(ws, tr->ev_join, 0)); }
+    JCHK(weight_grad(tr, tr->dyf, m->Fout, tr->xnf, D, G + tr->o_wf, G + tr->o_bf, acc, ws));
+    if (tr->dw_async) HIPCHK(hipEventRecord(tr->ev_layer[m->depth], ws));
+    KCHK(launch_norm_bwd(tr->x[m->depth], tr->dxn, m->final_norm, nullptr, 0, tr->dx, 0, tr->part, tr->dw_part, nullptr, nullptr, 0,
+                         tr->rms ? G + tr->o_fn : nullptr, acc, B, D, ntok, mode, s));
+    if (tr->dw_async) pending_hook = m->depth; else JCHK(fire_hook(m->depth));
+    for (int l = m->depth - 1; l >= 0; --l) {
+      TLayer& L = tr->L[l];
+      const int par = l & 1;
+      bf16_t *dy_m = tr->dy_m[par], *dh = tr->dh_b[par], *dy_a = tr->dy_a[par], *dq = tr->dq_b[par];
+      const float* mod = tr->mod + (int64_t)l * 6 * D;
+      float* dmod = tr->dmod + (int64_t)l * 6 * D;
+      // x_out = x_mid + gate_mlp * mlp(norm2(x_mid) * (1 + scale_mlp) + shift_mlp)          jat_audiosr_v3.py:303-306
+      JCHK(before_write(tr->ev_done[0][par]));
+      KCHK(launch_gate_bwd(tr->dx, L.y_mlp, mod + 5 * D, mstride, dy_m, tr->part, dmod + 5 * D, mstride, B, D, ntok,
+                           site(tr, l, 4), site(tr, l, 3), s));
+      JCHK(before_write(tr->ev_done[1][par]));
+      JCHK(input_grad(tr, dy_m, D, L.w2T, m->mlp, dh, s));
+      JCHK(dw_begin(tr->ev_ready[0][par]));
+      JCHK(weight_grad(tr, dy_m, D, L.h_post, m->mlp, G + L.o_w2, G + L.o_b2, acc, ws));
+      JCHK(dw_end(tr->ev_done[0][par]));
+      KCHK(launch_gelu_bwd(L.h_pre, dh, (int64_t)M * m->mlp, site(tr, l, 2), s));
+      JCHK(input_grad(tr, dh, m->mlp, L.w1T, D, tr->dxn, s));
+      JCHK(dw_begin(tr->ev_ready[1][par]));
+      JCHK(weight_grad(tr, dh, m->mlp, L.xn2, D, G + L.o_w1, G + L.o_b1, acc, ws));
+      JCHK(dw_end(tr->ev_done[1][par]));
+      KCHK(launch_norm_bwd(L.x_mid, tr->dxn, m->layers[l].norm2, mod + 4 * D, mstride, tr->dx, 1, tr->part, tr->dw_part, dmod + 3 * D,
+                           dmod + 4 * D, mstride, tr->rms ? G + L.o_n2 : nullptr, acc, B, D, ntok, mode, s));
+      // x_mid = x_in + gate_msa * out_proj(attn(norm1(x_in) * (1 + scale_msa) + shift_msa))   :297-300
+      JCHK(before_write(tr->ev_done[2][par]));
+      KCHK(launch_gate_bwd(tr->dx, L.y_attn, mod + 2 * D, mstride, dy_a, tr->part, dmod + 2 * D, mstride, B, D, ntok,
+                           site(tr, l, 1), kNoDrop, s));
+      JCHK(input_grad(tr, dy_a, D, L.woT, D, tr->dao, s));
+      JCHK(dw_begin(tr->ev_ready[2][par]));
+      JCHK(weight_grad(tr, dy_a, D, L.ao, D, G + L.o_o, nullptr, acc, ws));
+      JCHK(dw_end(tr->ev_done[2][par]));
+      JCHK(before_write(tr->ev_done[3][par]));
+      KCHK(launch_attention_bwd(L.q, L.k, L.vt, L.ao, tr->dao, L.lse, tr->delta, dq, m->rope_cos, m->rope_sin, B, ntok,
+                                m->Hq, m->Hkv, tr->npad, site(tr, l, 0), tr->dkv_part, s));
+      JCHK(input_grad(tr, dq, Nqkv, L.wqkvT, D, tr->dxn, s));
+      JCHK(dw_begin(tr->ev_ready[3][par]));
+      JCHK(weight_grad(tr, dq, Nqkv, L.xn1, D, tr->dwqkv, nullptr, false, ws));   // scratch: the unpack below is what accumulates
+      KCHK(launch_unpack_qkv_grad(tr->dwqkv, G + L.o_q, G + L.o_k, G + L.o_v, D, m->kvD, D, acc, ws));
+      JCHK(dw_end(tr->ev_done[3][par]));
+      KCHK(launch_norm_bwd(tr->x[l], tr->dxn, m->layers[l].norm1, mod + 1 * D, mstride, tr->dx, 1, tr->part, tr->dw_part, dmod + 0 * D,
+                           dmod + 1 * D, mstride, tr->rms ? G + L.o_n1 : nullptr, acc, B, D, ntok, mode, s));
+      // adaLN modulation Linear(SiLU(t_emb)) of this block (:275-278): its six dmod slices are complete now (a weight gradient
+      // like the others: nothing in the chain reads it)
+      JCHK(dw_begin(tr->ev_mod[par]));
+      KCHK(launch_small_dw(dmod, mstride, tr->t_emb, D, G + L.o_ada_w, G + L.o_ada_b, B, 6 * D, D, 1, acc, ws));
+      if (tr->dw_async) HIPCHK(hipEventRecord(tr->ev_layer[l], ws));
+      if (tr->dw_async) {
+        if (pending_hook >= 0) JCHK(fire_hook(pending_hook));
+        pending_hook = l;
+      } else {
+        JCHK(fire_hook(l));
+      }
     }
-  }
-  if (tr->dw_async) {   // join: everything below (and the optimiser) runs on `s` alone again and may reuse the dW scratch
+    return JAT_OK;
+  };
+  const int chain_rc = chain();
+  // join: everything below (and the optimiser) runs on `s` alone again and may reuse the dW scratch.  Also when the chain failed:
+  // whatever it did queue on the second stream is ordered before the caller's next work on `s` — an accumulating call reads
+  // the gradients the previous call's second stream wrote.
+  if (tr->dw_async) {
     HIPCHK(hipEventRecord(tr->ev_join, ws));
     HIPCHK(hipStreamWaitEvent(s, tr->ev_join, 0));
-    if (pending_hook >= 0) JCHK(fire_hook(pending_hook));
   }
+  if (chain_rc != JAT_OK) return chain_rc;
+  if (tr->dw_async && pending_hook >= 0) JCHK(fire_hook(pending_hook));
   // patch embed: Linear(Kp -> bott) - GELU - Linear(bott -> D)   (jat_audiosr_v3.py:221-225); no gradient to the input
   KCHK(launch_cast_bf16(tr->dx, tr->dy, (int64_t)M * D, s));
   JCHK(input_grad(tr, tr->dy, D, tr->pe_w2T, m->bott, tr->dh, s));
-  JCHK(weight_grad(tr, tr->dy, D, tr->pe_h, m->bott, G + tr->o_pe_w2, G + tr->o_pe_b2, s));
+  JCHK(weight_grad(tr, tr->dy, D, tr->pe_h, m->bott, G + tr->o_pe_w2, G + tr->o_pe_b2, acc, s));
   KCHK(launch_gelu_bwd(tr->pe_pre, tr->dh, (int64_t)M * m->bott, kNoDrop, s));
-  JCHK(weight_grad(tr, tr->dh, m->bott, tr->a_patch, m->Kp, G + tr->o_pe_w1, G + tr->o_pe_b1, s));
+  JCHK(weight_grad(tr, tr->dh, m->bott, tr->a_patch, m->Kp, G + tr->o_pe_w1, G + tr->o_pe_b1, acc, s));
   // the t_embedder MLP (:364-369) behind all adaLN Linears; fp32, B rows
   // d silu(t_emb) = dmod [B, depth*6D] @ W_ada (the packed bf16 copy the forward multiplied with), all layers at once
   KCHK(launch_small_dx(tr->dmod, mstride, m->wada, 1, tr->small_part, tr->dt_emb, B, (int)mstride, D, 0, tr->t_emb, s));
-  KCHK(launch_small_dw(tr->dt_emb, D, tr->t_h, D, G + tr->o_te_w2, G + tr->o_te_b2, B, D, D, 0, s));
+  KCHK(launch_small_dw(tr->dt_emb, D, tr->t_h, D, G + tr->o_te_w2, G + tr->o_te_b2, B, D, D, 0, acc, s));
   KCHK(launch_small_dx(tr->dt_emb, D, tr->P + tr->o_te_w2, 0, tr->small_part, tr->du1, B, D, D, 0, tr->u1, s));
-  KCHK(launch_small_dw(tr->du1, D, tr->e_sin, D, G + tr->o_te_w1, G + tr->o_te_b1, B, D, D, 0, s));
-  if (tr->hook) tr->hook(0, tr->block_lo[0], tr->hook_user);
+  KCHK(launch_small_dw(tr->du1, D, tr->e_sin, D, G + tr->o_te_w1, G + tr->o_te_b1, B, D, D, 0, acc, s));
+  if (tr->hook && !tr->no_hook) tr->hook(0, tr->block_lo[0], tr->hook_user);
   return JAT_OK;
 }
 
@@ -558,6 +599,7 @@ extern "C" int jat_trainer_create(jat_model* m, const jat_tensor_ref* params, in
       for (auto& sh : shapes)
         if (gemm_tn_supports(sh[0], sh[1])) need = std::max(need, (size_t)gemm_tn_ksplit(sh[0], sh[1], M) * sh[0] * sh[1]);
       tr->dw_split = (float*)take(need * 4);
+      tr->dw_split_floats = (int64_t)need;
     }
     tr->zero_cell = take(256);
     tr->copy_jobs = (CopyJob*)take((size_t)(8 + 5 * depth + 2) * sizeof(CopyJob));
@@ -703,12 +745,22 @@ extern "C" int jat_trainer_prepare(jat_trainer* tr, const float* hr_norm, float*
 extern "C" int jat_trainer_fwd_bwd(jat_trainer* tr, const float* z_t, const float* t, const float* x_cond,
                                    const float* target, const float* cond_clean, float loss_scale, uint64_t rng_seed,
                                    float* loss_out, float* x_pred_out, void* stream) {
+  return jat_trainer_fwd_bwd_ex(tr, z_t, t, x_cond, target, cond_clean, loss_scale, rng_seed, loss_out, x_pred_out, 0, stream);
+}
+
+extern "C" int jat_trainer_fwd_bwd_ex(jat_trainer* tr, const float* z_t, const float* t, const float* x_cond,
+                                      const float* target, const float* cond_clean, float loss_scale, uint64_t rng_seed,
+                                      float* loss_out, float* x_pred_out, int32_t flags, void* stream) {
   if (!tr || !z_t || !t || !x_cond || !target) return fail(JAT_E_INVALID, "null argument");
+  if (flags & ~(JAT_FB_ACCUMULATE | JAT_FB_NO_HOOK)) return fail(JAT_E_INVALID, "unknown flag bits 0x%x", (unsigned)flags);
   if (tr->lw != 0.0 && tr->cw != 0.0 && !cond_clean)
     return fail(JAT_E_INVALID, "the consistency loss needs the clean condition latent (cond_clean)");
   if (!tr->m->loaded) return fail(JAT_E_STATE, "weights not loaded");
   hipStream_t s = (hipStream_t)stream;
   tr->seed = rng_seed;
+  tr->accum = (flags & JAT_FB_ACCUMULATE) != 0;
+  tr->no_hook = (flags & JAT_FB_NO_HOOK) != 0;
+  if (tr->accum) JCHK(accumulate_supported(tr));   // before anything is queued: never a half-accumulated buffer
   JCHK(forward_train(tr, z_t, t, x_cond, s));
   JCHK(backward_train(tr, target, cond_clean, loss_scale, s));
   if (loss_out) HIPCHK(hipMemcpyAsync(loss_out, tr->scal, 4, hipMemcpyDeviceToDevice, s));
@@ -862,7 +914,7 @@ extern "C" int jat_k_norm_bwd(const float* x, const uint16_t* dy, const float* w
   if (work_bytes < need) return fail(JAT_E_INVALID, "work needs %zu bytes", need);
   float* part = (float*)work;
   KCHK(launch_norm_bwd(x, dy, w, scale, mod_bstride, dx, accumulate ? 1 : 0, part, part + part_f, dshift, dscale, dmod_bstride,
-                       dw, B, D, ntok, mode, (hipStream_t)stream));
+                       dw, 0, B, D, ntok, mode, (hipStream_t)stream));
   return JAT_OK;
 }
 
@@ -960,7 +1012,7 @@ extern "C" int jat_k_small_dw(const float* dy, int64_t ldy, const float* x, int6
   if (N <= 0 || K <= 0 || K % 4 != 0 || ldy < N || ldx < K || ldx % 4 != 0)
     return fail(JAT_E_INVALID, "N > 0, K a positive multiple of 4, ldy >= N, ldx >= K a multiple of 4");
   if (!al16(x) || !al16(dW)) return fail(JAT_E_INVALID, "x and dW must be 16-byte aligned");
-  KCHK(launch_small_dw(dy, ldy, x, ldx, dW, db, B, N, K, silu_x ? 1 : 0, (hipStream_t)stream));
+  KCHK(launch_small_dw(dy, ldy, x, ldx, dW, db, B, N, K, silu_x ? 1 : 0, 0, (hipStream_t)stream));
   return JAT_OK;
 }
 

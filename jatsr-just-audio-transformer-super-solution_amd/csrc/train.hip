@@ -73,6 +73,9 @@ hipError_t launch_transpose_bf16(const bf16_t* in, int64_t ld_in, int M, int C, 
 }
 
 // out[i] = sum_z part[z * stride + i]   (split-K partials of a dW GEMM, fixed order)
+// ACC (gradient accumulation): out[i] = out[i] + that sum, the partials summed in the same order first, then one add of the
+// resident value.  The same rule in every gradient writer below that takes ACC.
+template <bool ACC>
 __global__ void __launch_bounds__(256) sum_partials_kernel(const float* __restrict__ part, int nsplit, int64_t stride,
                                                            float* __restrict__ out, int64_t n4) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -82,15 +85,23 @@ __global__ void __launch_bounds__(256) sum_partials_kernel(const float* __restri
     const f32x4_t v = *(const f32x4_t*)(part + (int64_t)z * stride + i * 4);
     acc[0] += v[0]; acc[1] += v[1]; acc[2] += v[2]; acc[3] += v[3];
   }
+  if constexpr (ACC) {
+    const f32x4_t old = *(const f32x4_t*)(out + i * 4);
+    acc[0] = old[0] + acc[0]; acc[1] = old[1] + acc[1]; acc[2] = old[2] + acc[2]; acc[3] = old[3] + acc[3];
+  }
   *(f32x4_t*)(out + i * 4) = acc;
 }
-hipError_t launch_sum_partials(const float* part, int nsplit, int64_t stride, float* out, int64_t n, hipStream_t s) {
+// nsplit == 1 with accumulate: out += part (how a product that cannot accumulate in its own epilogue gets added)
+hipError_t launch_sum_partials(const float* part, int nsplit, int64_t stride, float* out, int64_t n, int accumulate, hipStream_t s) {
   if (n % 4 != 0 || stride % 4 != 0) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(sum_partials_kernel, dim3((unsigned)((n / 4 + 255) / 256)), dim3(256), 0, s, part, nsplit, stride, out, n / 4);
+  const dim3 grid((unsigned)((n / 4 + 255) / 256));
+  if (accumulate) hipLaunchKernelGGL(sum_partials_kernel<true>, grid, dim3(256), 0, s, part, nsplit, stride, out, n / 4);
+  else hipLaunchKernelGGL(sum_partials_kernel<false>, grid, dim3(256), 0, s, part, nsplit, stride, out, n / 4);
   return hipGetLastError();
 }
 
 // ---- row sums of a bf16 matrix [R][ld] over its first n columns -> fp32 [R]   (bias gradients from dY^T) -------
+template <bool ACC>
 __global__ void __launch_bounds__(256) rowsum_bf16_kernel(const bf16_t* __restrict__ x, int64_t ld, int R, int n,
                                                           float* __restrict__ out) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
@@ -103,11 +114,12 @@ __global__ void __launch_bounds__(256) rowsum_bf16_kernel(const bf16_t* __restri
     for (int i = 0; i < 8; ++i) acc += f[i];
   }
   acc = wave_sum_t(acc);
-  if (lane == 0) out[row] = acc;
+  if (lane == 0) out[row] = ACC ? out[row] + acc : acc;
 }
-hipError_t launch_rowsum_bf16(const bf16_t* x, int64_t ld, int R, int n, float* out, hipStream_t s) {
+hipError_t launch_rowsum_bf16(const bf16_t* x, int64_t ld, int R, int n, float* out, int accumulate, hipStream_t s) {
   if (n % 8 != 0) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(rowsum_bf16_kernel, dim3((R + 3) / 4), dim3(256), 0, s, x, ld, R, n, out);
+  if (accumulate) hipLaunchKernelGGL(rowsum_bf16_kernel<true>, dim3((R + 3) / 4), dim3(256), 0, s, x, ld, R, n, out);
+  else hipLaunchKernelGGL(rowsum_bf16_kernel<false>, dim3((R + 3) / 4), dim3(256), 0, s, x, ld, R, n, out);
   return hipGetLastError();
 }
 
@@ -229,7 +241,9 @@ __global__ void __launch_bounds__(512) gate_bwd_kernel(const float* __restrict__
     *(f32x4_t*)(part + ((int64_t)b * nchunk + chunk) * D + c) = acc;
   }
 }
-// out[b*out_bstride + c] = sum_chunk part[(b*nchunk + chunk)*chunk_stride + c]   (sum_b: also over b, out has one row)
+// out[b*out_bstride + c] = sum_chunk part[(b*nchunk + chunk)*chunk_stride + c]   (sum_b: also over b, out has one row;
+// ACC, with sum_b only: out[c] = out[c] + that sum)
+template <bool ACC>
 __global__ void __launch_bounds__(256) reduce_chunks_kernel(const float* __restrict__ part, int nchunk, int64_t chunk_stride,
                                                             float* __restrict__ out, int64_t out_bstride, int B, int ncols,
                                                             int sum_b) {
@@ -239,7 +253,7 @@ __global__ void __launch_bounds__(256) reduce_chunks_kernel(const float* __restr
     float acc = 0.f;
     for (int b = 0; b < B; ++b)
       for (int k = 0; k < nchunk; ++k) acc += part[((int64_t)b * nchunk + k) * chunk_stride + c];
-    out[c] = acc;
+    out[c] = ACC ? out[c] + acc : acc;
   } else {
     const int b = blockIdx.y;
     float acc = 0.f;
@@ -255,7 +269,7 @@ hipError_t launch_gate_bwd(const float* dx, const bf16_t* y, const float* gate, 
   const int nthr = (D / 4 <= 512 && D % 256 == 0) ? D / 4 : 256;
   hipLaunchKernelGGL(gate_bwd_kernel, dim3(nchunk, B), dim3(nthr), 0, s, dx, y, gate, gate_bstride, dy, part, D, ntok, path,
                      elem);
-  hipLaunchKernelGGL(reduce_chunks_kernel, dim3((D + 255) / 256, B), dim3(256), 0, s, part, nchunk, (int64_t)D, dgate,
+  hipLaunchKernelGGL(reduce_chunks_kernel<false>, dim3((D + 255) / 256, B), dim3(256), 0, s, part, nchunk, (int64_t)D, dgate,
                      dgate_bstride, B, D, 0);
   return hipGetLastError();
 }
@@ -378,11 +392,11 @@ __global__ void __launch_bounds__(256) norm_bwd_finish_kernel(const float* __res
   for (int k = 0; k < nchunk; ++k) acc += part[(((int64_t)b * nchunk + k) * 3 + which) * D + c];
   out[(int64_t)b * (which == 2 ? (int64_t)D : dmod_bstride) + c] = acc;
 }
-// dshift/dscale: [B] rows with stride dmod_bstride (nullptr: skip); dw [D] (nullptr: skip).  part: B*nchunk*3*D floats,
-// dw_part: B*D floats.
+// dshift/dscale: [B] rows with stride dmod_bstride (nullptr: skip); dw [D] (nullptr: skip; dw_accumulate: added into dw).
+// part: B*nchunk*3*D floats, dw_part: B*D floats.
 hipError_t launch_norm_bwd(const float* x, const bf16_t* dy, const float* w, const float* scale, int64_t mod_bstride,
                            float* dx, int accumulate, float* part, float* dw_part, float* dshift, float* dscale,
-                           int64_t dmod_bstride, float* dw, int B, int D, int ntok, int mode, hipStream_t s) {
+                           int64_t dmod_bstride, float* dw, int dw_accumulate, int B, int D, int ntok, int mode, hipStream_t s) {
   if (D % 256 != 0 || D > 2048) return hipErrorInvalidValue;
   const int nchunk = train_nchunk(ntok);
 #define NORM_BWD_CASE(NCH)                                                                                              \
@@ -402,8 +416,11 @@ hipError_t launch_norm_bwd(const float* x, const bf16_t* dy, const float* w, con
   // one launch finishes dshift / dscale per sample and the per-sample part of dw; a second sums dw over the samples
   hipLaunchKernelGGL(norm_bwd_finish_kernel, dim3((D + 255) / 256, B, 3), dim3(256), 0, s, part, nchunk, D, dshift, dscale,
                      dmod_bstride, dw ? dw_part : nullptr);
-  if (dw)
-    hipLaunchKernelGGL(reduce_chunks_kernel, dim3((D + 255) / 256), dim3(256), 0, s, dw_part, 1, (int64_t)D, dw, (int64_t)0, B,
+  if (dw && dw_accumulate)
+    hipLaunchKernelGGL(reduce_chunks_kernel<true>, dim3((D + 255) / 256), dim3(256), 0, s, dw_part, 1, (int64_t)D, dw, (int64_t)0, B,
+                       D, 1);
+  else if (dw)
+    hipLaunchKernelGGL(reduce_chunks_kernel<false>, dim3((D + 255) / 256), dim3(256), 0, s, dw_part, 1, (int64_t)D, dw, (int64_t)0, B,
                        D, 1);
   return hipGetLastError();
 }
@@ -888,6 +905,23 @@ hipError_t launch_charbonnier_grad(const float* pred, const float* target, float
   return hipGetLastError();
 }
 
+// ---- gradient accumulation: the loss cells add up over the micro-batches of one optimiser step --------------------------------
+// cell = the 1-float loss (n = 1) or the six terms of the latent loss (n = 6), keep = n spare floats beside it.  phase 0, before
+// the loss kernels overwrite the cells: keep = cell; phase 1, after them: cell = keep + cell (the earlier sum first).
+__global__ void __launch_bounds__(64) loss_carry_kernel(float* __restrict__ loss, float* __restrict__ loss_keep,
+                                                        float* __restrict__ terms, float* __restrict__ terms_keep, int phase) {
+  const int i = threadIdx.x;
+  if (i > 6 || (i > 0 && !terms)) return;
+  float* cell = i == 0 ? loss : terms + (i - 1);
+  float* keep = i == 0 ? loss_keep : terms_keep + (i - 1);
+  if (phase == 0) *keep = *cell;
+  else *cell = *keep + *cell;
+}
+hipError_t launch_loss_carry(float* loss, float* loss_keep, float* terms, float* terms_keep, int phase, hipStream_t s) {
+  hipLaunchKernelGGL(loss_carry_kernel, dim3(1), dim3(64), 0, s, loss, loss_keep, terms, terms_keep, phase);
+  return hipGetLastError();
+}
+
 // ---- global gradient norm + clip + AdamW (torch.nn.utils.clip_grad_norm_, torch.optim.AdamW semantics) ---------------
 __global__ void __launch_bounds__(256) sqsum_kernel(const float* __restrict__ g, int64_t n, float* __restrict__ part) {
   __shared__ float red[4];
@@ -987,11 +1021,18 @@ hipError_t launch_adamw(float* p, float* g, float* m, float* v, int64_t n, const
   return hipGetLastError();
 }
 
+// old + g per element: one rounded fp32 add that is never contracted into an FMA with the multiply that produced g
+__device__ __forceinline__ f32x4_t add4_rn(const f32x4_t old, const f32x4_t g) {
+#pragma clang fp contract(off)
+  return f32x4_t{old[0] + g[0], old[1] + g[1], old[2] + g[2], old[3] + g[3]};
+}
+
 // ---- small-batch Linear backward (adaLN modulation and t_embedder: B <= 32 rows, weights up to [215040, 1280]) --------
 // Both are HBM-bound streams over the weight-sized operand: dW is written once (fp32), W is read once (bf16 or fp32).
 // dW[n][k] = sum_b dy[b][n] * x[b][k]   (optionally x -> silu(x));   db[n] = sum_b dy[b][n]
 // One block = DW_R output rows; a thread owns 4 consecutive k (float4 stores) and keeps DW_R x 4 accumulators.
 constexpr int DW_R = 16;
+template <bool ACC>   // ACC: dW and db are added into
 __global__ void __launch_bounds__(320) small_dw_kernel(const float* __restrict__ dy, int64_t ldy, const float* __restrict__ x,
                                                        int64_t ldx, float* __restrict__ dW, float* __restrict__ db, int B,
                                                        int N, int K, int silu_x) {
@@ -1023,12 +1064,16 @@ __global__ void __launch_bounds__(320) small_dw_kernel(const float* __restrict__
     }
 #pragma unroll
     for (int r = 0; r < DW_R; ++r)
-      if (n0 + r < N) *(f32x4_t*)(dW + (int64_t)(n0 + r) * K + k) = acc[r];
+      if (n0 + r < N) {
+        float* dst = dW + (int64_t)(n0 + r) * K + k;
+        if constexpr (ACC) *(f32x4_t*)dst = add4_rn(*(const f32x4_t*)dst, acc[r]);
+        else *(f32x4_t*)dst = acc[r];
+      }
   }
   if (db && threadIdx.x < DW_R && n0 + threadIdx.x < N) {
     float bsum = 0.f;
     for (int b = 0; b < B; ++b) bsum += sdy[b][threadIdx.x];
-    db[n0 + threadIdx.x] = bsum;
+    db[n0 + threadIdx.x] = ACC ? db[n0 + threadIdx.x] + bsum : bsum;
   }
 }
 // partial dx: part[slab][b][k] = sum_{n in slab} dy[b][n] * W[n][k]; W bf16 (packed operand copy) or fp32.
@@ -1086,10 +1131,12 @@ __global__ void __launch_bounds__(256) small_dx_finish_kernel(const float* __res
   dx[i] = acc;
 }
 hipError_t launch_small_dw(const float* dy, int64_t ldy, const float* x, int64_t ldx, float* dW, float* db, int B, int N,
-                           int K, int silu_x, hipStream_t s) {
+                           int K, int silu_x, int accumulate, hipStream_t s) {
   if (K % 4 != 0 || B > 64) return hipErrorInvalidValue;
   const int threads = K / 4 >= 320 ? 320 : 64 * ((K / 4 + 63) / 64);   // one pass over K for K = 1280
-  hipLaunchKernelGGL(small_dw_kernel, dim3((N + DW_R - 1) / DW_R), dim3(threads), 0, s, dy, ldy, x, ldx, dW, db, B, N, K, silu_x);
+  const dim3 grid((N + DW_R - 1) / DW_R);
+  if (accumulate) hipLaunchKernelGGL(small_dw_kernel<true>, grid, dim3(threads), 0, s, dy, ldy, x, ldx, dW, db, B, N, K, silu_x);
+  else hipLaunchKernelGGL(small_dw_kernel<false>, grid, dim3(threads), 0, s, dy, ldy, x, ldx, dW, db, B, N, K, silu_x);
   return hipGetLastError();
 }
 int small_dx_slab(int N) { return N >= 16384 ? 256 : 32; }
@@ -1121,6 +1168,7 @@ hipError_t launch_silu_f32(const float* in, float* out, int64_t n, hipStream_t s
 
 // ---- gradient of the fused, pair-interleaved [Wq; Wk; Wv] back to the reference's three tensors -------------------------
 // fused row (h*64 + 2d + e) of the q / k part holds reference row (h*64 + d + 32e)   (elementwise.hip cast_bf16_rope_rows)
+template <bool ACC>   // ACC: added into gq / gk / gv
 __global__ void __launch_bounds__(256) unpack_qkv_grad_kernel(const float* __restrict__ fused, float* __restrict__ gq,
                                                               float* __restrict__ gk, float* __restrict__ gv, int D, int kvD,
                                                               int K) {
@@ -1133,11 +1181,17 @@ __global__ void __launch_bounds__(256) unpack_qkv_grad_kernel(const float* __res
   } else {
     dst = gv + (int64_t)(r - D - kvD) * K;
   }
-  for (int k = threadIdx.x * 4; k < K; k += 1024) *(f32x4_t*)(dst + k) = *(const f32x4_t*)(fused + (int64_t)r * K + k);
+  for (int k = threadIdx.x * 4; k < K; k += 1024) {
+    const f32x4_t v = *(const f32x4_t*)(fused + (int64_t)r * K + k);
+    if constexpr (ACC) *(f32x4_t*)(dst + k) = add4_rn(*(const f32x4_t*)(dst + k), v);
+    else *(f32x4_t*)(dst + k) = v;
+  }
 }
-hipError_t launch_unpack_qkv_grad(const float* fused, float* gq, float* gk, float* gv, int D, int kvD, int K, hipStream_t s) {
+hipError_t launch_unpack_qkv_grad(const float* fused, float* gq, float* gk, float* gv, int D, int kvD, int K, int accumulate,
+                                  hipStream_t s) {
   if (K % 4 != 0) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(unpack_qkv_grad_kernel, dim3(D + 2 * kvD), dim3(256), 0, s, fused, gq, gk, gv, D, kvD, K);
+  if (accumulate) hipLaunchKernelGGL(unpack_qkv_grad_kernel<true>, dim3(D + 2 * kvD), dim3(256), 0, s, fused, gq, gk, gv, D, kvD, K);
+  else hipLaunchKernelGGL(unpack_qkv_grad_kernel<false>, dim3(D + 2 * kvD), dim3(256), 0, s, fused, gq, gk, gv, D, kvD, K);
   return hipGetLastError();
 }
 

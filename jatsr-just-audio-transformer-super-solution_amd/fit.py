@@ -35,6 +35,22 @@ VAL_TAGS = {"mse_loss": "Val/MSE_Loss", "freq_loss": "Val/LatentPerc_FreqLoss", 
             "consistency_loss": "Val/LatentPerc_ConsistencyLoss", "total_latent_loss": "Val/LatentPerc_TotalLoss"}
 
 
+def _accum_steps(text):
+    k = int(text)
+    if k < 1:
+        raise argparse.ArgumentTypeError(f"must be >= 1, got {k}")
+    return k
+
+
+def steps_per_epoch(n_batches, grad_accum_steps):
+    """(optimiser steps, batches left over) of an epoch whose plan has n_batches batches: a step consumes grad_accum_steps
+    consecutive batches, and what does not fill a step is dropped."""
+    k = int(grad_accum_steps)
+    if k < 1:
+        raise ValueError(f"grad_accum_steps must be >= 1, got {grad_accum_steps!r}")
+    return n_batches // k, n_batches % k
+
+
 def build_parser():
     from .io import frames_for_seconds
     d = DEFAULTS
@@ -65,6 +81,9 @@ def build_parser():
                         "raw weights, stored in every checkpoint (infer --ema samples from it); default: none")
     p.add_argument("--no-ema-warmup", dest="ema_warmup", action="store_false",
                    help="with --ema-decay: the constant decay from the first step instead of min(decay, (1 + n) / (10 + n))")
+    p.add_argument("--grad-accum-steps", type=_accum_steps, default=1,
+                   help="micro-batches per optimiser step (effective batch = this x --batch-size per rank); steps, --max-steps, "
+                        "--log-interval and --save-interval-steps count optimiser steps; default 1: none")
     p.add_argument("--amp-dtype", default=None, choices=["bf16", "fp16"], help="must match the loaded library (JAT_OPERAND_DTYPE)")
     p.add_argument("--samples-per-epoch-multiplier", type=int, default=d["samples_per_epoch_multiplier"])
     p.add_argument("--max-resident-gb", type=float, default=None, help="device memory for the data set; default half of what is free")
@@ -140,7 +159,8 @@ def build_trainer(args, model, total_steps, process_group=None, rank=0, distribu
                    condition_noise_ratio=args.condition_noise_ratio, use_adaptive_noise=args.use_adaptive_noise,
                    warmup_steps=args.warmup_steps, total_steps=total_steps, process_group=process_group,
                    seed=args.seed + rank, latent_loss_weight=args.latent_loss_weight, distributed=distributed,
-                   amp_dtype=args.amp_dtype, loss=args.loss, ema_decay=args.ema_decay, ema_warmup=args.ema_warmup)
+                   amp_dtype=args.amp_dtype, loss=args.loss, ema_decay=args.ema_decay, ema_warmup=args.ema_warmup,
+                   grad_accum_steps=getattr(args, "grad_accum_steps", 1))
 
 
 def loop_step(trainer, store, plans, i, stats, lr, monitor):
@@ -150,6 +170,15 @@ def loop_step(trainer, store, plans, i, stats, lr, monitor):
     if i + 1 < len(plans):
         store.prefetch(*plans[i + 1])
     return trainer.step_normalised(hr_norm, lr_norm, monitor=monitor, lr=lr)
+
+
+def loop_micro(trainer, store, plans, i, stats):
+    """The same data path for a batch that is not the last micro-batch of its optimiser step (--grad-accum-steps): its
+    gradients are added up, nothing steps and the host does not wait."""
+    hr_norm, lr_norm = store.batch(*plans[i], stats)
+    if i + 1 < len(plans):
+        store.prefetch(*plans[i + 1])
+    trainer.accumulate_normalised(hr_norm, lr_norm)
 
 
 class _ValDraws:
@@ -195,6 +224,8 @@ def run(args):
         raise ValueError(f"loss must be 'mse' or 'charbonnier', got {args.loss!r}")
     if args.loss == "charbonnier" and args.latent_loss_weight != 0.0:
         raise ValueError("--loss charbonnier needs --latent-loss-weight 0 (train_ddp_v3m2mod1.py has no latent term)")
+    accum = int(getattr(args, "grad_accum_steps", 1))
+    steps_per_epoch(0, accum)                         # rejects a count below 1
     L.require_gpu()
     rank, world, local = _dist_setup()
     master = rank == 0
@@ -221,9 +252,12 @@ def run(args):
     val_store = LatentStore(args.data_dir, "val", T, device, budget) if has_val else None
     stats_path = args.stats_file if os.path.isabs(args.stats_file) else os.path.join(args.data_dir, args.stats_file)
     stats = jio.load_stats(stats_path, channels=C, device=device)
-    per_epoch = len(epoch_batches(len(train_store), mult, B, 0, rank, world, True, args.seed))
+    per_epoch, dropped = steps_per_epoch(len(epoch_batches(len(train_store), mult, B, 0, rank, world, True, args.seed)), accum)
     if per_epoch == 0:
-        raise ValueError(f"{len(train_store)} files x {mult} over {world} rank(s) give no batch of {B}")
+        raise ValueError(f"{len(train_store)} files x {mult} over {world} rank(s) give no batch of {B}" +
+                         (f" x {accum} micro-batches" if accum > 1 else ""))
+    if dropped and master:
+        print(f"{dropped} batch(es) per epoch do not fill an optimiser step of {accum} micro-batches and are dropped")
     total_steps = per_epoch * args.epochs
     model = build_model(args, device)
     trainer = build_trainer(args, model, total_steps, rank=rank, distributed=world > 1)
@@ -261,14 +295,17 @@ def run(args):
             break
         batches = epoch_batches(len(train_store), mult, B, epoch, rank, world, True, args.seed)
         plans = [train_batch_plan(train_store.lengths, T, b, args.seed, epoch) for b in batches]
+        plans = plans[:per_epoch * accum]       # an optimiser step consumes `accum` consecutive batches of the plan
         t0, epoch_loss = time.time(), 0.0
-        for i, (files, starts) in enumerate(plans):
+        for i in range(accum - 1, len(plans), accum):     # i: the step's last micro-batch
             g = trainer.global_step
             if args.max_steps is not None and g >= args.max_steps:
                 done = True          # inside an epoch: no last.pt for it; resume restarts from the last finished epoch
                 break
             lr_now = get_lr(g, total_steps, args.warmup_steps, args.lr)
             logging = g % args.log_interval == 0
+            for j in range(i - accum + 1, i):
+                loop_micro(trainer, train_store, plans, j, stats)
             out = loop_step(trainer, train_store, plans, i, stats, lr_now, logging)
             epoch_loss += out["loss"]
             if logging:

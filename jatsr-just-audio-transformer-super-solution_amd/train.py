@@ -163,7 +163,8 @@ class Trainer:
                  warmup_steps=1000, total_steps=None, use_grad_scaler=True, process_group=None, seed=None,
                  latent_loss_weight=0.0, freq_loss_weight=0.5, ms_loss_weight=0.5, consistency_weight=0.1,
                  low_freq_phase_ratio=0.3, strict_cutoff=0.30, soft_cutoff=0.36, overlap_grad_allreduce=True,
-                 distributed=True, amp_dtype=None, loss="mse", charbonnier_eps=1e-6, ema_decay=None, ema_warmup=True):
+                 distributed=True, amp_dtype=None, loss="mse", charbonnier_eps=1e-6, ema_decay=None, ema_warmup=True,
+                 grad_accum_steps=1):
         """latent_loss_weight > 0 selects the v3mod2 trainer's loss, MSE + latent perceptual loss
         (train_ddp_v3mod2.py:53-321,362-372,889-896; its TrainConfig uses 0.3 with the other defaults given here, no CFG
         dropout and condition_noise_ratio 0.05); 0 is the MSE-only loss of train_ddp_v3m2.py:585.
@@ -174,6 +175,14 @@ class Trainer:
         ema_decay: keep an exponential moving average of the weights (the reference keeps none), updated inside the AdamW
         pass: `ema`, a fifth flat buffer, `ema_weights()` to run on it, `ema_state_dict()` to read it.  ema_warmup: the
         schedule of `ema_decay_at`.  None: no buffer, no extra work.
+        grad_accum_steps: k micro-batches per optimiser step (an effective batch of k * batch_size per rank).  The trainer counts
+        the `forward_backward` calls since the last `optimizer_step`: the first overwrites `grads`, the later ones add to it
+        inside the gradient kernels (`jat_trainer_fwd_bwd_ex`, JAT_FB_ACCUMULATE: no further buffer, no add pass), and only the
+        k-th lets the gradient-ready hook fire, so an overlapped exchange runs once per step, on the sums.  `optimizer_step`
+        divides by k through its un-scale factor and returns the mean loss; the scaler, `global_step`, `opt_step`, the moving
+        average and the LR schedule advance once per optimiser step, and a non-finite value in any micro-batch skips the whole
+        step.  With k > 1, `optimizer_step` after fewer than k calls, or a (k+1)-th `forward_backward`, raises JatError.  1 (the
+        default): every call is what it was without the option, and nothing is counted or refused.
         amp_dtype: "bf16" (train_ddp_v3m2.py:545) or "fp16" (`torch.amp.autocast('cuda')` of train_ddp_v3mod2.py:854, with
         the dynamic loss scale of :745); must match the operand dtype of the loaded library, which is a process-level
         choice (JAT_OPERAND_DTYPE=fp16 loads libjat_hip_fp16.so).  None: whatever the library is."""
@@ -186,6 +195,8 @@ class Trainer:
                              "the Charbonnier trainer (train_ddp_v3m2mod1.py) has no latent term")
         if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
             raise ValueError(f"ema_decay must be in [0, 1), got {ema_decay!r}")
+        if int(grad_accum_steps) != grad_accum_steps or int(grad_accum_steps) < 1:
+            raise ValueError(f"grad_accum_steps must be an integer >= 1, got {grad_accum_steps!r}")
         L.require_gpu()
         have = L.operand_dtype()
         want = {None: have, "bf16": "bf16", "bfloat16": "bf16", "fp16": "fp16", "float16": "fp16"}[amp_dtype]
@@ -203,6 +214,9 @@ class Trainer:
         self.scaler = GradScaler(enabled=use_grad_scaler)
         self.group = process_group
         self.distributed = bool(distributed)
+        self.grad_accum_steps = int(grad_accum_steps)
+        self._micro = 0          # forward_backward calls since the last optimizer_step
+        self._last_micro = 1     # micro-batches behind the loss cells of the latest optimiser step
         self.global_step = 0     # every call of optimizer_step (LR schedule, mask seed, checkpoint: train_ddp_v3m2.py:634)
         self.opt_step = 0        # optimiser steps actually taken (AdamW bias correction; skipped when the scaler finds inf)
         dev = next(model.parameters()).device
@@ -318,11 +332,13 @@ class Trainer:
 
     def loss_terms(self):
         """{total, mse, freq, ms, consistency, latent} of the latest step (the trainer's `latent_loss_dict`,
-        train_ddp_v3mod2.py:313-318); MSE-only trainers return {total}."""
+        train_ddp_v3mod2.py:313-318); MSE-only trainers return {total}.  With grad_accum_steps > 1: the means over the step's
+        micro-batches (the library keeps the sums; between two micro-batches, the mean over those run so far)."""
+        n = self._micro if self._micro > 0 else self._last_micro
         if self.latent_loss["latent_weight"] == 0.0:
-            return dict(total=float(self._scal[0]))
+            return dict(total=float(self._scal[0]) / n)
         L.check(L.lib().jat_trainer_loss_terms(self.ptr, L.ptr(self._terms), L.stream_ptr()))
-        return dict(zip(("total", "mse", "freq", "ms", "consistency", "latent"), self._terms.tolist()))
+        return dict(zip(("total", "mse", "freq", "ms", "consistency", "latent"), (v / n for v in self._terms.tolist())))
 
     def set_regularisers(self, dropout, drop_path):
         """Per-layer nn.Dropout p and DropPath rate (defaults: what the model was constructed with,
@@ -333,11 +349,16 @@ class Trainer:
         self.dropout, self.drop_path = [float(x) for x in dropout], [float(x) for x in drop_path]
         L.check(L.lib().jat_trainer_set_regularisers(self.ptr, (C.c_float * n)(*self.dropout), (C.c_float * n)(*self.drop_path)))
 
-    def step_seed(self, step=None):
-        """64-bit mask seed of a step: splitmix64 of (trainer seed, step index, rank)."""
+    def step_seed(self, step=None, micro=0):
+        """64-bit mask seed of micro-batch `micro` of a step: splitmix64 of (trainer seed, step index, micro-batch, rank).  A step
+        owns 4096 consecutive counters, micro * 64 + rank + 1 of them here: distinct for micro < 64 and rank < 64, and micro = 0
+        is the seed the step has without gradient accumulation."""
         import torch.distributed as dist
         rank = dist.get_rank(self.group) if self._dist_on() else 0
-        x = (self.mask_seed + 0x9E3779B97F4A7C15 * ((self.global_step if step is None else step) * 4096 + rank + 1)) & (2 ** 64 - 1)
+        return self._step_seed(self.global_step if step is None else step, micro, rank)
+
+    def _step_seed(self, step, micro, rank):
+        x = (self.mask_seed + 0x9E3779B97F4A7C15 * (step * 4096 + micro * 64 + rank + 1)) & (2 ** 64 - 1)
         x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & (2 ** 64 - 1)
         x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & (2 ** 64 - 1)
         return x ^ (x >> 31)
@@ -392,7 +413,9 @@ class Trainer:
 
     def forward_backward(self, z_t, t, cond, target, want_pred=False, mask_seed=None, cond_clean=None):
         """pred = model(z_t, t, cond); loss(pred, target[, cond_clean]); backward -> self.grads (scaled by scaler.scale).
-        mask_seed: 64-bit seed of this step's Dropout / DropPath masks (default: `step_seed()`).
+        mask_seed: 64-bit seed of this call's Dropout / DropPath masks (default: `step_seed(micro=j)` for the j-th call since
+        the last `optimizer_step`).  With grad_accum_steps = k > 1 call 0 overwrites `grads`, calls 1 .. k-1 add to it, `loss_terms`
+        and the loss `optimizer_step` returns add up alike, and a (k+1)-th call raises.
         cond_clean: the normalised LR latent before the condition noise (`lr_norm_original`, train_ddp_v3mod2.py:861),
         needed by the consistency term of the latent perceptual loss."""
         for x in (z_t, cond, target) + ((cond_clean,) if cond_clean is not None else ()):
@@ -404,20 +427,34 @@ class Trainer:
         self.model._get_handle()     # parameters overwritten through PyTorch (load_state_dict)? re-pack, incl. this trainer's copies
         pred = torch.empty_like(z_t) if want_pred else None
         self._pending, self._covered = [], 0
-        L.check(L.lib().jat_trainer_fwd_bwd(self.ptr, L.ptr(z_t.contiguous()), L.ptr(t.contiguous()), L.ptr(cond.contiguous()),
-                                            L.ptr(target.contiguous()),
-                                            L.ptr(cond_clean.contiguous()) if cond_clean is not None else None,
-                                            float(self.scaler.scale),
-                                            C.c_uint64(self.step_seed() if mask_seed is None else int(mask_seed)),
-                                            L.ptr(self._scal),
-                                            L.ptr(pred) if want_pred else None, L.stream_ptr()))
+        k = self.grad_accum_steps
+        j = self._micro if k > 1 else 0
+        if j >= k:
+            raise L.JatError(f"forward_backward call {j + 1} since the last optimizer_step, but grad_accum_steps is {k}: "
+                             "call optimizer_step first")
+        args = (self.ptr, L.ptr(z_t.contiguous()), L.ptr(t.contiguous()), L.ptr(cond.contiguous()), L.ptr(target.contiguous()),
+                L.ptr(cond_clean.contiguous()) if cond_clean is not None else None, float(self.scaler.scale),
+                C.c_uint64(self.step_seed(micro=j) if mask_seed is None else int(mask_seed)), L.ptr(self._scal),
+                L.ptr(pred) if want_pred else None)
+        if k == 1:
+            L.check(L.lib().jat_trainer_fwd_bwd(*args, L.stream_ptr()))
+        else:     # all but the last micro-batch keep the gradient-ready hook silent: one exchange per optimiser step
+            flags = (L.FB_ACCUMULATE if j > 0 else 0) | (L.FB_NO_HOOK if j < k - 1 else 0)
+            L.check(L.lib().jat_trainer_fwd_bwd_ex(*args, flags, L.stream_ptr()))
+            self._micro = j + 1
         return pred
 
     def optimizer_step(self, lr=None):
         """All-reduce, unscale, clip_grad_norm_(grad_clip), AdamW, re-pack.  Returns (loss, grad_norm) as floats —
-        the one host synchronisation of the step, like the reference's `.item()` calls (train_ddp_v3m2.py:615,622)."""
+        the one host synchronisation of the step, like the reference's `.item()` calls (train_ddp_v3m2.py:615,622).
+        With grad_accum_steps = k > 1: after exactly k `forward_backward` calls (else JatError); the loss is the mean of the k
+        losses and the norm that of the averaged gradient (the 1/k is part of the un-scale factor, `grads` keeps the sums)."""
         self._check_attached()
         self._check_not_in_ema("optimizer_step")
+        k = self.grad_accum_steps
+        if k > 1 and self._micro != k:
+            raise L.JatError(f"optimizer_step after {self._micro} forward_backward call(s), but grad_accum_steps is {k}: "
+                             f"run the remaining {k - self._micro} micro-batch(es) first")
         if self._pending:          # slices were reduced under the backward: the step's stream waits for the last of them
             for w in self._pending:
                 w.wait()
@@ -428,7 +465,7 @@ class Trainer:
             world = allreduce_mean_(self.grads, self.group) if self._dist_on() else 1
         if lr is None:
             lr = get_lr(self.global_step, self.total_steps, self.warmup_steps, self.base_lr) if self.total_steps else self.base_lr
-        scale = self.scaler.scale * world
+        scale = self.scaler.scale * world * k
         if self.ema is not None:
             L.check(L.lib().jat_trainer_set_ema(self.ptr, L.ptr(self.ema),
                                                 ema_decay_at(self.ema_updates + 1, self.ema_decay, self.ema_warmup)))
@@ -436,7 +473,9 @@ class Trainer:
                                           float(self.weight_decay), float(self.grad_clip or 0.0), float(scale),
                                           self.opt_step + 1, C.c_void_p(self._scal.data_ptr() + 4), L.stream_ptr()))
         loss, gnorm = self._scal.tolist()
+        loss /= k
         gnorm /= scale
+        self._micro, self._last_micro = 0, k
         found_inf = not math.isfinite(gnorm)    # the same on every rank: the norm is taken over the all-reduced gradients
         self.scaler.update(found_inf)
         self.global_step += 1                   # counts batches, skipped or not (train_ddp_v3m2.py:634)
@@ -448,8 +487,27 @@ class Trainer:
         self.last_lr = lr
         return loss, gnorm
 
+    def accumulate(self, hr, lr, hr_mean, hr_std, lr_mean, lr_std):
+        """Raw latents in, one micro-batch of a step with grad_accum_steps > 1: normalise, prepare, forward_backward, no
+        optimiser step.  The k-th micro-batch of a step goes to `train_step`."""
+        from .sampler import channel_affine
+        hr_norm = channel_affine(hr.to(self.device, torch.float32), hr_mean, hr_std)
+        lr_norm = channel_affine(lr.to(self.device, torch.float32), lr_mean, lr_std)
+        self.accumulate_normalised(hr_norm, lr_norm)
+
+    def accumulate_normalised(self, hr_norm, lr_norm):
+        """One micro-batch on latents that are already normalised: prepare -> forward_backward(..., cond_clean=lr_norm),
+        without stepping and without a host synchronisation.  The k-th micro-batch of a step goes to `step_normalised`."""
+        if self._micro >= self.grad_accum_steps - 1:
+            raise L.JatError(f"micro-batch {self._micro + 1} of {self.grad_accum_steps} is the step's last: it belongs to "
+                             "step_normalised / train_step, which also take the optimiser step")
+        z_t, t, cond = self.prepare(hr_norm, lr_norm)
+        self.forward_backward(z_t, t, cond, hr_norm, cond_clean=lr_norm)
+
     def train_step(self, hr, lr, hr_mean, hr_std, lr_mean, lr_std):
-        """Raw latents in, one optimisation step (train_ddp_v3m2.py:533-622).  Returns dict(loss, grad_norm, lr)."""
+        """Raw latents in, one optimisation step (train_ddp_v3m2.py:533-622).  Returns dict(loss, grad_norm, lr).  With
+        grad_accum_steps = k > 1 this is the step's LAST micro-batch, after k - 1 calls of `accumulate`; the loss returned is
+        the mean over the k."""
         from .sampler import channel_affine
         hr_norm = channel_affine(hr.to(self.device, torch.float32), hr_mean, hr_std)
         lr_norm = channel_affine(lr.to(self.device, torch.float32), lr_mean, lr_std)
@@ -462,7 +520,9 @@ class Trainer:
         """One optimisation step on latents that are already normalised (what `LatentStore.batch` returns with the
         statistics): prepare -> forward_backward(..., cond_clean=lr_norm) -> optimizer_step, `train_step` without its two
         normalisation passes.  monitor=True also keeps the prediction and returns the figures the reference logs
-        (train_ddp_v3mod2.py:902-919): snr_db, pred_mean, pred_std, cond_noise_std, from one `jat_train_monitor` pass."""
+        (train_ddp_v3mod2.py:902-919): snr_db, pred_mean, pred_std, cond_noise_std, from one `jat_train_monitor` pass.
+        With grad_accum_steps = k > 1 this is the step's LAST micro-batch, after k - 1 calls of `accumulate_normalised`: loss
+        and grad_norm are those of the whole step, the monitor figures those of this last micro-batch alone."""
         z_t, t, cond = self.prepare(hr_norm, lr_norm)
         pred = self.forward_backward(z_t, t, cond, hr_norm, want_pred=monitor, cond_clean=lr_norm)
         sums = train_monitor(pred, hr_norm, lr_norm) if monitor else None      # queued before the step's one host sync
