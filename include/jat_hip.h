@@ -212,7 +212,20 @@ int jat_trainer_set_latent_loss(jat_trainer* tr, double latent_weight, double fr
  *   charbonnier_loss(pred, target, eps) = mean(sqrt((pred - target)^2 + eps)),  eps = 1e-6 (ADDED to the squared difference)
  * eps > 0 selects it, eps == 0 returns to F.mse_loss.  Not combinable with the latent perceptual loss (JAT_E_STATE). */
 int jat_trainer_set_charbonnier(jat_trainer* tr, double eps);
-/* out6 (device): {total, mse, freq, ms, consistency, weighted latent sum} of the latest jat_trainer_fwd_bwd. */
+/* The whole loss of the V3-MOD3 trainer in one call (train_ddp_v3mod3.py:57-85,400-434,955-969; validation :1138-1159):
+ *   loss = recon_weight * recon + latent_weight * (freq_weight * freq + ms_weight * ms + consistency_weight * consistency)
+ * recon = charbonnier_loss(pred, target, recon_eps) for recon_eps > 0 (`use_charbonnier_loss`), F.mse_loss for recon_eps == 0;
+ * the reference's defaults are 1e-6 / 1.0 / 0.3 / 0.5 / 0.5 / 0.1 and the band ratios of jat_trainer_set_latent_loss.  With a latent
+ * weight the reconstruction term is computed inside the latent loss kernels (no pass of its own over the prediction); with
+ * latent_weight == 0 the plain MSE / Charbonnier kernels run and recon_weight scales their result.  (0, 1, ...) is exactly
+ * jat_trainer_set_latent_loss.  Everything is validated before anything is stored: JAT_E_INVALID for a negative or non-finite
+ * recon_eps, a non-finite weight or bad band ratios; recon_weight == 0 is legal.  The two setters above keep rejecting each other
+ * (JAT_E_STATE) whatever this call stored. */
+int jat_trainer_set_loss_ex(jat_trainer* tr, double recon_eps, double recon_weight, double latent_weight, double freq_weight,
+                            double ms_weight, double consistency_weight, double low_freq_phase_ratio, double strict_cutoff,
+                            double soft_cutoff);
+/* out6 (device): {total, mse, freq, ms, consistency, weighted latent sum} of the latest jat_trainer_fwd_bwd.  Slot 1 is the
+ * reconstruction term, un-weighted, whatever its kind (the Charbonnier mean after jat_trainer_set_loss_ex with recon_eps > 0). */
 int jat_trainer_loss_terms(jat_trainer* tr, float* out6, void* stream);
 int jat_trainer_workspace_bytes(const jat_trainer* tr, size_t* out);
 /* Re-derive every operand copy (bf16 weights and their transposes, fp32 operand tensors) from params_flat after the
@@ -345,6 +358,14 @@ int jat_k_latent_loss(const float* pred, const float* target, const float* lr, f
                       int32_t rows, int32_t T, double latent_weight, double freq_weight, double ms_weight,
                       double consistency_weight, double low_freq_phase_ratio, double strict_cutoff, double soft_cutoff,
                       float loss_scale, void* work, size_t work_bytes, void* stream);
+/* jat_k_latent_loss with the reconstruction term of jat_trainer_set_loss_ex: total = recon_weight * recon + latent_weight * (...),
+ * out6[1] = recon, un-weighted (Charbonnier mean for recon_eps > 0, MSE for 0).  The same work buffer, and the same rejections
+ * before anything is launched, plus JAT_E_INVALID for a negative or non-finite recon_eps or a non-finite weight.  recon_eps == 0
+ * with recon_weight == 1 runs the very kernels of jat_k_latent_loss. */
+int jat_k_latent_loss_ex(const float* pred, const float* target, const float* lr, float* dpred, float* out6, int32_t rows,
+                         int32_t T, double recon_eps, double recon_weight, double latent_weight, double freq_weight,
+                         double ms_weight, double consistency_weight, double low_freq_phase_ratio, double strict_cutoff,
+                         double soft_cutoff, float loss_scale, void* work, size_t work_bytes, void* stream);
 /* The code path the v3mod2 loss takes at sequence length T, which depends on T alone: kind 0 = rejected (T too long for the
  * kernels' LDS image; jat_k_latent_loss and the trainer fail), 1 = direct DFT kernel with (a, b) = (bins, samples) per thread
  * (1, 2), (2, 4) or (3, 6), the last looping in chunks beyond 768 bins / 1536 samples, 2 = DFT factored T = a * b with a the

@@ -101,6 +101,7 @@ SIGNATURES = {
     "jat_k_small_dw": (C.c_int, [_VP, _I64, _VP, _I64, _VP, _VP] + [_I32] * 4 + [_VP]),
     "jat_k_small_dx": (C.c_int, [_VP, _I64, _VP, _I32, _VP] + [_I32] * 4 + [_VP, _VP, _SZ, _VP]),
     "jat_k_latent_loss": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I32, _I32] + [C.c_double] * 7 + [_F32, _VP, _SZ, _VP]),
+    "jat_k_latent_loss_ex": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I32, _I32] + [C.c_double] * 9 + [_F32, _VP, _SZ, _VP]),
     "jat_k_latent_loss_plan": (C.c_int, [_I32, _VP, _VP, _VP, _VP]),
     "jat_trainer_create": (C.c_int, [_VP, C.POINTER(JatTensorRef), _I32, _VP, _VP, _VP, _VP, _I64, _I32, _I32, _VP,
                                      C.POINTER(_VP)]),
@@ -112,6 +113,7 @@ SIGNATURES = {
     "jat_trainer_set_regularisers": (C.c_int, [_VP, C.POINTER(_F32), C.POINTER(_F32)]),
     "jat_trainer_set_latent_loss": (C.c_int, [_VP] + [C.c_double] * 7),
     "jat_trainer_set_charbonnier": (C.c_int, [_VP, C.c_double]),
+    "jat_trainer_set_loss_ex": (C.c_int, [_VP] + [C.c_double] * 9),
     "jat_trainer_loss_terms": (C.c_int, [_VP, _VP, _VP]),
     "jat_trainer_fwd_bwd": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _F32, C.c_uint64, _VP, _VP, _VP]),
     "jat_trainer_fwd_bwd_ex": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _F32, C.c_uint64, _VP, _VP, _I32, _VP]),

@@ -197,15 +197,18 @@ hipError_t launch_norm_bwd(const float* x, const bf16_t* dy, const float* w, con
 hipError_t launch_attention_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* vt, const bf16_t* o, const bf16_t* dout,
                                 const float* lse, float* delta, bf16_t* dqkv, const float* rope_cos, const float* rope_sin,
                                 int B, int N, int Hq, int Hkv, int npad, DropSpec drop, float* dkv_part, hipStream_t s);
+// rw: weight of the loss (the v3mod3 trainer's reconstruction_weight): loss2[0] = rw * mse and its gradient, by host arithmetic
 hipError_t launch_mse_grad(const float* pred, const float* target, float* dpred, float* part, float* loss2, int64_t n,
-                           float loss_scale, hipStream_t s);
+                           float loss_scale, float rw, hipStream_t s);
 // Charbonnier loss mean(sqrt((pred - target)^2 + eps)) (train_ddp_v3m2mod1.py:72-101) and d(loss * loss_scale)/d pred;
-// part: train_red_blocks() floats, loss2[0] = loss
+// part: train_red_blocks() floats, loss2[0] = rw * loss
 hipError_t launch_charbonnier_grad(const float* pred, const float* target, float* dpred, float* part, float* loss2, int64_t n,
-                                   float eps, float loss_scale, hipStream_t s);
+                                   float eps, float loss_scale, float rw, hipStream_t s);
 // v3mod2 loss (MSE + lw * (fw*freq + mw*ms + cw*cons)): dpred = d(loss * loss_scale)/d pred, out6 = {total, mse, freq, ms,
 // cons, fw*freq + mw*ms + cw*cons}; part: rows*8 floats; tw: [T] (cos, sin)(2 pi m / T); lr may be null when cw == 0.
 // low / strict / soft band edges (in rfft bins) are computed by the caller exactly as the reference does (int(F * ratio)).
+// recon_eps / recon_weight: the v3mod3 loss, recon_weight * recon + lw * (...), recon = Charbonnier(recon_eps) for recon_eps > 0,
+// MSE for 0; out6[1] is the un-weighted recon term.  (0, 1) is the v3mod2 loss on the kernels it always had.
 // The path launch_latent_loss takes at sequence length T (the one place that decides it): kind 0 = rejected (the direct LDS
 // image does not fit), 1 = direct DFT on latent_loss_kernel<a, b> = <FB, NB>, 2 = factored T = a * b = N1 * N2; lds = the
 // dynamic LDS bytes of that launch (kind 0: what the direct kernel would have needed).  Host arithmetic only.
@@ -213,7 +216,7 @@ struct LatentLossPlan { int kind, a, b; size_t lds; };
 LatentLossPlan plan_latent_loss(int T);
 hipError_t launch_latent_loss(const float* pred, const float* target, const float* lr, const float2* tw, float* dpred,
                               float* part, float* out6, int rows, int T, float lw, float fw, float mw, float cw, int low,
-                              int strict, int soft, float loss_scale, hipStream_t s);
+                              int strict, int soft, float recon_eps, float recon_weight, float loss_scale, hipStream_t s);
 hipError_t launch_grad_sqsum(const float* g, int64_t n, float* part, float* norm2, hipStream_t s);
 hipError_t launch_adamw(float* p, float* g, float* m, float* v, int64_t n, const float* norm2, float inv_scale,
                         float max_norm, float lr, float beta1, float beta2, float eps, float wd, int step, float* ema,

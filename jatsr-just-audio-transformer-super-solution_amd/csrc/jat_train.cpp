@@ -64,6 +64,7 @@ struct jat_trainer {
   // v3mod2 latent perceptual loss (jat_trainer_set_latent_loss); lw == 0: plain MSE (the V3 trainer)
   double lw = 0.0, fw = 0.5, mw = 0.5, cw = 0.1, phase_ratio = 0.3, strict_cut = 0.30, soft_cut = 0.36;
   double charb_eps = 0.0;              // > 0: Charbonnier reconstruction loss (train_ddp_v3m2mod1.py:72-101) instead of MSE
+  double rw = 1.0;                     // weight of the reconstruction term (jat_trainer_set_loss_ex; train_ddp_v3mod3.py:416,966)
   float2* tw = nullptr;                // [T] twiddles
   float *ll_part = nullptr, *terms = nullptr;
   float* dw_split = nullptr;           // split-K partials of the small dW GEMMs
@@ -293,13 +294,15 @@ int backward_train(jat_trainer* tr, const float* target, const float* cond_clean
     const int F = T / 2 + 1;   // band edges exactly as the reference computes them: int(freq_bins * ratio) in double
     KCHK(launch_latent_loss(tr->pred, target, cond_clean, tr->tw, tr->dpred, tr->ll_part, tr->terms, B * m->Cin, T,
                             (float)tr->lw, (float)tr->fw, (float)tr->mw, (float)tr->cw, (int)((double)F * tr->phase_ratio),
-                            (int)((double)F * tr->strict_cut), (int)((double)F * tr->soft_cut), loss_scale, s));
+                            (int)((double)F * tr->strict_cut), (int)((double)F * tr->soft_cut), (float)tr->charb_eps,
+                            (float)tr->rw, loss_scale, s));
     HIPCHK(hipMemcpyAsync(tr->scal, tr->terms, 4, hipMemcpyDeviceToDevice, s));
   } else if (tr->charb_eps > 0.0) {
     KCHK(launch_charbonnier_grad(tr->pred, target, tr->dpred, tr->red_part, tr->scal, (int64_t)B * m->Cin * T,
-                                 (float)tr->charb_eps, loss_scale, s));
+                                 (float)tr->charb_eps, loss_scale, (float)tr->rw, s));
   } else {
-    KCHK(launch_mse_grad(tr->pred, target, tr->dpred, tr->red_part, tr->scal, (int64_t)B * m->Cin * T, loss_scale, s));
+    KCHK(launch_mse_grad(tr->pred, target, tr->dpred, tr->red_part, tr->scal, (int64_t)B * m->Cin * T, loss_scale,
+                         (float)tr->rw, s));
   }
   if (acc) KCHK(launch_loss_carry(tr->scal, tr->scal + 12, terms, terms_keep, 1, s));
   // Where a weight gradient runs: on `s` itself, or (dw_async) on the second stream behind an event of the kernel that
@@ -714,6 +717,27 @@ extern "C" int jat_trainer_set_charbonnier(jat_trainer* tr, double eps) {
   return JAT_OK;
 }
 
+// The whole loss in one call (the v3mod3 trainer, train_ddp_v3mod3.py:400-434,955-969):
+//   recon_weight * recon + latent_weight * (freq_weight * freq + ms_weight * ms + consistency_weight * cons)
+// recon = Charbonnier(recon_eps) for recon_eps > 0, MSE for 0.  Everything is validated before anything is stored.
+extern "C" int jat_trainer_set_loss_ex(jat_trainer* tr, double recon_eps, double recon_weight, double latent_weight,
+                                       double freq_weight, double ms_weight, double consistency_weight,
+                                       double low_freq_phase_ratio, double strict_cutoff, double soft_cutoff) {
+  if (!tr) return fail(JAT_E_INVALID, "null argument");
+  if (!(recon_eps >= 0.0) || !std::isfinite(recon_eps) || (recon_eps > 0.0 && (float)recon_eps == 0.f))
+    return fail(JAT_E_INVALID, "recon_eps must be finite and >= 0 (0 selects the MSE loss) and, if positive, not below fp32's range");
+  if (!std::isfinite(recon_weight) || !std::isfinite(latent_weight) || !std::isfinite(freq_weight) || !std::isfinite(ms_weight) ||
+      !std::isfinite(consistency_weight))
+    return fail(JAT_E_INVALID, "loss weights must be finite");
+  if (!(low_freq_phase_ratio >= 0 && low_freq_phase_ratio <= 1 && strict_cutoff >= 0 && soft_cutoff >= strict_cutoff &&
+        soft_cutoff <= 1))
+    return fail(JAT_E_INVALID, "band ratios must satisfy 0 <= strict <= soft <= 1 and 0 <= phase ratio <= 1");
+  tr->charb_eps = recon_eps; tr->rw = recon_weight;
+  tr->lw = latent_weight; tr->fw = freq_weight; tr->mw = ms_weight; tr->cw = consistency_weight;
+  tr->phase_ratio = low_freq_phase_ratio; tr->strict_cut = strict_cutoff; tr->soft_cut = soft_cutoff;
+  return JAT_OK;
+}
+
 extern "C" int jat_trainer_loss_terms(jat_trainer* tr, float* out6, void* stream) {
   if (!tr || !out6) return fail(JAT_E_INVALID, "null argument");
   if (tr->lw == 0.0) return fail(JAT_E_STATE, "the latent perceptual loss is off (jat_trainer_set_latent_loss)");
@@ -810,8 +834,8 @@ extern "C" int jat_k_recon_loss(const float* pred, const float* target, float* d
   hipStream_t s = (hipStream_t)stream;
   float* part = (float*)work;
   float* loss2 = part + train_red_blocks();
-  if (eps > 0.0) KCHK(launch_charbonnier_grad(pred, target, dpred, part, loss2, n, (float)eps, loss_scale, s));
-  else KCHK(launch_mse_grad(pred, target, dpred, part, loss2, n, loss_scale, s));
+  if (eps > 0.0) KCHK(launch_charbonnier_grad(pred, target, dpred, part, loss2, n, (float)eps, loss_scale, 1.0f, s));
+  else KCHK(launch_mse_grad(pred, target, dpred, part, loss2, n, loss_scale, 1.0f, s));
   HIPCHK(hipMemcpyAsync(loss_out, loss2, 4, hipMemcpyDeviceToDevice, s));
   return JAT_OK;
 }
@@ -824,11 +848,11 @@ extern "C" int jat_k_latent_loss_plan(int32_t T, int32_t* kind, int32_t* a, int3
   return JAT_OK;
 }
 
-// per-kernel entry point (unit parity): the v3mod2 loss on [rows, T] tensors; `work` holds align_up(T*8, 256) + rows*32 bytes
-extern "C" int jat_k_latent_loss(const float* pred, const float* target, const float* lr, float* dpred, float* out6,
-                                 int32_t rows, int32_t T, double latent_weight, double freq_weight, double ms_weight,
-                                 double consistency_weight, double low_freq_phase_ratio, double strict_cutoff,
-                                 double soft_cutoff, float loss_scale, void* work, size_t work_bytes, void* stream) {
+// body of jat_k_latent_loss / jat_k_latent_loss_ex; `work` holds align_up(T*8, 256) + rows*32 bytes
+static int k_latent_loss(const float* pred, const float* target, const float* lr, float* dpred, float* out6, int32_t rows, int32_t T,
+                         double recon_eps, double recon_weight, double latent_weight, double freq_weight, double ms_weight,
+                         double consistency_weight, double low_freq_phase_ratio, double strict_cutoff, double soft_cutoff,
+                         float loss_scale, void* work, size_t work_bytes, void* stream) {
   if (!pred || !target || !dpred || !out6 || !work || rows <= 0 || T <= 0) return fail(JAT_E_INVALID, "bad argument");
   // what launch_latent_loss would reject, before anything is copied or launched
   if (!(low_freq_phase_ratio >= 0 && low_freq_phase_ratio <= 1 && strict_cutoff >= 0 && soft_cutoff >= strict_cutoff &&
@@ -851,8 +875,35 @@ extern "C" int jat_k_latent_loss(const float* pred, const float* target, const f
   const int F = T / 2 + 1;
   KCHK(launch_latent_loss(pred, target, lr, tw, dpred, part, out6, rows, T, (float)latent_weight, (float)freq_weight,
                           (float)ms_weight, (float)consistency_weight, (int)((double)F * low_freq_phase_ratio),
-                          (int)((double)F * strict_cutoff), (int)((double)F * soft_cutoff), loss_scale, s));
+                          (int)((double)F * strict_cutoff), (int)((double)F * soft_cutoff), (float)recon_eps,
+                          (float)recon_weight, loss_scale, s));
   return JAT_OK;
+}
+
+// per-kernel entry point (unit parity): the v3mod2 loss on [rows, T] tensors
+extern "C" int jat_k_latent_loss(const float* pred, const float* target, const float* lr, float* dpred, float* out6,
+                                 int32_t rows, int32_t T, double latent_weight, double freq_weight, double ms_weight,
+                                 double consistency_weight, double low_freq_phase_ratio, double strict_cutoff,
+                                 double soft_cutoff, float loss_scale, void* work, size_t work_bytes, void* stream) {
+  return k_latent_loss(pred, target, lr, dpred, out6, rows, T, 0.0, 1.0, latent_weight, freq_weight, ms_weight, consistency_weight,
+                       low_freq_phase_ratio, strict_cutoff, soft_cutoff, loss_scale, work, work_bytes, stream);
+}
+
+// the same with the v3mod3 reconstruction term (train_ddp_v3mod3.py:955-969): recon_weight * recon + latent_weight * (...), recon =
+// Charbonnier(recon_eps) for recon_eps > 0, MSE for 0; out6[1] = the un-weighted recon term.  (0, 1) is jat_k_latent_loss, kernel
+// for kernel.  Same work buffer and the same rejections before anything is launched.
+extern "C" int jat_k_latent_loss_ex(const float* pred, const float* target, const float* lr, float* dpred, float* out6,
+                                    int32_t rows, int32_t T, double recon_eps, double recon_weight, double latent_weight,
+                                    double freq_weight, double ms_weight, double consistency_weight,
+                                    double low_freq_phase_ratio, double strict_cutoff, double soft_cutoff, float loss_scale,
+                                    void* work, size_t work_bytes, void* stream) {
+  if (!(recon_eps >= 0.0) || !std::isfinite(recon_eps) || (recon_eps > 0.0 && (float)recon_eps == 0.f))
+    return fail(JAT_E_INVALID, "recon_eps must be finite and >= 0 (0 selects the MSE loss) and, if positive, not below fp32's range");
+  if (!std::isfinite(recon_weight) || !std::isfinite(latent_weight) || !std::isfinite(freq_weight) || !std::isfinite(ms_weight) ||
+      !std::isfinite(consistency_weight))
+    return fail(JAT_E_INVALID, "loss weights must be finite");
+  return k_latent_loss(pred, target, lr, dpred, out6, rows, T, recon_eps, recon_weight, latent_weight, freq_weight, ms_weight,
+                       consistency_weight, low_freq_phase_ratio, strict_cutoff, soft_cutoff, loss_scale, work, work_bytes, stream);
 }
 
 // ---- per-kernel entry points of the training step (unit parity against fp64 references; include/jat_hip.h) ------------

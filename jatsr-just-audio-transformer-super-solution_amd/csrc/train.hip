@@ -887,21 +887,21 @@ __global__ void __launch_bounds__(256) charbonnier_grad_kernel(const float* __re
 }
 constexpr int RED_BLOCKS = 1024;
 int train_red_blocks() { return RED_BLOCKS; }
-hipError_t launch_charbonnier_grad(const float* pred, const float* target, float* dpred, float* part, float* loss2, int64_t n,
-                                   float eps, float loss_scale, hipStream_t s);
+// rw (the v3mod3 trainer's reconstruction_weight) is host arithmetic on both launchers: it multiplies the gradient scale and the
+// scale of the finished sum, so the kernels are the same for every weight and rw = 1 gives the bits it gave without it
 hipError_t launch_mse_grad(const float* pred, const float* target, float* dpred, float* part, float* loss2, int64_t n,
-                           float loss_scale, hipStream_t s) {
+                           float loss_scale, float rw, hipStream_t s) {
   hipLaunchKernelGGL(mse_grad_kernel, dim3(RED_BLOCKS), dim3(256), 0, s, pred, target, dpred, part, n,
-                     2.0f * loss_scale / (float)n);
-  hipLaunchKernelGGL(finish_sum_kernel, dim3(1), dim3(256), 0, s, part, RED_BLOCKS, 1.0f / (float)n, loss2);
+                     2.0f * loss_scale / (float)n * rw);
+  hipLaunchKernelGGL(finish_sum_kernel, dim3(1), dim3(256), 0, s, part, RED_BLOCKS, 1.0f / (float)n * rw, loss2);
   return hipGetLastError();
 }
 
 hipError_t launch_charbonnier_grad(const float* pred, const float* target, float* dpred, float* part, float* loss2, int64_t n,
-                                   float eps, float loss_scale, hipStream_t s) {
+                                   float eps, float loss_scale, float rw, hipStream_t s) {
   hipLaunchKernelGGL(charbonnier_grad_kernel, dim3(RED_BLOCKS), dim3(256), 0, s, pred, target, dpred, part, n, eps,
-                     loss_scale / (float)n);
-  hipLaunchKernelGGL(finish_sum_kernel, dim3(1), dim3(256), 0, s, part, RED_BLOCKS, 1.0f / (float)n, loss2);
+                     loss_scale / (float)n * rw);
+  hipLaunchKernelGGL(finish_sum_kernel, dim3(1), dim3(256), 0, s, part, RED_BLOCKS, 1.0f / (float)n * rw, loss2);
   return hipGetLastError();
 }
 
@@ -1269,6 +1269,9 @@ hipError_t launch_multi_copy(const CopyJob* jobs_dev, int njobs, hipStream_t s) 
 
 // ---- v3mod2 training loss: MSE + latent perceptual loss (train_ddp_v3mod2.py:53-321, 889-896) ------------------------------
 //   loss = mse + lw * (fw * freq + mw * ms + cw * cons)
+// and the v3mod3 trainer's (train_ddp_v3mod3.py:57-85, 955-969), reconstruction mode RECON_GENERAL of the same kernels:
+//   loss = rw * recon + lw * (...),  recon = mean sqrt((p - h)^2 + eps) for eps > 0 (eps is ADDED to the squared difference),
+//                                            mse for eps == 0
 //   freq = mean|log(|P|+1e-7) - log(|H|+1e-7)| + 0.1 * mean_{k<low}|P - H|                 (:97-123)   P, H, R = rfft over T
 //   ms   = (mean|p-h| + mean|pool2(p)-pool2(h)| + mean|pool4(p)-pool4(h)|) / 3             (:158-171)  of pred, target, clean LR
 //   cons = mean_{k<strict}|P - R| + mean_{strict<=k<soft} w_k ||P| - |R||, w = linspace(1,0) (:229-262)
@@ -1276,17 +1279,73 @@ hipError_t launch_multi_copy(const CopyJob* jobs_dev, int njobs, hipStream_t s) 
 // the spectra are direct fp32 DFTs against an exact twiddle table (cos, sin of 2 pi m / T, m < T, index k*n mod T kept
 // incrementally), and the gradient is the adjoint sum  dp_n = Re sum_k g_k e^{+i 2 pi k n / T}  over the rfft bins.
 // Bound: fp32 VALU (8 FMA per (k, n) pair).  Loss terms: per-row partials, finished in fixed order.
+// Reconstruction term of the loss kernels, a compile-time mode carried by the argument type.  RECON_MSE1 (LatentLossArgs): mse
+// with weight 1, the v3mod2 loss; its kernels take the arguments they always took.  RECON_GENERAL (LatentLossArgsEx, two more
+// floats): rw * Charbonnier(eps) for eps > 0, rw * mse for eps == 0.
+enum { RECON_MSE1 = 0, RECON_GENERAL = 1 };
 struct LatentLossArgs {
+  static constexpr int RM = RECON_MSE1;
   const float *pred, *target, *lr;   // [rows, T]; lr = clean normalised condition (may be null when cw == 0)
   const float2* tw;                  // [T] (cos, sin)(2 pi m / T)
   float* dpred;                      // [rows, T]   d(total loss * gscale)/d pred
-  float* part;                       // [rows, 8] partial sums: se, logmag, low, l1, l1p2, l1p4, strict, trans
+  float* part;                       // [rows, 8] partial sums: recon (se, or the Charbonnier sum), logmag, low, l1, l1p2, l1p4, strict, trans
   int rows, T, F, low, strict, soft;
   float lw, fw, mw, cw, gscale;      // weights; gscale = loss_scale
   float inv_n;                       // 1 / (rows * T)
 };
-template <int FB, int NB>   // bins / samples per thread of the blocked DFT loops (the launcher picks the smallest cover)
-__global__ void __launch_bounds__(256) latent_loss_kernel(const LatentLossArgs a) {
+struct LatentLossArgsEx : LatentLossArgs {
+  static constexpr int RM = RECON_GENERAL;
+  float rw, eps;                     // weight of the reconstruction term; Charbonnier eps (0: mse)
+};
+template <class A> __device__ __forceinline__ float recon_weight_of(const A& a) {
+  if constexpr (A::RM == RECON_GENERAL) return a.rw; else return 1.0f;
+}
+template <class A> __device__ __forceinline__ float recon_eps_of(const A& a) {
+  if constexpr (A::RM == RECON_GENERAL) return a.eps; else return 0.f;
+}
+// time-domain terms of sample n (reconstruction, multi-scale L1) and the output gradient
+//   dpred = gscale * rw * d recon / d pred * inv_n + lw * gscale * (s + mw * gt / 3);   acc[0] += the un-weighted recon term
+template <int RM>
+__device__ __forceinline__ void time_terms(const LatentLossArgs& a, const float* sp, const float* sh, int n, float s, int64_t row,
+                                           float* acc, float rw, float eps) {
+  const int T = a.T, T2 = T / 2, T4 = T / 4;
+  const float rows_f = (float)a.rows;
+  const float e = sp[n] - sh[n];
+  float dr = 0.f;            // RECON_GENERAL: d recon / d pred of this sample, before the 1 / n
+  if constexpr (RM == RECON_MSE1) {
+    acc[0] += e * e;
+  } else if (eps > 0.f) {    // as charbonnier_grad_kernel
+    const float r = sqrtf(e * e + eps);
+    acc[0] += r;
+    dr = e / r;
+  } else {
+    acc[0] += e * e;
+    dr = 2.0f * e;
+  }
+  acc[3] += fabsf(e);
+  float gt = (e > 0.f ? 1.f : (e < 0.f ? -1.f : 0.f)) * a.inv_n;
+  if (n < 2 * T2) {
+    const int j = n >> 1;
+    const float q = 0.5f * ((sp[2 * j] - sh[2 * j]) + (sp[2 * j + 1] - sh[2 * j + 1]));
+    if ((n & 1) == 0) acc[4] += fabsf(q);
+    gt += (q > 0.f ? 1.f : (q < 0.f ? -1.f : 0.f)) * 0.5f / (rows_f * T2);
+  }
+  if (n < 4 * T4) {
+    const int j = n >> 2;
+    float q = 0.f;
+#pragma unroll
+    for (int u = 0; u < 4; ++u) q += sp[4 * j + u] - sh[4 * j + u];
+    q *= 0.25f;
+    if ((n & 3) == 0) acc[5] += fabsf(q);
+    gt += (q > 0.f ? 1.f : (q < 0.f ? -1.f : 0.f)) * 0.25f / (rows_f * T4);
+  }
+  if constexpr (RM == RECON_MSE1)
+    a.dpred[row * T + n] = a.gscale * 2.0f * e * a.inv_n + a.lw * a.gscale * (s + a.mw * gt * (1.0f / 3.0f));
+  else
+    a.dpred[row * T + n] = a.gscale * rw * dr * a.inv_n + a.lw * a.gscale * (s + a.mw * gt * (1.0f / 3.0f));
+}
+template <int FB, int NB, class A>   // bins / samples per thread of the blocked DFT loops (the launcher picks the smallest cover)
+__global__ void __launch_bounds__(256) latent_loss_kernel(const A a) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int T = a.T, F = a.F, tid = threadIdx.x;
   constexpr int RS = 8;    // twiddle re-seed interval (see the forward loop)
@@ -1435,6 +1494,12 @@ __global__ void __launch_bounds__(256) latent_loss_kernel(const LatentLossArgs a
   for (int j = 0; j < NB; ++j) {
     const int n = nbase + tid + 256 * j;
     if (n >= T) continue;
+    if constexpr (A::RM != RECON_MSE1) {
+      time_terms<A::RM>(a, sp, sh, n, sv[j], row, acc, recon_weight_of(a), recon_eps_of(a));
+      continue;
+    }
+    // RECON_MSE1: the statements of time_terms<RECON_MSE1> in the form this kernel has always had them (lam hoisted), so that the
+    // v3mod2 loss keeps its instruction stream; a change to the time-domain terms goes to both places
     const float s = sv[j];
     const float e = sp[n] - sh[n];
     acc[0] += e * e;
@@ -1505,33 +1570,8 @@ __device__ __forceinline__ float2 spectral_terms(const LatentLossArgs& a, const 
   }
   return float2{ga, gb};
 }
-// time-domain terms of sample n (MSE, multi-scale L1) and the output gradient
-__device__ __forceinline__ void time_terms(const LatentLossArgs& a, const float* sp, const float* sh, int n, float s, int64_t row,
-                                           float* acc) {
-  const int T = a.T, T2 = T / 2, T4 = T / 4;
-  const float rows_f = (float)a.rows;
-  const float e = sp[n] - sh[n];
-  acc[0] += e * e;
-  acc[3] += fabsf(e);
-  float gt = (e > 0.f ? 1.f : (e < 0.f ? -1.f : 0.f)) * a.inv_n;
-  if (n < 2 * T2) {
-    const int j = n >> 1;
-    const float q = 0.5f * ((sp[2 * j] - sh[2 * j]) + (sp[2 * j + 1] - sh[2 * j + 1]));
-    if ((n & 1) == 0) acc[4] += fabsf(q);
-    gt += (q > 0.f ? 1.f : (q < 0.f ? -1.f : 0.f)) * 0.5f / (rows_f * T2);
-  }
-  if (n < 4 * T4) {
-    const int j = n >> 2;
-    float q = 0.f;
-#pragma unroll
-    for (int u = 0; u < 4; ++u) q += sp[4 * j + u] - sh[4 * j + u];
-    q *= 0.25f;
-    if ((n & 3) == 0) acc[5] += fabsf(q);
-    gt += (q > 0.f ? 1.f : (q < 0.f ? -1.f : 0.f)) * 0.25f / (rows_f * T4);
-  }
-  a.dpred[row * T + n] = a.gscale * 2.0f * e * a.inv_n + a.lw * a.gscale * (s + a.mw * gt * (1.0f / 3.0f));
-}
-__global__ void __launch_bounds__(256) latent_loss_fft_kernel(const LatentLossArgs a, int N1, int N2) {
+template <class A>
+__global__ void __launch_bounds__(256) latent_loss_fft_kernel(const A a, int N1, int N2) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int T = a.T, F = a.F, tid = threadIdx.x, N1h = N1 / 2 + 1;
   float* sp = sm;
@@ -1635,7 +1675,7 @@ __global__ void __launch_bounds__(256) latent_loss_fft_kernel(const LatentLossAr
       sv += z.x * w.x - z.y * w.y;
       idx += step; if (idx >= T) idx -= T;
     }
-    time_terms(a, sp, sh, n, sv, row, acc);
+    time_terms<A::RM>(a, sp, sh, n, sv, row, acc, recon_weight_of(a), recon_eps_of(a));
   }
 #pragma unroll
   for (int i = 0; i < 8; ++i) acc[i] = wave_sum_t(acc[i]);
@@ -1645,8 +1685,10 @@ __global__ void __launch_bounds__(256) latent_loss_fft_kernel(const LatentLossAr
   __syncthreads();
   if (tid < 8) a.part[row * 8 + tid] = red[tid] + red[8 + tid] + red[16 + tid] + red[24 + tid];
 }
-// out[0] = total, [1] = mse, [2] = freq, [3] = ms, [4] = cons, [5] = fw*freq + mw*ms + cw*cons
-__global__ void __launch_bounds__(256) latent_loss_finish_kernel(const float* __restrict__ part, const LatentLossArgs a,
+// out[0] = total, [1] = recon (mse or Charbonnier, un-weighted), [2] = freq, [3] = ms, [4] = cons, [5] = fw*freq + mw*ms + cw*cons;
+// total = recon + lw * [5] (RECON_MSE1) or rw * recon + lw * [5] (RECON_GENERAL)
+template <class A>
+__global__ void __launch_bounds__(256) latent_loss_finish_kernel(const float* __restrict__ part, const A a,
                                                                  float* __restrict__ out) {
   __shared__ double red[8][256];
   double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -1664,14 +1706,16 @@ __global__ void __launch_bounds__(256) latent_loss_finish_kernel(const float* __
   }
   if (threadIdx.x == 0) {
     const double rows = a.rows, T = a.T, n = rows * T;
-    const double mse = red[0][0] / n;
+    const double mse = red[0][0] / n;   // the reconstruction mean, whatever its kind
     const double freq = red[1][0] / (rows * a.F) + (a.low > 0 ? 0.1 * red[2][0] / (rows * a.low) : 0.0);
     const int T2 = a.T / 2, T4 = a.T / 4;
     const double ms = (red[3][0] / n + (T2 > 0 ? red[4][0] / (rows * T2) : 0.0) + (T4 > 0 ? red[5][0] / (rows * T4) : 0.0)) / 3.0;
     const int bw = a.soft - a.strict;
     const double cons = (a.strict > 0 ? red[6][0] / (rows * a.strict) : 0.0) + (bw > 0 ? red[7][0] / (rows * bw) : 0.0);
     const double lat = a.fw * freq + a.mw * ms + a.cw * cons;
-    out[0] = (float)(mse + a.lw * lat); out[1] = (float)mse; out[2] = (float)freq; out[3] = (float)ms;
+    if constexpr (A::RM == RECON_MSE1) out[0] = (float)(mse + a.lw * lat);
+    else out[0] = (float)((double)recon_weight_of(a) * mse + a.lw * lat);
+    out[1] = (float)mse; out[2] = (float)freq; out[3] = (float)ms;
     out[4] = (float)cons; out[5] = (float)lat;
   }
 }
@@ -1707,29 +1751,21 @@ LatentLossPlan plan_latent_loss(int T) {
   else { pl.a = 3; pl.b = 6; }
   return pl;
 }
-hipError_t launch_latent_loss(const float* pred, const float* target, const float* lr, const float2* tw, float* dpred,
-                              float* part, float* out6, int rows, int T, float lw, float fw, float mw, float cw, int low,
-                              int strict, int soft, float loss_scale, hipStream_t s) {
-  LatentLossArgs a;
-  a.pred = pred; a.target = target; a.lr = lr; a.tw = tw; a.dpred = dpred; a.part = part;
-  a.rows = rows; a.T = T; a.F = T / 2 + 1;
-  a.low = low; a.strict = strict; a.soft = soft;
-  if (low < 0 || low > a.F || strict < 0 || soft < strict || soft > a.F) return hipErrorInvalidValue;
-  a.lw = lw; a.fw = fw; a.mw = mw; a.cw = cw; a.gscale = loss_scale;
-  a.inv_n = 1.0f / ((float)rows * (float)T);
-  const LatentLossPlan pl = plan_latent_loss(T);
-  if (pl.kind == 0) return hipErrorInvalidValue;
+// One launch of the loss with argument type A (= reconstruction mode); the plan, the LDS sizes and the geometry do not depend on it.
+template <class A>
+static hipError_t launch_latent_loss_mode(const A& a, const LatentLossPlan& pl, float* out6, hipStream_t s) {
+  const int rows = a.rows;
   if (pl.kind == 2) {
     const int N1 = pl.a, N2 = pl.b;
     const size_t lds2 = pl.lds;
     static size_t attr2 = 0;
     if (lds2 > attr2) {
-      hipError_t e = hipFuncSetAttribute((const void*)latent_loss_fft_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
+      hipError_t e = hipFuncSetAttribute((const void*)latent_loss_fft_kernel<A>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
       if (e != hipSuccess) return e;
       attr2 = lds2;
     }
-    hipLaunchKernelGGL(latent_loss_fft_kernel, dim3(rows), dim3(256), lds2, s, a, N1, N2);
-    hipLaunchKernelGGL(latent_loss_finish_kernel, dim3(1), dim3(256), 0, s, part, a, out6);
+    hipLaunchKernelGGL(latent_loss_fft_kernel<A>, dim3(rows), dim3(256), lds2, s, a, N1, N2);
+    hipLaunchKernelGGL(latent_loss_finish_kernel<A>, dim3(1), dim3(256), 0, s, a.part, a, out6);
     return hipGetLastError();
   }
   const size_t lds = pl.lds;
@@ -1737,17 +1773,36 @@ hipError_t launch_latent_loss(const float* pred, const float* target, const floa
   {                                                                                                                    \
     static size_t attr_set = 0;                                                                                        \
     if (lds > attr_set) {                                                                                              \
-      hipError_t e = hipFuncSetAttribute((const void*)latent_loss_kernel<FBv, NBv>,                                    \
+      hipError_t e = hipFuncSetAttribute((const void*)latent_loss_kernel<FBv, NBv, A>,                                 \
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                        \
       if (e != hipSuccess) return e;                                                                                   \
       attr_set = lds;                                                                                                  \
     }                                                                                                                  \
-    hipLaunchKernelGGL((latent_loss_kernel<FBv, NBv>), dim3(rows), dim3(256), lds, s, a);                              \
+    hipLaunchKernelGGL((latent_loss_kernel<FBv, NBv, A>), dim3(rows), dim3(256), lds, s, a);                           \
   }
   if (pl.a == 1) LL_CASE(1, 2)
   else if (pl.a == 2) LL_CASE(2, 4)
   else LL_CASE(3, 6)   // larger T: the kernel loops in chunks of 256 * FB bins / 256 * NB samples
 #undef LL_CASE
-  hipLaunchKernelGGL(latent_loss_finish_kernel, dim3(1), dim3(256), 0, s, part, a, out6);
+  hipLaunchKernelGGL(latent_loss_finish_kernel<A>, dim3(1), dim3(256), 0, s, a.part, a, out6);
   return hipGetLastError();
+}
+// recon_eps == 0 and recon_weight == 1 (the v3mod2 loss, mse + lw * latent) go to the RECON_MSE1 instances; anything else to
+// RECON_GENERAL.  The plan, the LDS sizes and the launch geometry are the same for both.
+hipError_t launch_latent_loss(const float* pred, const float* target, const float* lr, const float2* tw, float* dpred,
+                              float* part, float* out6, int rows, int T, float lw, float fw, float mw, float cw, int low,
+                              int strict, int soft, float recon_eps, float recon_weight, float loss_scale, hipStream_t s) {
+  LatentLossArgsEx a;
+  a.pred = pred; a.target = target; a.lr = lr; a.tw = tw; a.dpred = dpred; a.part = part;
+  a.rows = rows; a.T = T; a.F = T / 2 + 1;
+  a.low = low; a.strict = strict; a.soft = soft;
+  if (low < 0 || low > a.F || strict < 0 || soft < strict || soft > a.F) return hipErrorInvalidValue;
+  if (!(recon_eps >= 0.f) || !(recon_weight == recon_weight)) return hipErrorInvalidValue;
+  a.lw = lw; a.fw = fw; a.mw = mw; a.cw = cw; a.gscale = loss_scale;
+  a.inv_n = 1.0f / ((float)rows * (float)T);
+  const LatentLossPlan pl = plan_latent_loss(T);
+  if (pl.kind == 0) return hipErrorInvalidValue;
+  a.rw = recon_weight; a.eps = recon_eps;
+  if (recon_eps == 0.f && recon_weight == 1.0f) return launch_latent_loss_mode<LatentLossArgs>(a, pl, out6, s);   // the base slice
+  return launch_latent_loss_mode<LatentLossArgsEx>(a, pl, out6, s);
 }

@@ -1,5 +1,6 @@
 """Training run on MI355X — one rank of reference `train_ddp_v3mod2.py:main` (:603-1018), or of `train_ddp_v3m2.py` /
-`train_ddp_v3m2mod1.py` by flag (`--model v3 --latent-loss-weight 0 [--loss charbonnier]`).
+`train_ddp_v3m2mod1.py` by flag (`--model v3 --latent-loss-weight 0 [--loss charbonnier]`), or of `train_ddp_v3mod3.py`
+(`--loss charbonnier_latent`: Charbonnier + latent perceptual loss with configurable weights).
 
     python -m jatsr_amd.fit --data-dir data_processed_v13_final --save-dir-base checkpoints/v3mod2_full_run
     python -m jatsr_amd.fit --data-dir ... --resume                 # newest run folder; --resume PATH for a given file
@@ -25,8 +26,11 @@ DEFAULTS = dict(seed=42, data_dir="data_processed_v13_final", stats_file="global
                 batch_size=28, lr=5e-5, weight_decay=0.1, warmup_steps=1000, epochs=300, grad_clip=1.0,
                 condition_noise_ratio=0.05, latent_loss_weight=0.3, dropout=0.1, drop_path_rate=0.05,
                 save_dir_base="checkpoints/v3mod2_full_run", save_interval_steps=1000, samples_per_epoch_multiplier=6,
-                log_interval=10)
+                log_interval=10,
+                # train_ddp_v3mod3.py:408-422
+                reconstruction_weight=1.0, charbonnier_eps=1e-6, freq_loss_weight=0.5, ms_loss_weight=0.5, consistency_weight=0.1)
 MODEL_DIMS = ("input_channels", "patch_len", "hidden_size", "depth", "num_q_heads", "num_kv_heads", "bottleneck_dim", "mlp_ratio")
+CHARBONNIER_TAG = "Train/Charbonnier_Loss"      # in place of Train/MSE_Loss with a Charbonnier loss (train_ddp_v3mod3.py:1030-1032)
 TRAIN_TAGS = {"mse": "Train/MSE_Loss", "freq": "Train/LatentPerc_FreqLoss", "ms": "Train/LatentPerc_MSLoss",
               "consistency": "Train/LatentPerc_ConsistencyLoss", "latent": "Train/LatentPerc_TotalLoss"}
 EMA_VAL_TAGS = {"mse_loss": "Val/EMA_MSE_Loss", "freq_loss": "Val/EMA_LatentPerc_FreqLoss", "ms_loss": "Val/EMA_LatentPerc_MSLoss",
@@ -75,7 +79,15 @@ def build_parser():
     p.add_argument("--condition-noise-ratio", type=float, default=d["condition_noise_ratio"])
     p.add_argument("--no-adaptive-noise", dest="use_adaptive_noise", action="store_false")
     p.add_argument("--latent-loss-weight", type=float, default=d["latent_loss_weight"], help="0: MSE only (train_ddp_v3m2.py)")
-    p.add_argument("--loss", default="mse", help="mse or charbonnier (train_ddp_v3m2mod1.py; needs --latent-loss-weight 0)")
+    p.add_argument("--loss", default="mse",
+                   help="mse, charbonnier (train_ddp_v3m2mod1.py; needs --latent-loss-weight 0) or charbonnier_latent "
+                        "(train_ddp_v3mod3.py: Charbonnier + latent perceptual loss)")
+    p.add_argument("--reconstruction-weight", type=float, default=d["reconstruction_weight"],
+                   help="weight of the MSE / Charbonnier term (train_ddp_v3mod3.py:416)")
+    p.add_argument("--charbonnier-eps", type=float, default=d["charbonnier_eps"], help="added to the squared difference (:409)")
+    p.add_argument("--freq-loss-weight", type=float, default=d["freq_loss_weight"], help="inside the latent perceptual loss (:420)")
+    p.add_argument("--ms-loss-weight", type=float, default=d["ms_loss_weight"], help="inside the latent perceptual loss (:421)")
+    p.add_argument("--consistency-weight", type=float, default=d["consistency_weight"], help="inside the latent perceptual loss (:422)")
     p.add_argument("--ema-decay", type=float, default=None,
                    help="keep an exponential moving average of the weights with this decay (e.g. 0.9999): validated beside the "
                         "raw weights, stored in every checkpoint (infer --ema samples from it); default: none")
@@ -160,7 +172,13 @@ def build_trainer(args, model, total_steps, process_group=None, rank=0, distribu
                    warmup_steps=args.warmup_steps, total_steps=total_steps, process_group=process_group,
                    seed=args.seed + rank, latent_loss_weight=args.latent_loss_weight, distributed=distributed,
                    amp_dtype=args.amp_dtype, loss=args.loss, ema_decay=args.ema_decay, ema_warmup=args.ema_warmup,
-                   grad_accum_steps=getattr(args, "grad_accum_steps", 1))
+                   grad_accum_steps=getattr(args, "grad_accum_steps", 1), **_loss_keywords(args))
+
+
+def _loss_keywords(args):
+    """The loss flags a namespace carries as Trainer keywords (one written before the flags existed: Trainer's defaults)."""
+    names = ("reconstruction_weight", "charbonnier_eps", "freq_loss_weight", "ms_loss_weight", "consistency_weight")
+    return {k: getattr(args, k) for k in names if hasattr(args, k)}
 
 
 def loop_step(trainer, store, plans, i, stats, lr, monitor):
@@ -219,11 +237,10 @@ def run(args):
     from . import _lib as L
     from . import io as jio
     from .data import LatentStore, epoch_batches, train_batch_plan, val_batch_plan
-    from .train import get_lr
-    if args.loss not in ("mse", "charbonnier"):       # before any device memory is taken; Trainer checks again
-        raise ValueError(f"loss must be 'mse' or 'charbonnier', got {args.loss!r}")
-    if args.loss == "charbonnier" and args.latent_loss_weight != 0.0:
-        raise ValueError("--loss charbonnier needs --latent-loss-weight 0 (train_ddp_v3m2mod1.py has no latent term)")
+    from .train import check_loss_arguments, get_lr
+    kw = _loss_keywords(args)                         # before any device memory is taken; Trainer checks again
+    check_loss_arguments(args.loss, args.latent_loss_weight, kw.get("reconstruction_weight", 1.0), kw.get("charbonnier_eps", 1e-6),
+                         tuple(kw.get(k, 0.0) for k in ("freq_loss_weight", "ms_loss_weight", "consistency_weight")))
     accum = int(getattr(args, "grad_accum_steps", 1))
     steps_per_epoch(0, accum)                         # rejects a count below 1
     L.require_gpu()
@@ -317,6 +334,8 @@ def run(args):
                 if args.latent_loss_weight != 0.0:
                     terms = trainer.loss_terms()
                     rec.update({tag: terms[k] for k, tag in TRAIN_TAGS.items()})
+                    if args.loss != "mse":
+                        rec[CHARBONNIER_TAG] = rec.pop(TRAIN_TAGS["mse"])
                 log(rec)
                 if master:
                     print(f"epoch {epoch} step {g}: loss {out['loss']:.5f} lr {lr_now:.2e} grad norm {out['grad_norm']:.3f}")

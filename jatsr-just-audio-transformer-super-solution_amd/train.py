@@ -154,6 +154,26 @@ def _check_norm_batch(x, device):
     return x.contiguous()
 
 
+LOSSES = ("mse", "charbonnier", "charbonnier_latent")
+
+
+def check_loss_arguments(loss, latent_loss_weight, reconstruction_weight=1.0, charbonnier_eps=1e-6, sub_weights=()):
+    """The argument errors of a loss selection, raised as ValueError before anything touches the GPU (`Trainer`, `fit.run`)."""
+    if loss not in LOSSES:
+        raise ValueError(f"loss must be 'mse', 'charbonnier' or 'charbonnier_latent', got {loss!r}")
+    weights = (latent_loss_weight, reconstruction_weight) + tuple(sub_weights)
+    if not all(math.isfinite(float(w)) for w in weights):
+        raise ValueError(f"loss weights must be finite, got {weights!r}")
+    if loss == "charbonnier" and float(latent_loss_weight) != 0.0:
+        raise ValueError("loss='charbonnier' is the Charbonnier trainer (train_ddp_v3m2mod1.py), which has no latent term: "
+                         "use loss='charbonnier_latent' (train_ddp_v3mod3.py) for Charbonnier + latent perceptual loss, or "
+                         "latent_loss_weight=0")
+    if loss == "charbonnier_latent" and float(latent_loss_weight) == 0.0:
+        raise ValueError("loss='charbonnier_latent' needs latent_loss_weight != 0; the Charbonnier loss alone is loss='charbonnier'")
+    if loss == "charbonnier_latent" and not (math.isfinite(float(charbonnier_eps)) and float(charbonnier_eps) > 0.0):
+        raise ValueError(f"charbonnier_eps must be finite and > 0, got {charbonnier_eps!r}")
+
+
 class Trainer:
     """One rank of the reference training loop.  Hyper-parameter names and defaults are TrainConfig's
     (train_ddp_v3m2.py:55-101)."""
@@ -164,13 +184,20 @@ class Trainer:
                  latent_loss_weight=0.0, freq_loss_weight=0.5, ms_loss_weight=0.5, consistency_weight=0.1,
                  low_freq_phase_ratio=0.3, strict_cutoff=0.30, soft_cutoff=0.36, overlap_grad_allreduce=True,
                  distributed=True, amp_dtype=None, loss="mse", charbonnier_eps=1e-6, ema_decay=None, ema_warmup=True,
-                 grad_accum_steps=1):
+                 grad_accum_steps=1, reconstruction_weight=1.0):
         """latent_loss_weight > 0 selects the v3mod2 trainer's loss, MSE + latent perceptual loss
         (train_ddp_v3mod2.py:53-321,362-372,889-896; its TrainConfig uses 0.3 with the other defaults given here, no CFG
         dropout and condition_noise_ratio 0.05); 0 is the MSE-only loss of train_ddp_v3m2.py:585.
         loss: "mse" (F.mse_loss, train_ddp_v3m2.py:585) or "charbonnier" — the V3M2-MOD1 trainer's reconstruction loss
         mean(sqrt((pred - target)^2 + charbonnier_eps)) (train_ddp_v3m2mod1.py:72-101, `use_charbonnier_loss` / `charbonnier_eps`
-        :150-151), used for the training step and for validation (:817-819); not combinable with the latent perceptual loss.
+        :150-151), used for the training step and for validation (:817-819); not combinable with the latent perceptual loss
+        under this name.  "charbonnier_latent" — the V3-MOD3 trainer's loss (train_ddp_v3mod3.py:57-85,400-434,955-969; validation
+        :1138-1159): reconstruction_weight * charbonnier(pred, target, charbonnier_eps) + latent_loss_weight * latent perceptual
+        loss, the Charbonnier term computed inside the latent loss kernels; needs latent_loss_weight != 0 (its TrainConfig uses 0.3
+        with the sub-weights given here).
+        reconstruction_weight: weight of the reconstruction term of any of the three (train_ddp_v3mod3.py:416); with loss="mse"
+        and a latent weight this is the V3-MOD3 trainer with use_charbonnier_loss = False.  `loss_terms()` and the validation
+        metrics report the reconstruction term un-weighted.
         distributed=False: never issue a collective even if a process group exists (a single rank timing a local step).
         ema_decay: keep an exponential moving average of the weights (the reference keeps none), updated inside the AdamW
         pass: `ema`, a fifth flat buffer, `ema_weights()` to run on it, `ema_state_dict()` to read it.  ema_warmup: the
@@ -188,11 +215,8 @@ class Trainer:
         choice (JAT_OPERAND_DTYPE=fp16 loads libjat_hip_fp16.so).  None: whatever the library is."""
         # argument errors first: nothing below (the release of the model's previous trainer, 15-28 GB of new workspace) has
         # happened when a mistyped flag is reported
-        if loss not in ("mse", "charbonnier"):
-            raise ValueError(f"loss must be 'mse' or 'charbonnier', got {loss!r}")
-        if loss == "charbonnier" and float(latent_loss_weight) != 0.0:
-            raise ValueError("the latent perceptual loss is defined on top of the MSE loss (train_ddp_v3mod2.py:889-896); "
-                             "the Charbonnier trainer (train_ddp_v3m2mod1.py) has no latent term")
+        check_loss_arguments(loss, latent_loss_weight, reconstruction_weight, charbonnier_eps,
+                             (freq_loss_weight, ms_loss_weight, consistency_weight))
         if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
             raise ValueError(f"ema_decay must be in [0, 1), got {ema_decay!r}")
         if int(grad_accum_steps) != grad_accum_steps or int(grad_accum_steps) < 1:
@@ -276,8 +300,14 @@ class Trainer:
                                 low_freq_phase_ratio=float(low_freq_phase_ratio), strict_cutoff=float(strict_cutoff),
                                 soft_cutoff=float(soft_cutoff))
         self.loss, self.charbonnier_eps = loss, float(charbonnier_eps)
-        L.check(L.lib().jat_trainer_set_latent_loss(self.ptr, *self.latent_loss.values()))
-        L.check(L.lib().jat_trainer_set_charbonnier(self.ptr, self.charbonnier_eps if loss == "charbonnier" else 0.0))
+        self.reconstruction_weight = float(reconstruction_weight)
+        self.recon_eps = self.charbonnier_eps if loss != "mse" else 0.0      # what the library is given: 0 selects MSE
+        if loss == "charbonnier_latent" or self.reconstruction_weight != 1.0:
+            L.check(L.lib().jat_trainer_set_loss_ex(self.ptr, self.recon_eps, self.reconstruction_weight,
+                                                    *self.latent_loss.values()))
+        else:
+            L.check(L.lib().jat_trainer_set_latent_loss(self.ptr, *self.latent_loss.values()))
+            L.check(L.lib().jat_trainer_set_charbonnier(self.ptr, self.recon_eps))
         self._terms = torch.zeros(6, dtype=torch.float32, device=dev)
         # moving average of the weights: taken after the broadcast above, so every rank starts from the same copy and, as all
         # ranks apply the same all-reduced step, stays equal without a collective of its own
@@ -331,14 +361,18 @@ class Trainer:
         self._covered += n
 
     def loss_terms(self):
-        """{total, mse, freq, ms, consistency, latent} of the latest step (the trainer's `latent_loss_dict`,
-        train_ddp_v3mod2.py:313-318); MSE-only trainers return {total}.  With grad_accum_steps > 1: the means over the step's
+        """{total, mse, freq, ms, consistency, latent, reconstruction} of the latest step (the trainer's `latent_loss_dict`,
+        train_ddp_v3mod2.py:313-318); trainers without a latent term return {total}.  "mse" is the reconstruction term,
+        un-weighted, whatever its kind (the Charbonnier mean with loss="charbonnier_latent"); "reconstruction" is the same value
+        under its own name.  With grad_accum_steps > 1: the means over the step's
         micro-batches (the library keeps the sums; between two micro-batches, the mean over those run so far)."""
         n = self._micro if self._micro > 0 else self._last_micro
         if self.latent_loss["latent_weight"] == 0.0:
             return dict(total=float(self._scal[0]) / n)
         L.check(L.lib().jat_trainer_loss_terms(self.ptr, L.ptr(self._terms), L.stream_ptr()))
-        return dict(zip(("total", "mse", "freq", "ms", "consistency", "latent"), (v / n for v in self._terms.tolist())))
+        terms = dict(zip(("total", "mse", "freq", "ms", "consistency", "latent"), (v / n for v in self._terms.tolist())))
+        terms["reconstruction"] = terms["mse"]
+        return terms
 
     def set_regularisers(self, dropout, drop_path):
         """Per-layer nn.Dropout p and DropPath rate (defaults: what the model was constructed with,
@@ -564,14 +598,20 @@ class Trainer:
                 work = torch.empty(4104, dtype=torch.uint8, device=self.device)
                 L.check(L.lib().jat_k_recon_loss(L.ptr(pred), L.ptr(hr_norm), L.ptr(scratch), L.ptr(out6), pred.numel(),
                                                  self.charbonnier_eps, 1.0, L.ptr(work), work.numel(), L.stream_ptr()))
-                acc[0] += out6[0].double(); acc[1] += 1
-                losses.append(float(out6[0]))
+                val = out6[0].double() * self.reconstruction_weight
+                acc[0] += val; acc[1] += 1
+                losses.append(float(val))
                 continue
             work = torch.empty((Tv * 8 + 255) // 256 * 256 + rows * 32, dtype=torch.uint8, device=self.device)
-            L.check(L.lib().jat_k_latent_loss(L.ptr(pred), L.ptr(hr_norm), L.ptr(lr_norm), L.ptr(scratch), L.ptr(out6), rows, Tv,
-                                              ll["latent_weight"], ll["freq_weight"], ll["ms_weight"], ll["consistency_weight"],
-                                              ll["low_freq_phase_ratio"], ll["strict_cutoff"], ll["soft_cutoff"], 1.0,
-                                              L.ptr(work), work.numel(), L.stream_ptr()))
+            weights = (ll["latent_weight"], ll["freq_weight"], ll["ms_weight"], ll["consistency_weight"],
+                       ll["low_freq_phase_ratio"], ll["strict_cutoff"], ll["soft_cutoff"])
+            if self.recon_eps == 0.0 and self.reconstruction_weight == 1.0:
+                L.check(L.lib().jat_k_latent_loss(L.ptr(pred), L.ptr(hr_norm), L.ptr(lr_norm), L.ptr(scratch), L.ptr(out6), rows, Tv,
+                                                  *weights, 1.0, L.ptr(work), work.numel(), L.stream_ptr()))
+            else:                               # train_ddp_v3mod3.py:1138-1159: the training loss, Charbonnier and weights included
+                L.check(L.lib().jat_k_latent_loss_ex(L.ptr(pred), L.ptr(hr_norm), L.ptr(lr_norm), L.ptr(scratch), L.ptr(out6), rows,
+                                                     Tv, self.recon_eps, self.reconstruction_weight, *weights, 1.0, L.ptr(work),
+                                                     work.numel(), L.stream_ptr()))
             o = out6.double()
             acc[0] += o[0]; acc[1] += 1; acc[2:7] += o[1:6]
             losses.append(float(o[0]))
