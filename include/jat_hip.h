@@ -348,6 +348,10 @@ int jat_k_weight_grad(const uint16_t* dY, const uint16_t* X, float* dW, float* d
  * added to the old contents.  accumulate == 0 is jat_k_weight_grad. */
 int jat_k_weight_grad_ex(const uint16_t* dY, const uint16_t* X, float* dW, float* db, int32_t tokens, int32_t out, int32_t in,
                          int32_t ksplit, void* work, size_t work_bytes, int32_t accumulate, void* stream);
+/* The launch jat_k_weight_grad (ksplit == 0) and the trainer make of a weight [out, in] over `tokens` rows: tile = 128 or 256
+ * (the square output tile of the GEMM kernel), ksplit = the K slices (1..16).  JAT_E_INVALID for a NULL output, a non-positive
+ * size, or widths that are not multiples of 128.  Host arithmetic only: launches nothing and needs no GPU. */
+int jat_k_weight_grad_plan(int32_t out, int32_t in, int32_t tokens, int32_t* tile, int32_t* ksplit);
 /* GQA attention on bf16 q[M,Hq*64], k[M,Hkv*64], vt[B,Hkv,64,Npad] -> o[M,Hq*64]; softmax(q k^T / 8) v. */
 int jat_k_attention(const uint16_t* q, const uint16_t* k, const uint16_t* vt, uint16_t* o, int32_t B,
                     int32_t N, int32_t Hq, int32_t Hkv, int32_t Npad, void* stream);

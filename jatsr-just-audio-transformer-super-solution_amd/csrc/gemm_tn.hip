@@ -25,7 +25,6 @@
 // 16 x 16 tile, stored as one float4.
 #include "jat_kernels.h"
 #include "jat_dtype.h"
-#include <cstdlib>
 
 typedef jat_opx8 opx8;
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -380,11 +379,13 @@ __global__ void __launch_bounds__(512, 1) gemm_tn256_kernel(GemmTnArgs p) {
 }
 
 bool gemm_tn_supports(int M, int N) { return M % TBM == 0 && N % TBN == 0; }
-// split-K slices that fill the chip: one 256 x 256 tile per CU when both sides allow it, else the 128 x 128 kernel (2 blocks/CU)
+// the tile of a weight: one 256 x 256 tile per CU when both sides allow it and there are at least 16 of them, else the 128 x 128
+// kernel (2 blocks/CU)
+int gemm_tn_tile(int M, int N) { return M % 256 == 0 && N % 256 == 0 && (int64_t)M * N >= 1024 * 1024 ? 256 : TBM; }
+// split-K slices that fill the chip
 int gemm_tn_ksplit(int M, int N, int K) {
-  const int nkt = (K + 63) / 64;
-  const bool big = M % 256 == 0 && N % 256 == 0 && (int64_t)M * N >= 1024 * 1024;
-  const int tiles = big ? (M / 256) * (N / 256) : (M / TBM) * (N / TBN), slots = big ? 256 : 512;
+  const int nkt = (K + 63) / 64, tile = gemm_tn_tile(M, N);
+  const int tiles = (M / tile) * (N / tile), slots = tile == 256 ? 256 : 512;
   int s = slots / tiles;
   if (s > nkt / 8) s = nkt / 8;     // at least 8 K-tiles per slice: the prologue, epilogue and the partial sums are not free
   return s < 1 ? 1 : (s > 16 ? 16 : s);
@@ -395,6 +396,8 @@ hipError_t launch_gemm_tn(const bf16_t* dY, int64_t ldy, const bf16_t* X, int64_
   if (!gemm_tn_supports(M, N) || K <= 0 || ldy % 8 != 0 || ldx % 8 != 0 || ldo % 4 != 0) return hipErrorInvalidValue;
   if (ksplit < 1 || ksplit > (K + TBK - 1) / TBK) return hipErrorInvalidValue;
   if (accumulate && ksplit > 1) return hipErrorInvalidValue;   // partial slices are overwritten; their sum is what accumulates
+  const bool big = gemm_tn_tile(M, N) == 256;
+  if (big && !zeros) return hipErrorInvalidValue;   // the 256 x 256 kernel's source for token rows past the end
   static bool attr_set = false;
   if (!attr_set) {
     hipError_t e = hipFuncSetAttribute((const void*)gemm_tn_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * STAGE);
@@ -407,8 +410,6 @@ hipError_t launch_gemm_tn(const bf16_t* dY, int64_t ldy, const bf16_t* X, int64_
   GemmTnArgs a{};
   a.A = dY; a.lda = ldy; a.B = X; a.ldb = ldx; a.out = dW; a.ldo = ldo; a.M = M; a.N = N; a.K = K;
   a.ksplit = ksplit; a.split_stride = split_stride; a.zeros = zeros;
-  static const int force = getenv("JAT_TN_TILE") ? atoi(getenv("JAT_TN_TILE")) : 0;   // 128 / 256: tests and tools
-  const bool big = M % 256 == 0 && N % 256 == 0 && zeros && (force ? force == 256 : (int64_t)M * N >= 1024 * 1024);
   if (big && accumulate)
     hipLaunchKernelGGL(gemm_tn256_kernel<true>, dim3((M / 256) * (N / 256), ksplit), dim3(512), 2 * tn256::STAGE2, s, a);
   else if (big)

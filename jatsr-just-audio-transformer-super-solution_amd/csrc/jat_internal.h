@@ -103,3 +103,12 @@ int jat_gemm(const jat_model* m, int site, const bf16_t* A, int64_t lda, const b
              int epi, GemmArgs extra, hipStream_t s, const GemmPlan* plan = nullptr);
 // (re)pack the bf16 / fp32 device copies of the model from named fp32 tensors; sync_tables: also (re)build the RoPE tables
 int jat_pack_weights(jat_model* m, const jat_tensor_ref* named, int32_t n, hipStream_t s, bool build_tables);
+
+// One weight gradient dW[out,in] = dY^T X (+ db[out] = column sums of dY when db) from token-major dY [tokens,out], X [tokens,in]
+// (gemm_tn.hip): the GEMM, the ordered sum of its K slices when ksplit > 1, the column sum.  acc: added into dW / db, in the GEMM's
+// epilogue when there is one slice, in the sum of the slices otherwise.  zeros: >= 16 zero bytes; split / colsum: scratch of
+// jat_weight_grad_scratch(...) floats.  Both the trainer and jat_k_weight_grad_ex run this.
+struct DwScratch { size_t split_floats, colsum_floats; };
+DwScratch jat_weight_grad_scratch(int tokens, int out, int in, int ksplit, bool with_db);
+int jat_weight_grad(const bf16_t* dY, const bf16_t* X, float* dW, float* db, int tokens, int out, int in, int ksplit,
+                    const void* zeros, float* split, float* colsum, bool acc, hipStream_t s);

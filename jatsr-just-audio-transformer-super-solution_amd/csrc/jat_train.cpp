@@ -4,11 +4,13 @@
 // re-pack of the bf16 operand copies.  Sequencing only: the arithmetic lives in gemm.hip / attention.hip /
 // elementwise.hip / train.hip.
 //
-// Every Linear runs its three GEMMs on gemm_bf16_kernel (C = A W^T, both operands K-contiguous):
+// Every Linear runs its forward and input-gradient GEMMs on gemm_bf16_kernel (C = A W^T, both operands K-contiguous) and its
+// weight gradient on gemm_tn.hip, straight from the token-major operands:
 //   y  = x  W^T        A = x [M,in]          W = W   [out,in]
 //   dx = dy W          A = dy [M,out]        W = W^T [in,out]     (transposed bf16 copy, rebuilt after every update)
-//   dW = dy^T x        A = dy^T [out,Mpad]   W = x^T [in,Mpad]    (transpose_bf16_kernel, token axis zero-padded to 64)
+//   dW = dy^T x        jat_weight_grad below
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -33,7 +35,7 @@ struct TLayer {
 
 struct jat_trainer {
   jat_model* m = nullptr;
-  int B = 0, T = 0, ntok = 0, M = 0, Mpad = 0, npad = 0;
+  int B = 0, T = 0, ntok = 0, M = 0, npad = 0;
   float *P = nullptr, *G = nullptr, *m1 = nullptr, *m2 = nullptr;
   float* ema = nullptr;                // caller-owned moving average of P (jat_trainer_set_ema); nullptr: off
   float ema_decay = 0.f;
@@ -48,7 +50,7 @@ struct jat_trainer {
   float *e_sin, *u1, *t_h, *t_emb, *mod, *pred;
   // backward scratch
   float *dx, *dpred, *dmod, *part, *red_part, *scal, *delta, *dwqkv, *dt_emb, *du1, *small_part;
-  bf16_t *dy, *dh, *dxn, *dao, *dqkv, *tA, *tB, *dyf;
+  bf16_t *dy, *dh, *dxn, *dao, *dqkv, *dyf;
   int64_t o_pe_w1, o_pe_b1, o_pe_w2, o_pe_b2, o_te_w1, o_te_b1, o_te_w2, o_te_b2, o_fn, o_wf, o_bf;
   bool rms = true;
   // gradient-ready hook (DDP overlap): called on the host, during enqueue, once the last kernel writing the slice
@@ -67,12 +69,10 @@ struct jat_trainer {
   double rw = 1.0;                     // weight of the reconstruction term (jat_trainer_set_loss_ex; train_ddp_v3mod3.py:416,966)
   float2* tw = nullptr;                // [T] twiddles
   float *ll_part = nullptr, *terms = nullptr;
-  float* dw_split = nullptr;           // split-K partials of the small dW GEMMs
+  float* dw_split = nullptr;           // split-K partial slices of the dW GEMMs
   const void* zero_cell = nullptr;     // 256 zero bytes (the workspace is zeroed once and this cell is never written)
   float* colsum_part = nullptr;        // row-slice partials of the bias-gradient column sums
-  bool tn_dw = true;                   // dW straight from token-major operands (JAT_TN_DW=0: transposed copies + gemm_bf16_kernel)
   float* dkv_part = nullptr;           // per-query-head fp32 partials of dK / dV (attention backward)
-  int64_t split4_area = 0, split2_area = 0;
   // Weight gradients on a second stream (JAT_DW_STREAM=1).  dW = dY^T X of a Linear is off the critical path of the backward (nothing
   // reads it before the gradient norm), while the dX chain in front of it alternates MFMA-bound GEMMs with HBM- / VALU-bound
   // passes (norm and gate backward, GELU', attention backward): with the dW GEMMs queued beside that chain the chip works on a
@@ -87,7 +87,6 @@ struct jat_trainer {
   // the call in flight (jat_trainer_fwd_bwd_ex flags): accum: every writer of grads_flat, and the loss cells, add to what is there;
   // no_hook: the gradient-ready hook stays silent (not the last micro-batch of the optimiser step)
   bool accum = false, no_hook = false;
-  int64_t dw_split_floats = 0;         // capacity of dw_split
 };
 
 namespace {
@@ -145,55 +144,18 @@ int repack(jat_trainer* tr, hipStream_t s) {
   return build_transposes(tr, s);
 }
 
+// The weights whose gradient is a [out, in] GEMM over all tokens (weight_grad below), as {out, in}: final Linear, MLP fc2 / fc1,
+// out_proj, fused QKV, patch-embed proj.2 / proj.0
+std::array<std::array<int, 2>, 7> dw_shapes(const jat_model* m) {
+  const int D = m->D;
+  return {{{m->Fout, D}, {D, m->mlp}, {m->mlp, D}, {D, D}, {D + 2 * m->kvD, D}, {D, m->bott}, {m->bott, m->Kp}}};
+}
+
 // dW[out,in] = dY^T X and (optionally) db[out] = column sums of dY, from dY bf16 [M,out] and X bf16 [M,in]; acc: added into
 // dW / db (G = G_old + g) instead of overwriting them
 int weight_grad(jat_trainer* tr, const bf16_t* dY, int out, const bf16_t* X, int in, float* dW, float* db, bool acc, hipStream_t s) {
-  // M x N tiles of a small weight do not fill 256 CUs while K = all tokens is long: split K, sum the partials in order
-  const int64_t area = (int64_t)out * in;
-  const int split = area <= tr->split4_area ? 4 : (area <= tr->split2_area ? 2 : 1);
-  if (tr->tn_dw && gemm_tn_supports(out, in)) {   // straight from the token-major operands (gemm_tn.hip)
-    const int ks = gemm_tn_ksplit(out, in, tr->M);
-    // one slice: the add happens in the GEMM's epilogue; several: the slices are overwritten, their ordered sum is added
-    KCHK(launch_gemm_tn(dY, out, X, in, ks > 1 ? tr->dw_split : dW, in, out, in, tr->M, ks, area, tr->zero_cell, acc && ks == 1, s));
-    if (ks > 1) KCHK(launch_sum_partials(tr->dw_split, ks, area, dW, area, acc, s));
-    if (db) KCHK(launch_colsum_bf16(dY, out, tr->M, out, tr->colsum_part, db, acc, s));
-    return JAT_OK;
-  }
-  KCHK(launch_transpose_bf16(dY, out, tr->M, out, tr->tA, tr->Mpad, s));
-  KCHK(launch_transpose_bf16(X, in, tr->M, in, tr->tB, tr->Mpad, s));
-  GemmArgs e{};
-  e.ldo = in; e.ntok = out;
-  if (split > 1 || acc) {   // acc: gemm.hip's fp32 epilogue only overwrites, so an unsplit product goes through the scratch as well
-    if ((int64_t)split * area > tr->dw_split_floats)
-      return fail(JAT_E_STATE, "weight gradient [%d, %d] cannot accumulate: %d slice(s) do not fit the split scratch", out, in, split);
-    e.out = tr->dw_split;
-    if (split > 1) { e.ksplit = split; e.split_stride = area; }
-    JCHK(jat_gemm(tr->m, G_OTHER, tr->tA, tr->Mpad, tr->tB, tr->Mpad, out, in, tr->Mpad, EPI_F32, e, s));
-    KCHK(launch_sum_partials(tr->dw_split, split, area, dW, area, acc, s));
-  } else {
-    e.out = dW;
-    JCHK(jat_gemm(tr->m, G_OTHER, tr->tA, tr->Mpad, tr->tB, tr->Mpad, out, in, tr->Mpad, EPI_F32, e, s));
-  }
-  if (db) KCHK(launch_rowsum_bf16(tr->tA, tr->Mpad, out, tr->Mpad, db, acc, s));
-  return JAT_OK;
-}
-
-// Can every weight-gradient site of this trainer add into grads_flat?  The only one that may not is the transposed-copy path of
-// weight_grad, whose product has to fit the split scratch.  JAT_E_STATE, never a silent overwrite.
-int accumulate_supported(const jat_trainer* tr) {
-  const jat_model* m = tr->m;
-  const int D = m->D;
-  const int shapes[][2] = {{m->Fout, D}, {D, m->mlp}, {m->mlp, D}, {D, D}, {D, m->bott}, {m->bott, m->Kp}};   // QKV goes to its own scratch
-  for (auto& sh : shapes) {
-    if (tr->tn_dw && gemm_tn_supports(sh[0], sh[1])) continue;
-    const int64_t area = (int64_t)sh[0] * sh[1];
-    const int split = area <= tr->split4_area ? 4 : (area <= tr->split2_area ? 2 : 1);
-    if (split * area > tr->dw_split_floats)
-      return fail(JAT_E_STATE, "JAT_FB_ACCUMULATE: the weight gradient [%d, %d] takes the transposed-copy path and its %d slice(s) do "
-                  "not fit the split scratch (%lld floats): this trainer cannot accumulate", sh[0], sh[1], split,
-                  (long long)tr->dw_split_floats);
-  }
-  return JAT_OK;
+  return jat_weight_grad(dY, X, dW, db, tr->M, out, in, gemm_tn_ksplit(out, in, tr->M), tr->zero_cell, tr->dw_split, tr->colsum_part,
+                         acc, s);
 }
 
 // dX bf16 [M,in] = dY [M,out] W, with WT = W^T [in,out]
@@ -425,6 +387,22 @@ int backward_train(jat_trainer* tr, const float* target, const float* cond_clean
 
 }  // namespace
 
+// ---- one weight gradient (jat_internal.h): the trainer's weight_grad and jat_k_weight_grad_ex both run this ------------
+DwScratch jat_weight_grad_scratch(int tokens, int out, int in, int ksplit, bool with_db) {
+  return {ksplit > 1 ? (size_t)ksplit * out * in : 0, with_db ? (size_t)colsum_slices(tokens) * out : 0};
+}
+
+int jat_weight_grad(const bf16_t* dY, const bf16_t* X, float* dW, float* db, int tokens, int out, int in, int ksplit,
+                    const void* zeros, float* split, float* colsum, bool acc, hipStream_t s) {
+  // M x N tiles of a small weight do not fill 256 CUs while K = all tokens is long: split K, sum the partials in order
+  const int64_t area = (int64_t)out * in;
+  // one slice: the add happens in the GEMM's epilogue; several: the slices are overwritten, their ordered sum is added
+  KCHK(launch_gemm_tn(dY, out, X, in, ksplit > 1 ? split : dW, in, out, in, tokens, ksplit, area, zeros, acc && ksplit == 1, s));
+  if (ksplit > 1) KCHK(launch_sum_partials(split, ksplit, area, dW, area, acc, s));
+  if (db) KCHK(launch_colsum_bf16(dY, out, tokens, out, colsum, db, acc, s));
+  return JAT_OK;
+}
+
 extern "C" void jat_trainer_destroy(jat_trainer* tr) {
   if (!tr) return;
   if (tr->dw_stream) { (void)hipStreamSynchronize(tr->dw_stream); (void)hipStreamDestroy(tr->dw_stream); }
@@ -454,14 +432,20 @@ extern "C" int jat_trainer_create(jat_model* m, const jat_tensor_ref* params, in
   hipStream_t s = (hipStream_t)stream;
   jat_trainer* tr = new jat_trainer();
   tr->m = m; tr->B = B; tr->T = T; tr->ntok = ntok; tr->M = B * ntok;
-  tr->Mpad = (int)align_up((size_t)tr->M, 512);   // K of the dW GEMMs: divisible by 64 * (split-K factor <= 8)
   tr->npad = (int)align_up((size_t)ntok, 64);
   tr->P = params_flat; tr->G = grads_flat; tr->m1 = exp_avg; tr->m2 = exp_avg_sq; tr->total = total;
   tr->rms = m->cfg.norm_mode == JAT_NORM_RMS_W;
   tr->p_drop.assign(m->depth, 0.f);
   tr->p_path.assign(m->depth, 0.f);
   const int D = m->D, depth = m->depth, mlp = m->mlp, bott = m->bott, kvD = m->kvD, Nqkv = D + 2 * kvD;
-  const int M = tr->M, Mpad = tr->Mpad;
+  const int M = tr->M;
+  // every weight gradient runs on gemm_tn.hip.  jat_model_create's divisibility rules imply this; a model that broke it would
+  // otherwise fail at its first backward launch
+  for (auto& sh : dw_shapes(m))
+    if (!gemm_tn_supports(sh[0], sh[1])) {
+      delete tr;
+      return fail(JAT_E_INVALID, "weight [%d, %d]: the weight-gradient GEMM needs both widths to be multiples of 128", sh[0], sh[1]);
+    }
 
   // ---- parameter table: every tensor must lie inside the flat buffer, 16-B aligned, with the expected size ----
   std::unordered_map<std::string, int64_t> off;
@@ -527,7 +511,6 @@ extern "C" int jat_trainer_create(jat_model* m, const jat_tensor_ref* params, in
     rc = fail(JAT_E_INVALID, "%d parameters given, %zu belong to this model: every trainable tensor must be known", n, used);
   if (rc != JAT_OK) { delete tr; return rc; }
 
-  if (const char* e = getenv("JAT_TN_DW")) tr->tn_dw = atoi(e) != 0;
   tr->dw_async = true;   // measured: 61.2 -> 58.5 ms per step at T = 1378, 33.3 -> 31.5 ms at T = 512 (profiles/r03/train_dw_stream_ab.log)
   if (const char* e = getenv("JAT_DW_STREAM")) tr->dw_async = atoi(e) != 0;
   if (tr->dw_async) {
@@ -593,17 +576,13 @@ extern "C" int jat_trainer_create(jat_model* m, const jat_tensor_ref* params, in
       tr->small_part = (float*)take(slabs * B * D * 4);
     }
     tr->dw_part = (float*)take((size_t)B * D * 4);
-    tr->split4_area = (int64_t)Nqkv * D;            // q/k/v, out_proj, patch-embed proj.2: 4 slices
-    tr->split2_area = (int64_t)m->Fout * D;         // final Linear: 2 slices; the MLP weights fill the chip unsplit
-    if (tr->split2_area < tr->split4_area) tr->split2_area = tr->split4_area;
-    {
-      size_t need = (size_t)std::max(4 * tr->split4_area, 2 * tr->split2_area);
-      const int shapes[][2] = {{m->Fout, D}, {D, mlp}, {mlp, D}, {D, D}, {Nqkv, D}, {D, m->bott}, {m->bott, m->Kp}};
-      for (auto& sh : shapes)
-        if (gemm_tn_supports(sh[0], sh[1])) need = std::max(need, (size_t)gemm_tn_ksplit(sh[0], sh[1], M) * sh[0] * sh[1]);
-      tr->dw_split = (float*)take(need * 4);
-      tr->dw_split_floats = (int64_t)need;
+    size_t split_f = 0, colsum_f = 0;   // the largest scratch any weight gradient of the step asks for
+    for (auto& sh : dw_shapes(m)) {
+      const DwScratch need = jat_weight_grad_scratch(M, sh[0], sh[1], gemm_tn_ksplit(sh[0], sh[1], M), true);
+      split_f = std::max(split_f, need.split_floats);
+      colsum_f = std::max(colsum_f, need.colsum_floats);
     }
+    tr->dw_split = (float*)take(split_f * 4);
     tr->zero_cell = take(256);
     tr->copy_jobs = (CopyJob*)take((size_t)(8 + 5 * depth + 2) * sizeof(CopyJob));
     tr->dy = (bf16_t*)take(MD2); tr->dh = (bf16_t*)take((size_t)M * std::max(mlp, bott) * 2);
@@ -616,16 +595,7 @@ extern "C" int jat_trainer_create(jat_model* m, const jat_tensor_ref* params, in
       tr->dq_b[1] = (bf16_t*)take((size_t)M * Nqkv * 2);
     }
     tr->dyf = (bf16_t*)take((size_t)M * m->Fout * 2);
-    const int rowsA = std::max(std::max(m->Fout, Nqkv), std::max(mlp, std::max(D, bott)));
-    const int rowsB = std::max(std::max(m->Kp, mlp), std::max(D, bott));
-    {   // transposed activation copies: only for the weights gemm_tn.hip does not take (widths that are not multiples of 128)
-      const int shapes[][2] = {{m->Fout, D}, {D, mlp}, {mlp, D}, {D, D}, {Nqkv, D}, {D, bott}, {bott, m->Kp}};
-      bool need = !tr->tn_dw;
-      for (auto& sh : shapes) need = need || !gemm_tn_supports(sh[0], sh[1]);
-      tr->tA = need ? (bf16_t*)take((size_t)rowsA * Mpad * 2) : nullptr;
-      tr->tB = need ? (bf16_t*)take((size_t)rowsB * Mpad * 2) : nullptr;
-    }
-    tr->colsum_part = (float*)take((size_t)colsum_slices(M) * rowsA * 4);
+    tr->colsum_part = (float*)take(colsum_f * 4);
     if (pass == 0) {
       tr->blob_bytes = o;
       if (hipMalloc((void**)&tr->blob, o) != hipSuccess) {
@@ -784,7 +754,6 @@ extern "C" int jat_trainer_fwd_bwd_ex(jat_trainer* tr, const float* z_t, const f
   tr->seed = rng_seed;
   tr->accum = (flags & JAT_FB_ACCUMULATE) != 0;
   tr->no_hook = (flags & JAT_FB_NO_HOOK) != 0;
-  if (tr->accum) JCHK(accumulate_supported(tr));   // before anything is queued: never a half-accumulated buffer
   JCHK(forward_train(tr, z_t, t, x_cond, s));
   JCHK(backward_train(tr, target, cond_clean, loss_scale, s));
   if (loss_out) HIPCHK(hipMemcpyAsync(loss_out, tr->scal, 4, hipMemcpyDeviceToDevice, s));
@@ -1053,6 +1022,37 @@ extern "C" int jat_k_adamw_ema(float* p, const float* g, float* m, float* v, flo
   KCHK(launch_adamw(p, (float*)g, m, v, n, norm2, 1.0f / loss_scale, max_grad_norm, lr, beta1, beta2, eps, weight_decay, step, ema,
                     ema_decay, s));
   if (grad_norm_out) HIPCHK(hipMemcpyAsync(grad_norm_out, norm2 + 1, 4, hipMemcpyDeviceToDevice, s));
+  return JAT_OK;
+}
+
+// the weight / bias gradient of one Linear, as the trainer's weight_grad runs it; ksplit == 0: the trainer's own choice.
+// work: 256 zero-cell bytes, then the split slices, then the column-sum partials
+extern "C" int jat_k_weight_grad(const uint16_t* dY, const uint16_t* X, float* dW, float* db, int32_t tokens, int32_t out,
+                                 int32_t in, int32_t ksplit, void* work, size_t work_bytes, void* stream) {
+  return jat_k_weight_grad_ex(dY, X, dW, db, tokens, out, in, ksplit, work, work_bytes, 0, stream);
+}
+extern "C" int jat_k_weight_grad_ex(const uint16_t* dY, const uint16_t* X, float* dW, float* db, int32_t tokens, int32_t out,
+                                    int32_t in, int32_t ksplit, void* work, size_t work_bytes, int32_t accumulate, void* stream) {
+  if (!gemm_tn_supports(out, in)) return fail(JAT_E_INVALID, "out and in must be multiples of 128");
+  if (tokens <= 0) return fail(JAT_E_INVALID, "tokens must be positive");
+  if (ksplit == 0) ksplit = gemm_tn_ksplit(out, in, tokens);
+  if (ksplit < 1 || ksplit > (tokens + 63) / 64) return fail(JAT_E_INVALID, "bad ksplit");
+  const DwScratch sc = jat_weight_grad_scratch(tokens, out, in, ksplit, db != nullptr);
+  const size_t need = 256 + (sc.split_floats + sc.colsum_floats) * 4;
+  if (!work || work_bytes < need) return fail(JAT_E_INVALID, "work needs %zu bytes", need);
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(hipMemsetAsync(work, 0, 256, s));   // the zero cell ragged token tiles are padded from
+  float* split = (float*)((char*)work + 256);
+  return jat_weight_grad(dY, X, dW, db, tokens, out, in, ksplit, work, split, split + sc.split_floats, accumulate != 0, s);
+}
+
+// which launch a weight gradient [out, in] over `tokens` rows is (gemm_tn.hip): the output tile (128 or 256) and the K slices;
+// host only, launches nothing
+extern "C" int jat_k_weight_grad_plan(int32_t out, int32_t in, int32_t tokens, int32_t* tile, int32_t* ksplit) {
+  if (!tile || !ksplit || out <= 0 || in <= 0 || tokens <= 0) return fail(JAT_E_INVALID, "bad argument");
+  if (!gemm_tn_supports(out, in)) return fail(JAT_E_INVALID, "out and in must be multiples of 128");
+  *tile = gemm_tn_tile(out, in);
+  *ksplit = gemm_tn_ksplit(out, in, tokens);
   return JAT_OK;
 }
 

@@ -91,35 +91,11 @@ __global__ void __launch_bounds__(256) sum_partials_kernel(const float* __restri
   }
   *(f32x4_t*)(out + i * 4) = acc;
 }
-// nsplit == 1 with accumulate: out += part (how a product that cannot accumulate in its own epilogue gets added)
 hipError_t launch_sum_partials(const float* part, int nsplit, int64_t stride, float* out, int64_t n, int accumulate, hipStream_t s) {
   if (n % 4 != 0 || stride % 4 != 0) return hipErrorInvalidValue;
   const dim3 grid((unsigned)((n / 4 + 255) / 256));
   if (accumulate) hipLaunchKernelGGL(sum_partials_kernel<true>, grid, dim3(256), 0, s, part, nsplit, stride, out, n / 4);
   else hipLaunchKernelGGL(sum_partials_kernel<false>, grid, dim3(256), 0, s, part, nsplit, stride, out, n / 4);
-  return hipGetLastError();
-}
-
-// ---- row sums of a bf16 matrix [R][ld] over its first n columns -> fp32 [R]   (bias gradients from dY^T) -------
-template <bool ACC>
-__global__ void __launch_bounds__(256) rowsum_bf16_kernel(const bf16_t* __restrict__ x, int64_t ld, int R, int n,
-                                                          float* __restrict__ out) {
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-  if (row >= R) return;
-  float acc = 0.f;
-  for (int c = lane * 8; c < n; c += 512) {   // n % 8 == 0
-    float f[8];
-    unpack8(*(const u32x4_t*)(x + (int64_t)row * ld + c), f);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) acc += f[i];
-  }
-  acc = wave_sum_t(acc);
-  if (lane == 0) out[row] = ACC ? out[row] + acc : acc;
-}
-hipError_t launch_rowsum_bf16(const bf16_t* x, int64_t ld, int R, int n, float* out, int accumulate, hipStream_t s) {
-  if (n % 8 != 0) return hipErrorInvalidValue;
-  if (accumulate) hipLaunchKernelGGL(rowsum_bf16_kernel<true>, dim3((R + 3) / 4), dim3(256), 0, s, x, ld, R, n, out);
-  else hipLaunchKernelGGL(rowsum_bf16_kernel<false>, dim3((R + 3) / 4), dim3(256), 0, s, x, ld, R, n, out);
   return hipGetLastError();
 }
 

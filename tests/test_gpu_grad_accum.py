@@ -23,6 +23,7 @@ import jatsr_amd._lib as L  # noqa: E402
 import jatsr_amd.io as jio  # noqa: E402
 import jatsr_amd.recipe as recipe  # noqa: E402
 from helpers import rel_l2  # noqa: E402
+from weight_grad_rule import tn_path  # noqa: E402
 from jatsr_amd import fit as F  # noqa: E402
 from jatsr_amd.data import LatentStore, epoch_batches, train_batch_plan  # noqa: E402
 from jatsr_amd.model import JaT_AudioSR_V2, JaT_AudioSR_V3  # noqa: E402
@@ -40,22 +41,15 @@ def cuda(a):
 
 
 # ---- 1. the kernel ------------------------------------------------------------------------------------------------------
-def tn_path(out, inn, tokens):
-    """(tile, K slices) a weight gradient [out, in] over `tokens` rows takes: the rule of gemm_tn_ksplit / launch_gemm_tn
-    (csrc/gemm_tn.hip), restated."""
-    nkt = (tokens + 63) // 64
-    big = out % 256 == 0 and inn % 256 == 0 and out * inn >= 1024 * 1024
-    tiles = (out // 256) * (inn // 256) if big else (out // 128) * (inn // 128)
-    s = min((256 if big else 512) // tiles, nkt // 8)
-    return (256 if big else 128), max(1, min(s, 16))
-
-
 @pytest.mark.parametrize("with_db", [True, False])
 @pytest.mark.parametrize("out,inn,tokens,tile,split", [(128, 128, 100, 128, False), (256, 256, 1100, 128, True),
                                                        (1024, 1024, 200, 256, False), (1024, 1024, 1100, 256, True)])
 def test_weight_grad_accumulate_is_prefill_plus_overwrite_result(out, inn, tokens, tile, split, with_db):
     got_tile, ks = tn_path(out, inn, tokens)
     assert got_tile == tile and (ks > 1) == split, (got_tile, ks)       # the four shapes take the four paths
+    lib_tile, lib_ks = ctypes.c_int32(-1), ctypes.c_int32(-1)           # ... by the library's own account of its launch
+    L.check(L.lib().jat_k_weight_grad_plan(out, inn, tokens, ctypes.byref(lib_tile), ctypes.byref(lib_ks)))
+    assert lib_tile.value == tile and (lib_ks.value > 1) == split and (lib_tile.value, lib_ks.value) == (got_tile, ks)
     if not split:
         assert tokens % 64 != 0                                         # ragged last K-tile in the one-slice launches
     g = torch.Generator(device="cpu").manual_seed(1000 + out + tokens)
@@ -135,12 +129,11 @@ SEEDS = (0x1234567, 0x89ABCDEF01, 0x5555AAAA5555)
 
 @pytest.mark.parametrize("cfg_name,norm,B,T,kw,env", [
     ("micro", "rms", 2, 22, dict(dropout=0.1, drop_path=0.1), None),
-    ("micro", "rms", 2, 22, dict(dropout=0.1, drop_path=0.1), ("JAT_TN_DW", "0")),
     ("micro", "rms", 2, 22, dict(dropout=0.1, drop_path=0.1), ("JAT_DW_STREAM", "0")),
     ("micro", "ln", 1, 9, {}, None),
     ("micro", "rms", 2, 22, dict(latent_loss_weight=0.3), None),
     ("wide2", "rms", 3, 1378, {}, None),
-], ids=["micro_rms_T22_drop", "micro_rms_T22_drop_no_tn_dw", "micro_rms_T22_drop_one_stream", "micro_ln_B1_T9", "micro_latent_loss",
+], ids=["micro_rms_T22_drop", "micro_rms_T22_drop_one_stream", "micro_ln_B1_T9", "micro_latent_loss",
         "wide2_B3_T1378"])
 def test_three_accumulated_micro_batches_equal_the_sum_of_the_single_runs(cfg_name, norm, B, T, kw, env, monkeypatch):
     """Every parameter, bit for bit: singles in overwrite mode through the C ABI, then the same three through
