@@ -131,7 +131,8 @@ int jat_solver_plan(const float* times, int32_t n, int32_t solver, jat_solver_ev
 /* jat_sampler_create with a solver and a time grid of n_times values (times == NULL: linspace(0, 1, n_times));
  * jat_sampler_create(m, B, T, steps, s, out) is jat_sampler_create_ex(m, B, T, NULL, steps + 1, JAT_SOLVER_EULER, s, out).
  * The whole evaluation list is captured as one graph; the folded-weight table is shared between samplers of one model whose
- * lists of distinct times are equal. */
+ * lists of distinct times are equal.  The LR latent is the condition and has the sampled latent's shape [B, input_channels, T]: a
+ * model with cond_channels != input_channels is JAT_E_INVALID here (its forward, jat_forward, takes both counts). */
 int jat_sampler_create_ex(jat_model* m, int32_t B, int32_t T, const float* times, int32_t n_times, int32_t solver,
                           float cfg_scale, jat_sampler** out);
 void jat_sampler_destroy(jat_sampler* s);
@@ -185,7 +186,8 @@ int jat_crossfade_pair(const float* prev, int32_t Tp, const float* cur, int32_t 
  * gradient / moment of a tensor lives at the same offset of its buffer.  Gaps between tensors must be zero-filled.
  * Dropout (attention probabilities :175, MLP :269,271) and DropPath (:38-64, :300,306) draw their masks from a
  * counter-based generator keyed by (rng_seed of the step, layer, site, element index) — the same Bernoulli(1-p) / (1-p)
- * semantics as nn.Dropout / drop_path, a different random stream than torch's Philox.  Per-rank batch B <= 32. */
+ * semantics as nn.Dropout / drop_path, a different random stream than torch's Philox.  Per-rank batch B <= 32.  The condition
+ * is a latent of the target's shape: a model with cond_channels != input_channels is JAT_E_INVALID at creation. */
 typedef struct jat_trainer jat_trainer;
 int jat_trainer_create(jat_model* m, const jat_tensor_ref* params, int32_t n_params, float* params_flat,
                        float* grads_flat, float* exp_avg, float* exp_avg_sq, int64_t total, int32_t B, int32_t T,
@@ -355,6 +357,14 @@ int jat_k_weight_grad_plan(int32_t out, int32_t in, int32_t tokens, int32_t* til
 /* GQA attention on bf16 q[M,Hq*64], k[M,Hkv*64], vt[B,Hkv,64,Npad] -> o[M,Hq*64]; softmax(q k^T / 8) v. */
 int jat_k_attention(const uint16_t* q, const uint16_t* k, const uint16_t* vt, uint16_t* o, int32_t B,
                     int32_t N, int32_t Hq, int32_t Hkv, int32_t Npad, void* stream);
+/* The kernel jat_k_attention / jat_k_attention_train, the forward, the sampler and the trainer launch for N tokens per sample with
+ * V padded to Npad keys, for a call with (training forward) or without an lse output and with or without dropout: group = 1: the
+ * group kernel (K / V staged once per KV head, N <= 128); group = 0: the streaming kernel with qt * 16 queries per wave (qt 1
+ * or 2) and kvb keys per staged block (64 or 128).  Follows JAT_ATTN_GROUP / JAT_ATTN_QT / JAT_ATTN_KVB, which are read once
+ * per process.  JAT_E_INVALID for a NULL output, N <= 0, or an Npad that is no multiple of 64 or below N.  Host arithmetic only:
+ * launches nothing and needs no GPU. */
+int jat_k_attention_route(int32_t N, int32_t Npad, int32_t has_lse, int32_t has_dropout, int32_t* group, int32_t* qt,
+                          int32_t* kvb);
 /* The v3mod2 loss (see jat_trainer_set_latent_loss) on pred / target / clean-LR tensors [rows, T]: dpred = d(total *
  * loss_scale)/d pred, out6 = {total, mse, freq, ms, consistency, weighted latent sum}; work: align_up(T*8, 256) + rows*32
  * bytes of device scratch. */

@@ -87,6 +87,7 @@ SIGNATURES = {
     "jat_k_weight_grad_ex": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _VP, _SZ, _I32, _VP]),
     "jat_k_weight_grad_plan": (C.c_int, [_I32, _I32, _I32, _VP, _VP]),
     "jat_k_attention": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP]),
+    "jat_k_attention_route": (C.c_int, [_I32, _I32, _I32, _I32, _VP, _VP, _VP]),
     "jat_k_recon_loss": (C.c_int, [_VP, _VP, _VP, _VP, _I64, C.c_double, _F32, _VP, _SZ, _VP]),
     "jat_k_cast_bf16": (C.c_int, [_VP, _VP, _I64, _VP]),
     "jat_k_attention_train": (C.c_int, [_VP] * 5 + [_I32] * 5 + [C.c_uint64, _I32, _F32, _VP]),
@@ -178,6 +179,9 @@ def lib():
         if not os.path.exists(LIB_PATH):
             raise JatError(f"{LIB_PATH} not found: build it first (`python -c 'import __graft_entry__ as g; "
                            f"g.build()'` or `make -C {os.path.dirname(LIB_PATH)}`); there is no CPU fallback")
+        # torch first: it brings its own copy of the HIP runtime, and a process that loaded the system's copy through this library
+        # before it finds no device at the first kernel launch ("no ROCm-capable device is detected")
+        import torch  # noqa: F401
         h = C.CDLL(LIB_PATH)
         for name, (res, args) in SIGNATURES.items():
             if not hasattr(h, name) and os.environ.get("JAT_LIB_ALLOW_MISSING"):

@@ -366,8 +366,9 @@ __global__ void __launch_bounds__(NWV * 64) attn_group_kernel(const AttnArgs p) 
   }
 }
 
-hipError_t launch_attention(const AttnArgs& a, hipStream_t s) {
-  if (a.N <= 0 || a.B <= 0 || a.Hq % a.Hkv != 0 || a.npad % 64 != 0 || a.npad < a.N) return hipErrorInvalidValue;
+// Which kernel launch_attention starts, from the shape and what the call carries alone (host arithmetic; jat_k_attention_route
+// reports the same).  The three switches are read once per process.
+AttnRoute attention_route(int N, int npad, bool has_lse, bool has_dropout) {
   static const int kvb_env = getenv("JAT_ATTN_KVB") ? atoi(getenv("JAT_ATTN_KVB")) : 64;
   static const int group_env = getenv("JAT_ATTN_GROUP") ? atoi(getenv("JAT_ATTN_GROUP")) : 1;
   static const int qt_env = getenv("JAT_ATTN_QT") ? atoi(getenv("JAT_ATTN_QT")) : 0;   // 0: by block count
@@ -375,16 +376,25 @@ hipError_t launch_attention(const AttnArgs& a, hipStream_t s) {
   // (and dropout-hash) VALU work of a wave, not by staging, and twice the blocks hide each other's barriers better: measured
   // one chunk (B = 2 with CFG, N = 345: 120 -> 240 blocks) 140.8 -> 134.6 ms, a four-chunk file 243.8 -> 241.4 ms, the training
   // step (B = 28, N = 345) 62.05 -> 61.39 ms (profiles/r03/single_chunk_attention_qt_sweep.log, attention_qt_long_train.log)
-  const int qt = qt_env ? qt_env : 1;
-  dim3 grid((a.N + 64 * qt - 1) / (64 * qt), a.Hq, a.B);
-  const bool kvb64 = kvb_env == 64 || a.N <= 64;
-  if (group_env && a.N <= 128 && a.npad >= 128 && !a.lse && !a.drop.thresh) {   // the sampler's shape: K/V staged once per KV head (lens honoured)
+  AttnRoute r;
+  r.qt = qt_env ? (qt_env == 1 ? 1 : 2) : 1;
+  r.kvb = (kvb_env == 64 || N <= 64) ? 64 : 128;
+  // the sampler's shape: K/V staged once per KV head (lens honoured)
+  r.group = group_env && N <= 128 && npad >= 128 && !has_lse && !has_dropout;
+  return r;
+}
+
+hipError_t launch_attention(const AttnArgs& a, hipStream_t s) {
+  if (a.N <= 0 || a.B <= 0 || a.Hq % a.Hkv != 0 || a.npad % 64 != 0 || a.npad < a.N) return hipErrorInvalidValue;
+  const AttnRoute r = attention_route(a.N, a.npad, a.lse != nullptr, a.drop.thresh != 0);
+  dim3 grid((a.N + 64 * r.qt - 1) / (64 * r.qt), a.Hq, a.B);
+  if (r.group) {
     hipLaunchKernelGGL((attn_group_kernel<1, 8>), dim3(a.Hkv, a.B), dim3(512), 0, s, a);
-  } else if (qt == 1) {
-    if (kvb64) hipLaunchKernelGGL((attn_fwd_kernel<1, 64>), grid, dim3(256), 0, s, a);
+  } else if (r.qt == 1) {
+    if (r.kvb == 64) hipLaunchKernelGGL((attn_fwd_kernel<1, 64>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((attn_fwd_kernel<1, 128>), grid, dim3(256), 0, s, a);
   } else {
-    if (kvb64) hipLaunchKernelGGL((attn_fwd_kernel<2, 64>), grid, dim3(256), 0, s, a);
+    if (r.kvb == 64) hipLaunchKernelGGL((attn_fwd_kernel<2, 64>), grid, dim3(256), 0, s, a);
     else hipLaunchKernelGGL((attn_fwd_kernel<2, 128>), grid, dim3(256), 0, s, a);
   }
   return hipGetLastError();

@@ -872,6 +872,10 @@ extern "C" int jat_sampler_create_ex(jat_model* m, int32_t B, int32_t T, const f
   if (!m || !out) return fail(JAT_E_INVALID, "null argument");
   if (!m->loaded) return fail(JAT_E_STATE, "weights not loaded");
   if (B <= 0 || T <= 0) return fail(JAT_E_INVALID, "B, T, steps must be positive");
+  // the LR latent is the condition of every step and has the shape of the sampled latent (infer_test_v3m2.py:107-185)
+  if (m->Cc != m->Cin)
+    return fail(JAT_E_INVALID, "the sampler conditions on a latent of the sampled shape: cond_channels (%d) must equal input_channels (%d)",
+                m->Cc, m->Cin);
   // the evaluation list first: it validates the grid and the solver, and sizes the tables (one row / entry per distinct time)
   std::vector<jat_solver_eval> plan((size_t)(n_times > 1 ? 2 * (n_times - 1) : 0));
   std::vector<float> distinct(plan.size());
@@ -1241,6 +1245,15 @@ extern "C" int jat_k_attention(const uint16_t* q, const uint16_t* k, const uint1
   a.B = B; a.N = N; a.Hq = Hq; a.Hkv = Hkv; a.npad = Npad;
   a.scale_log2e = kAttnScaleLog2e;
   KCHK(launch_attention(a, (hipStream_t)stream));
+  return JAT_OK;
+}
+// which kernel launch_attention starts for this shape (attention.hip); host only, launches nothing
+extern "C" int jat_k_attention_route(int32_t N, int32_t Npad, int32_t has_lse, int32_t has_dropout, int32_t* group, int32_t* qt,
+                                     int32_t* kvb) {
+  if (!group || !qt || !kvb) return fail(JAT_E_INVALID, "null output");
+  if (N <= 0 || Npad % 64 != 0 || Npad < N) return fail(JAT_E_INVALID, "N > 0 and Npad a multiple of 64, >= N");
+  const AttnRoute r = attention_route(N, Npad, has_lse != 0, has_dropout != 0);
+  *group = r.group ? 1 : 0; *qt = r.qt; *kvb = r.kvb;
   return JAT_OK;
 }
 extern "C" int jat_prof_gemm_site(jat_model* m, int32_t site, int32_t max_launches) {

@@ -104,6 +104,11 @@ struct AttnArgs {
                      // longer ones, infer_test_v3m2.py:370-398: the reference runs it alone, unpadded); nullptr: all N keys
 };
 hipError_t launch_attention(const AttnArgs& a, hipStream_t s);
+// The launch launch_attention makes of a call: attn_group_kernel (group), or attn_fwd_kernel<qt, kvb> with qt * 16 queries per
+// wave and kvb keys per staged block.  Decided by N, npad, whether the call carries lse / dropout, and JAT_ATTN_GROUP /
+// JAT_ATTN_QT / JAT_ATTN_KVB (read once per process).
+struct AttnRoute { bool group; int qt, kvb; };
+AttnRoute attention_route(int N, int npad, bool has_lse, bool has_dropout);
 
 // ---- row-wise / elementwise ------------------------------------------------------------------------
 // y = norm(x)*w*(1+scale[b]) + shift[b] -> bf16.  mode: 0 RMS(+w), 1 LayerNorm no affine, 2 none (cast).

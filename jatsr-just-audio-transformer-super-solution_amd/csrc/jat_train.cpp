@@ -426,6 +426,10 @@ extern "C" int jat_trainer_create(jat_model* m, const jat_tensor_ref* params, in
     return fail(JAT_E_INVALID, "null argument");
   if (B <= 0 || T <= 0) return fail(JAT_E_INVALID, "B and T must be positive");
   if (B > 32) return fail(JAT_E_INVALID, "per-rank batch %d > 32 is not supported by the adaLN backward", B);
+  // the condition is the LR latent of the HR latent's shape: prepare, the losses and the Python driver take it at input_channels
+  if (m->Cc != m->Cin)
+    return fail(JAT_E_INVALID, "the trainer conditions on a latent of the target's shape: cond_channels (%d) must equal input_channels (%d)",
+                m->Cc, m->Cin);
   if (total <= 0 || total % 4 != 0) return fail(JAT_E_INVALID, "flat buffer length must be a positive multiple of 4");
   const int ntok = (T + 3) / 4;
   if (ntok > MAX_LEN) return fail(JAT_E_SEQLEN, "Sequence length %d exceeds max_len %d", ntok, MAX_LEN);

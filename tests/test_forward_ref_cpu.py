@@ -15,6 +15,7 @@ import jatsr_amd.recipe as recipe
 from oracle import jat_oracle as O
 
 import forward_ref as R
+from width_cases import FORWARD_CONFIGS
 
 EXACT = 1e-12
 CFGS = {"micro": recipe.CONFIGS["micro"], "v3mod2_depth1": dict(recipe.CONFIGS["v3mod2"], depth=1)}
@@ -51,6 +52,40 @@ def test_exact_twin_is_the_oracle(name, fold):
         assert R.rel_l2(tw.final(last, T), ref) < EXACT
     x = recipe.gaussian("blk_x", (1 if fold else 3, 10, D), 1).astype(np.float64)
     temb = recipe.gaussian("blk_t", (1 if fold else 3, D), 2).astype(np.float64)
+    for i in range(cfg["depth"]):
+        assert R.rel_l2(tw.adaln(i, R.t64(temb)), orc.adaln(i, temb)) < EXACT
+        assert R.rel_l2(tw.block(i, R.t64(x), R.t64(temb)), orc.block(i, x, temb)) < EXACT
+
+
+@pytest.mark.parametrize("norm", ["rms", "ln"])
+@pytest.mark.parametrize("name", list(FORWARD_CONFIGS))
+def test_exact_twin_is_the_oracle_at_the_other_widths(name, norm):
+    """The reference the GPU gates of tests/test_gpu_widths.py rest on, at the hidden sizes, Q / KV ratios (3, 8, 1, 4), MLP ratios
+    (4, 3, 2.5, 2) and channel counts (input != cond in one case) of tests/width_cases.py, for RMSNorm (V3) and LayerNorm (V2):
+    every stage of the forward, the time MLP, adaLN and each block on their own, ragged T; the folded arrangement (RMSNorm
+    only) and two CFG sampler steps where the model can be sampled (cond_channels == input_channels)."""
+    cfg = FORWARD_CONFIGS[name]
+    sd = recipe.make_state_dict(cfg, norm)
+    orc = O.OracleModel(cfg, sd, norm, np.float64)
+    Cin, Cc, D = cfg["input_channels"], cfg["cond_channels"], cfg["hidden_size"]
+    x_t, x_c = recipe.gaussian("x_t", (3, Cin, 70), 7), recipe.gaussian("x_cond", (3, Cc, 70), 7)
+    for fold in ([False, True] if norm == "rms" else [False]):
+        tw = R.Twin(cfg, sd, norm=norm, fold=fold)
+        t = np.array([0.3, 0.3, 0.3] if fold else [0.2, 0.55, 0.9], np.float32)
+        ref = orc.forward(x_t, t, x_c, record=True)
+        st = {}
+        got = tw.forward(x_t, t, x_c, stages=st)
+        assert got.shape == ref.shape == x_t.shape and R.rel_l2(got, ref) < EXACT
+        for k, v in st.items():
+            assert R.rel_l2(v, orc.stages[k]) < EXACT, k
+        if Cin == Cc:
+            lr, z0 = recipe.gaussian("lr_latent", (2, Cin, 22), 210), recipe.gaussian("z0", (2, Cin, 22), 211)
+            assert R.rel_l2(tw.sample(lr, z0, 2, 3.0), O.flow_matching_sample(orc, lr, z0, num_steps=2, cfg_scale=3.0)) < EXACT
+    tw = R.Twin(cfg, sd, norm=norm)
+    tt = np.array([0.0, 0.02, 0.5, 0.98, 1.0], np.float32)
+    assert R.rel_l2(tw.t_embed(R.t64(tt)), orc.t_embed(tt)) < EXACT
+    x = recipe.gaussian("blk_x", (3, 10, D), 1).astype(np.float64)
+    temb = recipe.gaussian("blk_t", (3, D), 2).astype(np.float64)
     for i in range(cfg["depth"]):
         assert R.rel_l2(tw.adaln(i, R.t64(temb)), orc.adaln(i, temb)) < EXACT
         assert R.rel_l2(tw.block(i, R.t64(x), R.t64(temb)), orc.block(i, x, temb)) < EXACT

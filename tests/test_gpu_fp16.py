@@ -36,6 +36,8 @@ def test_fp16_kernels_and_forward_parity():
     _child(["tests/test_gpu_train_kernels.py"])
     _child(["tests/test_gpu_model.py", "-k", "forward_vs_reference or sampler_vs_reference or benchmarked or fused"])
     _child(["tests/test_gpu_forward_paths.py"])     # every launch path at full width, gated on the fp16 rounding floor
+    # the other hidden sizes: norm_modulate_kernel and linear_f32_kernel's SiLU output store through jat_dtype.h
+    _child(["tests/test_gpu_widths.py", "-k", "norm or time_embed or forward"])
 
 
 def test_fp16_training_step_parity_and_loss_scaling():

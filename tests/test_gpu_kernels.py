@@ -49,42 +49,96 @@ def test_cast_bf16():
     assert torch.equal(out, x.to(OP))
 
 
-@pytest.mark.parametrize("mode", [0, 1, 2])
-@pytest.mark.parametrize("D,M,ntok,shared", [(1280, 257, 64, False), (512, 64, 32, True), (256, 9, 3, False)])
-def test_norm_modulate(mode, D, M, ntok, shared):
-    B = (M + ntok - 1) // ntok
-    x = gen((M, D), 2, 3.0) + 0.5
-    w = 1 + 0.2 * gen((D,), 3)
-    mod = gen((1 if shared else B, 2 * D), 4, 0.3)
-    y = torch.empty(M, D, dtype=OP, device=x.device)
-    shift, scale = mod[:, :D], mod[:, D:]
-    L.check(L.lib().jat_k_norm_modulate(L.ptr(x), L.ptr(w), C.c_void_p(mod.data_ptr()),
-                                        C.c_void_p(mod.data_ptr() + 4 * D), 0 if shared else 2 * D, L.ptr(y), M, D,
+MANT = 10 if OP == torch.float16 else 7          # stored mantissa bits of OP
+EMIN = -24 if OP == torch.float16 else -133      # exponent of OP's smallest subnormal
+F32 = 2.0 ** -24                                 # unit roundoff of fp32
+GUARD = 256                                      # elements of NaN on each side of the norm tests' output
+
+
+def op_ulp(r):
+    """Spacing of OP at each element of r (values representable in OP, as float64); `ulp` of tests/test_gpu_train_kernels.py."""
+    _, e = torch.frexp(r.float())
+    u = torch.pow(2.0, (e - 1 - MANT).clamp_min(EMIN).double())
+    return torch.where(r == 0, torch.full_like(u, 2.0 ** EMIN), u)
+
+
+def norm_modulate_case(x, w, shift, scale, mod_bstride, ntok, mode, what):
+    """jat_k_norm_modulate on x [M, D] into a NaN-filled output between NaN guard bands, against fp64:
+      - every element within one OP ulp of the fp64 result rounded to OP (its own rounding, plus the fp32 error before it, which
+        moves it across at most one rounding boundary), plus that fp32 error: the statistics are D-term fp32 sums (sum of squares,
+        and the mean for LayerNorm), g_D = D * 2^-24 relative to the sum of their absolute terms as tests/test_gpu_train_kernels.py
+        derives it — the sum of squares has no cancellation, so rstd carries at most g_D / 2, the mean g_D * mean|x| — and the
+        element-wise chain (x - mu) * rstd * w * (1 + scale) + shift adds <= 8 roundings of 2^-24 on |n (1 + scale)| + |shift|;
+      - the guard bands untouched, no NaN left inside;
+      - the rel-L2 gate the norm tests always had (3e-3: one OP rounding of the result).
+    shift / scale: [B or 1, D] views (row stride mod_bstride, 0 = one row for every sample) or None; w: [D] or None."""
+    M, D = x.shape
+    buf = torch.full((M * D + 2 * GUARD,), float("nan"), device=x.device).to(OP)
+    y = buf[GUARD:GUARD + M * D].view(M, D)
+    L.check(L.lib().jat_k_norm_modulate(L.ptr(x), L.ptr(w), C.c_void_p(shift.data_ptr()) if shift is not None else None,
+                                        C.c_void_p(scale.data_ptr()) if scale is not None else None, mod_bstride, L.ptr(y), M, D,
                                         ntok, mode, L.stream_ptr()))
+    torch.cuda.synchronize()
     xd = x.double()
+    ax = xd.abs().mean(-1, keepdim=True)
     if mode == 0:
-        n = xd / torch.sqrt((xd * xd).mean(-1, keepdim=True) + 1e-6) * w.double()
+        rstd = 1 / torch.sqrt((xd * xd).mean(-1, keepdim=True) + 1e-6)
+        n = xd * rstd * (w.double() if w is not None else 1.0)
     elif mode == 1:
         mu = xd.mean(-1, keepdim=True)
-        n = (xd - mu) / torch.sqrt(((xd - mu) ** 2).mean(-1, keepdim=True) + 1e-6)
+        rstd = 1 / torch.sqrt(((xd - mu) ** 2).mean(-1, keepdim=True) + 1e-6)
+        n = (xd - mu) * rstd
     else:
+        rstd = torch.zeros_like(ax)
         n = xd
-    bidx = torch.zeros(M, dtype=torch.long, device=x.device) if shared else torch.arange(M, device=x.device) // ntok
-    ref = n * (1 + scale.double()[bidx]) + shift.double()[bidx]
+    bidx = torch.arange(M, device=x.device) // ntok if mod_bstride else torch.zeros(M, dtype=torch.long, device=x.device)
+    one_plus = 1 + scale.double()[bidx] if scale is not None else torch.ones_like(n)
+    sh = shift.double()[bidx] if shift is not None else torch.zeros_like(n)
+    ref = n * one_plus + sh
+    g_d = D * F32
+    bound = (g_d / 2 + 8 * F32) * ((n * one_plus).abs() + sh.abs())
+    if mode == 1:
+        bound = bound + g_d * ax * rstd * one_plus.abs()
+    assert bool(torch.isnan(buf[:GUARD].float()).all()) and bool(torch.isnan(buf[-GUARD:].float()).all()), what
+    assert bool(torch.isfinite(y).all()), what
+    r = ref.to(OP).double()
+    err = (y.double() - r).abs()
+    tol = op_ulp(r) + bound
+    bad = ~(err <= tol)
+    print(f"{what}: worst element at {float((err / tol).max()):.3f} of its bound, rel-L2 {rel(y, ref):.3e}")
+    assert not bool(bad.any()), (f"{what}: {int(bad.sum())} / {bad.numel()} elements out of bound; first at "
+                                 f"{np.unravel_index(int(bad.flatten().nonzero()[0]), tuple(bad.shape))}, "
+                                 f"err {float(err[bad].flatten()[0]):.3e} tol {float(tol[bad].flatten()[0]):.3e}")
     # fp32 statistics, one bf16 rounding of the result (2^-9 relative)
     assert (y.double() - ref).abs().max() <= 2 ** -8 * ref.abs().max() + 1e-6
     assert rel(y, ref) < 3e-3
 
 
+# 256 / 512 / 1280 run norm_modulate_rows_kernel<1, 2, 5>, every other width norm_modulate_kernel (launch_norm_modulate); the first
+# three cases are the original ones, the other widths take the same (M, ntok) pairs and one more with M % 4 == 3 (the last block's
+# fourth wave has no row) and a ragged last sample
+NORM_WIDTHS = [768, 1024, 1536, 1792, 2048]
+NORM_SHAPES = [(1280, 257, 64, False), (512, 64, 32, True), (256, 9, 3, False)] + \
+              [(D, M, ntok, sh) for D in NORM_WIDTHS for M, ntok, sh in ((257, 64, False), (64, 32, True), (9, 3, False), (131, 50, False))] + \
+              [(D, 131, 50, False) for D in (256, 512, 1280)]
+
+
+@pytest.mark.parametrize("mode", [0, 1, 2])
+@pytest.mark.parametrize("D,M,ntok,shared", NORM_SHAPES)
+def test_norm_modulate(mode, D, M, ntok, shared):
+    B = (M + ntok - 1) // ntok
+    x = gen((M, D), 2, 3.0) + 0.5
+    w = 1 + 0.2 * gen((D,), 3)
+    mod = gen((1 if shared else B, 2 * D), 4, 0.3)
+    norm_modulate_case(x, w, mod[:, :D], mod[:, D:], 0 if shared else 2 * D, ntok, mode, f"norm_modulate D={D} M={M} mode {mode}")
+
+
 def test_norm_no_modulation():
-    D, M = 1280, 37
-    x = gen((M, D), 5)
-    w = 1 + 0.2 * gen((D,), 6)
-    y = torch.empty(M, D, dtype=OP, device=x.device)
-    L.check(L.lib().jat_k_norm_modulate(L.ptr(x), L.ptr(w), None, None, 0, L.ptr(y), M, D, M, 0, L.stream_ptr()))
-    xd = x.double()
-    ref = xd / torch.sqrt((xd * xd).mean(-1, keepdim=True) + 1e-6) * w.double()
-    assert rel(y, ref) < 3e-3
+    """The final norm's form (weight, no shift / scale) at every width: 1280 on the rows kernel, the others on norm_modulate_kernel."""
+    for D, M in [(1280, 37)] + [(D, 37) for D in NORM_WIDTHS]:
+        x = gen((M, D), 5)
+        w = 1 + 0.2 * gen((D,), 6)
+        norm_modulate_case(x, w, None, None, 0, M, 0, f"norm without modulation D={D}")
 
 
 GEMM_SHAPES = [(128, 128, 64), (256, 512, 128), (1000, 1792, 1280), (56, 1536, 256), (1035, 1280, 5120),

@@ -45,7 +45,7 @@ def gsub(a, meta):
 
 def make_trainer(meta, **kw):
     L.require_gpu()
-    cfg = recipe.CONFIGS[meta["cfg"]]
+    cfg = meta["cfg"] if isinstance(meta["cfg"], dict) else recipe.CONFIGS[meta["cfg"]]   # a config itself, or a recipe name
     cls = JaT_AudioSR_V3 if meta["norm"] == "rms" else JaT_AudioSR_V2
     m = cls(**cfg, dropout=0.0, drop_path_rate=0.0)
     sd = {k: torch.from_numpy(v) for k, v in recipe.make_state_dict(cfg, meta["norm"], meta["salt"]).items()}

@@ -5,6 +5,7 @@ import ctypes as C
 import os
 import re
 import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -66,6 +67,39 @@ def test_model_create_validation_and_workspace():
         rc, _ = _create(**bad)
         assert rc == L.JAT_E_INVALID, bad
         assert L.lib().jat_last_error()
+
+
+def _route(N, npad, lse=0, drop=0, lib=None):
+    g, qt, kvb = C.c_int32(-1), C.c_int32(-1), C.c_int32(-1)
+    rc = (lib or L.lib()).jat_k_attention_route(N, npad, lse, drop, C.byref(g), C.byref(qt), C.byref(kvb))
+    return rc, (g.value, qt.value, kvb.value)
+
+
+def test_attention_route_by_default_and_under_the_switches():
+    """`jat_k_attention_route` (the function `launch_attention` launches by): the group kernel for an eval call of at most 128
+    tokens whose V is padded to 128 keys or more, else attn_fwd_kernel<1, 64>; the training forward (lse, dropout) never takes
+    the group kernel.  The switches are read once per process: each setting in a fresh child (tests/test_gpu_widths.py runs the
+    kernels under the same three settings)."""
+    if not any(os.environ.get(k) for k in ("JAT_ATTN_GROUP", "JAT_ATTN_QT", "JAT_ATTN_KVB")):
+        assert _route(128, 128) == (0, (1, 1, 64)) and _route(100, 128) == (0, (1, 1, 64)) and _route(1, 128) == (0, (1, 1, 64))
+        assert _route(64, 64) == (0, (0, 1, 64)) and _route(129, 192) == (0, (0, 1, 64)) and _route(2048, 2048) == (0, (0, 1, 64))
+        assert _route(128, 128, lse=1) == (0, (0, 1, 64)) and _route(128, 128, drop=1) == (0, (0, 1, 64))
+    g = C.c_int32(-1)
+    for bad in ((0, 64), (-3, 64), (65, 64), (64, 100)):
+        assert _route(*bad) == (L.JAT_E_INVALID, (-1, -1, -1)), bad
+    assert L.lib().jat_k_attention_route(64, 64, 0, 0, None, C.byref(g), C.byref(g)) == L.JAT_E_INVALID and g.value == -1
+    code = ("import ctypes as C, jatsr_amd._lib as L\n"
+            "def r(N, npad, lse=0):\n"
+            "    o = [C.c_int32(-1) for _ in range(3)]\n"
+            "    L.check(L.lib().jat_k_attention_route(N, npad, lse, 0, *[C.byref(x) for x in o]))\n"
+            "    return tuple(x.value for x in o)\n"
+            "print(r(128, 128), r(345, 384), r(128, 128, 1), r(64, 64))\n")
+    for env, want in ((dict(JAT_ATTN_KVB="128", JAT_ATTN_GROUP="0"), "(0, 1, 128) (0, 1, 128) (0, 1, 128) (0, 1, 64)"),
+                      (dict(JAT_ATTN_QT="2", JAT_ATTN_GROUP="0"), "(0, 2, 64) (0, 2, 64) (0, 2, 64) (0, 2, 64)"),
+                      (dict(JAT_ATTN_KVB="128", JAT_ATTN_QT="2"), "(1, 2, 128) (0, 2, 128) (0, 2, 128) (0, 2, 64)")):
+        out = subprocess.run([sys.executable, "-c", code], cwd=ROOT, env=dict(os.environ, **env), capture_output=True, text=True,
+                             timeout=120)
+        assert out.returncode == 0 and out.stdout.strip() == want, (env, out.stdout, out.stderr[-500:])
 
 
 @pytest.mark.parametrize("cfg_name", ["micro", "tiny"])
