@@ -679,6 +679,49 @@ int jat_latent_gather(const void* const* hr_src, const void* const* lr_src, cons
 int jat_train_monitor(const float* pred, const float* target, const float* cond_clean, int64_t n, double* out, void* work,
                       size_t work_bytes, void* stream);
 
+/* ---- latent retrieval: exact nearest-neighbour bank and index-rate blend ------------------------------ */
+/* A bank holds up to `capacity` latent frames as fp16 rows [size, channels] with one fp32 squared norm per key row, computed
+ * from the stored fp16 values.  The stored rows ARE the bank: search and blend are defined on them.  A paired bank keeps
+ * separate key rows (what is searched) and value rows (what is blended in) at the same indices; otherwise they are one buffer.
+ * channels: a multiple of 32 in 32..1024.  All device memory is allocated at creation; every later call only enqueues on the
+ * caller's stream, never synchronises and may be captured into a graph.  The host-side size advances when a call is enqueued. */
+typedef struct jat_bank jat_bank;
+#define JAT_BANK_SLAB 4096   /* key rows per search workgroup: results do not depend on it, tests size banks across it */
+#define JAT_BANK_KEYS 0
+#define JAT_BANK_VALUES 1
+int jat_bank_create(int32_t channels, int32_t capacity, int32_t paired, jat_bank** out);
+void jat_bank_destroy(jat_bank* bank);
+int jat_bank_size(const jat_bank* bank, int32_t* size);
+int jat_bank_clear(jat_bank* bank);
+/* Appends `count` frames first, first + stride, ... of a [channels, len] latent array (fp16 or fp32, as the files store it):
+ *   row[size + i, c] = fp16((float(src[c, first + i stride]) - mean[c]) / std[c])      (the fp32 expression of the channel
+ * affine above, rounded to nearest even).  A paired bank takes value_src (same layout and len) with the value statistics; any
+ * other bank takes value_src NULL.  JAT_E_STATE, with the bank as it was, when size + count > capacity; JAT_E_INVALID when a
+ * frame lies outside the source. */
+int jat_bank_add(jat_bank* bank, const void* key_src, const void* value_src, int32_t src_is_fp16, int64_t len, int64_t first,
+                 int64_t stride, int32_t count, const float* key_mean, const float* key_std, const float* value_mean,
+                 const float* value_std, void* stream);
+/* Device pointers of the key or value rows (fp16 [capacity, channels]) and the key norms (fp32; NULL for the values of a
+ * paired bank), for saving a bank.  `norms` may be NULL. */
+int jat_bank_rows(const jat_bank* bank, int32_t which, const void** rows, const float** norms);
+/* Appends `count` ready fp16 rows (device; values exactly when the bank is paired) and recomputes their norms on the device. */
+int jat_bank_load_rows(jat_bank* bank, const void* keys, const void* values, int32_t count, void* stream);
+int jat_bank_search_workspace_bytes(const jat_bank* bank, int64_t n_queries, size_t* bytes);
+/* x fp32 [B, channels, T]: query (b, t) is the column x[b, :, t], normalised as (x - mean[c]) / std[c] when mean and std are
+ * given (both NULL: x is used as it is).  With d(q, i) = |q|^2 + |k_i|^2 - 2 q.k_i over key rows i < size:
+ *   idx[b, t] = argmin_i d, the lowest index on equal d, always in [0, size);  dist2[b, t] = max(d, 0)  (dist2 may be NULL).
+ * The product is exact in the fp16 keys and carries the query as two fp16 terms (error 2^-22 |q|), accumulated in fp32 in a
+ * fixed channel order: a query's result does not depend on B, on its neighbours or on how the key range is split, and two
+ * runs give the same bits.  A query component beyond the fp16 range (65504) makes that query's distances meaningless.
+ * work: 8-byte aligned, at least the bytes the query function above returns for B T queries; JAT_E_INVALID when smaller. */
+int jat_bank_search(jat_bank* bank, const float* x, const float* mean, const float* std, int32_t B, int32_t T, int32_t* idx,
+                    float* dist2, void* work, size_t work_bytes, void* stream);
+/* y[b, c, t] = (1 - rate) x[b, c, t] + rate v,  v = float(values[idx[b, t], c]), or that times value_std[c] plus
+ * value_mean[c] when both are given; each product and sum rounded once, nothing fused, so rate 0 returns x and rate 1 returns
+ * v.  y may be x.  rate in [0, 1]. */
+int jat_bank_blend(jat_bank* bank, const float* x, const int32_t* idx, const float* value_mean, const float* value_std,
+                   float rate, float* y, int32_t B, int32_t T, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

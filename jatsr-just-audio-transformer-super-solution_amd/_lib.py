@@ -159,9 +159,21 @@ SIGNATURES = {
     "jat_band_splice": (C.c_int, [_VP, _VP, _VP, _I32, _I64, _I64, _VP, _VP, _VP, _SZ, _VP]),
     "jat_latent_gather": (C.c_int, [_VP] * 10 + [_I32] * 3 + [_VP]),
     "jat_train_monitor": (C.c_int, [_VP, _VP, _VP, _I64, _VP, _VP, _SZ, _VP]),
+    "jat_bank_create": (C.c_int, [_I32, _I32, _I32, C.POINTER(_VP)]),
+    "jat_bank_destroy": (None, [_VP]),
+    "jat_bank_size": (C.c_int, [_VP, C.POINTER(_I32)]),
+    "jat_bank_clear": (C.c_int, [_VP]),
+    "jat_bank_add": (C.c_int, [_VP, _VP, _VP, _I32, _I64, _I64, _I64, _I32, _VP, _VP, _VP, _VP, _VP]),
+    "jat_bank_rows": (C.c_int, [_VP, _I32, C.POINTER(_VP), C.POINTER(_VP)]),
+    "jat_bank_load_rows": (C.c_int, [_VP, _VP, _VP, _I32, _VP]),
+    "jat_bank_search_workspace_bytes": (C.c_int, [_VP, _I64, C.POINTER(_SZ)]),
+    "jat_bank_search": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _VP, _VP, _VP, _SZ, _VP]),
+    "jat_bank_blend": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _F32, _VP, _I32, _I32, _VP]),
 }
 MONITOR_WORK_BYTES = 49152   # JAT_MONITOR_WORK_BYTES
 LTAS_SLICES = 64             # JAT_LTAS_SLICES
+BANK_SLAB = 4096             # JAT_BANK_SLAB
+BANK_KEYS, BANK_VALUES = 0, 1
 
 GRAD_HOOK = C.CFUNCTYPE(None, C.c_int64, C.c_int64, C.c_void_p)   # jat_trainer_set_grad_hook callback
 

@@ -1,0 +1,34 @@
+// Launchers of the latent-retrieval kernels (retrieval.hip), used by jat_retrieval.cpp.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+constexpr int RT_THREADS = 256;      // every retrieval kernel: 4 waves
+constexpr int RT_SLAB = 4096;        // key rows one search workgroup scans (JAT_BANK_SLAB)
+constexpr int RT_QTILE = 32;         // queries per search workgroup, resident in LDS as two fp16 planes
+constexpr int RT_KTILE = 128;        // key rows per step of the scan: one 32-row MFMA tile per wave
+constexpr int RT_KCHUNK = 64;        // channels of the key tile staged in LDS at once
+constexpr int RT_MIN_C = 32, RT_MAX_C = 1024;
+
+struct RtPartial {   // one per (slab, query)
+  float d;
+  int32_t idx;
+};
+
+inline bool rt_channels_ok(int C) { return C >= RT_MIN_C && C <= RT_MAX_C && C % 32 == 0; }
+
+// rows[row0 + i, c] = fp16((float(src[c, first + i * stride]) - mean[c]) / std[c]) for i < count, and with src2 the same into
+// rows2 with (mean2, std2).  src / src2: [C, len], fp16 or fp32.  The caller has checked first + (count - 1) * stride < len.
+hipError_t bank_pack_launch(const void* src, const void* src2, bool src_fp16, int64_t len, int64_t first, int64_t stride,
+                            int count, const float* mean, const float* std, const float* mean2, const float* std2,
+                            uint16_t* rows, uint16_t* rows2, int64_t row0, int C, hipStream_t s);
+// norms[row0 + i] = sum_c float(rows[row0 + i, c])^2 for i < count: one wave per row, a fixed order
+hipError_t bank_norms_launch(const uint16_t* rows, float* norms, int64_t row0, int count, int C, hipStream_t s);
+// x fp32 [B, C, T] -> idx int32 [B * T], dist2 fp32 [B * T] (may be null) over key rows [0, size); mean / std both null: x is
+// used as it is.  part: ceil(size / RT_SLAB) * B * T entries.
+hipError_t bank_search_launch(const uint16_t* keys, const float* norms, int size, int C, const float* x, const float* mean,
+                              const float* std, int B, int T, int32_t* idx, float* dist2, RtPartial* part, hipStream_t s);
+// y[b, c, t] = (1 - rate) x[b, c, t] + rate v,  v = float(values[idx[b, t], c]) (* std[c] + mean[c] when given); an index
+// outside [0, size) is clamped into it
+hipError_t bank_blend_launch(const uint16_t* values, int size, int C, const float* x, const int32_t* idx, const float* mean,
+                             const float* std, float rate, float* y, int B, int T, hipStream_t s);

@@ -18,6 +18,10 @@ per-channel normalisation (:381-394).  Differences, all outside the hot path's s
     band below HZ (bare flag: the detected band limit of the source) replaced by the source's own (jatsr_amd.splice,
     csrc/splice.hip).  The source is the 44.1 kHz waveform that was encoded (`--input-audio`), the whole file taken through
     the LR simulation (`--simulate-lr`), or the decoded LR latent (latent-file input).  Every other file is unchanged.
+  * `--index-bank PATH --index-rate R` also writes `{stem}_generated{suffix}_idx.pt` (and, with `--dac-weights`,
+    `{stem}_generated{suffix}_idx.wav`): the generated latent with R of each frame's nearest neighbour in a latent bank
+    (`python -m jatsr_amd.retrieval build`) mixed in (jatsr_amd.retrieval, csrc/retrieval.hip).  Every other file is
+    unchanged.
 
     python -m jatsr_amd.infer --checkpoint ckpt.pt --input-file clip.pt --stats-file stats.json --cfg-scale 3.0
 """
@@ -31,6 +35,7 @@ import torch
 
 from . import io as jio
 from .model import JaT_AudioSR_V2, JaT_AudioSR_V3, load_model
+from .retrieval import index_rate_arg
 from .sampler import chunk_plan, sample_long
 
 
@@ -75,6 +80,11 @@ def build_parser():
                         "codec error")
     p.add_argument("--lf-transition-hz", type=float, default=500.0,
                    help="with --lf-replace: width of the crossfade in frequency, below the cutoff")
+    p.add_argument("--index-bank", type=str, default=None, metavar="PATH",
+                   help="latent bank file (python -m jatsr_amd.retrieval build); also write {stem}_generated_idx.pt, the "
+                        "generated latent blended with each frame's nearest bank frame")
+    p.add_argument("--index-rate", type=index_rate_arg, default=0.4, metavar="R",
+                   help="with --index-bank: share of the retrieved frame in the blend, in [0, 1] (0.3 to 0.6 are usual)")
     return p
 
 
@@ -93,6 +103,8 @@ def run(args):
         raise SystemExit("--resample and --simulate-lr need --input-audio")
     if args.metrics and (not args.dac_weights or (args.input_audio and args.simulate_lr is None)):
         raise SystemExit("--metrics needs --dac-weights and an HR ground truth (--simulate-lr, or a latent file with hr_latent)")
+    index_bank = getattr(args, "index_bank", None)
+    index_rate = index_rate_arg(getattr(args, "index_rate", 0.4)) if index_bank else 0.0
     device = torch.device(args.device)
     os.makedirs(args.output_dir, exist_ok=True)
     model = load_model(args.checkpoint, device=device, cls=JaT_AudioSR_V2 if args.layernorm else JaT_AudioSR_V3,
@@ -140,7 +152,21 @@ def run(args):
                                    "frames": total, "seconds": dt})
     print(f"generated {gen.shape[-1]} frames in {dt:.2f} s -> {out_path}")
     if args.dac_weights:
-        decode_to_wav(args, gen, hr, lr, total, stem, suffix, device, codec, source)
+        codec = decode_to_wav(args, gen, hr, lr, total, stem, suffix, device, codec, source)
+    if index_bank:
+        from .retrieval import LatentBank
+        bank = LatentBank.load(index_bank, device=device)
+        query = lr[None, :, :total].to(device).float() if bank.key == "lr" else None
+        enhanced = bank.retrieve(gen, index_rate, stats=stats, query=query)
+        idx_path = os.path.join(args.output_dir, f"{stem}_generated{suffix}_idx.pt")
+        jio.save_latent_file(idx_path, generated_latent=enhanced[0].to("cpu", torch.float16),
+                             metadata={"source": os.path.basename(path), "index_bank": os.path.basename(index_bank),
+                                       "index_rate": index_rate, "bank_rows": len(bank), "bank_key": bank.key})
+        print(f"retrieval: {len(bank)} bank rows (key={bank.key}), index rate {index_rate} -> {idx_path}")
+        if args.dac_weights:
+            name = f"{stem}_generated{suffix}_idx.wav"
+            jio.write_wav_float32(os.path.join(args.output_dir, name), codec.decode(enhanced[:1])[0, 0], codec.sample_rate)
+            print(f"decoded the blended latent -> {name}")
     return out_path
 
 
@@ -236,6 +262,7 @@ def decode_to_wav(args, gen, hr, lr, total, stem, suffix, device, codec=None, so
         with open(out, "w") as f:
             json.dump(rep, f, indent=2)
         print(f"metrics -> {out}")
+    return codec
 
 
 def main(argv=None):

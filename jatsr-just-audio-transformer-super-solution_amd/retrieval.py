@@ -1,0 +1,394 @@
+"""Latent feature retrieval — the first item of the reference's roadmap (DOCs/future_work.md): a bank of high-resolution
+training latent frames, an exact nearest-neighbour lookup per generated frame (what `faiss.IndexFlatL2`, k = 1, returns) and
+the RVC-style blend  enhanced = (1 - index_rate) * pred_hr + index_rate * retrieved.
+
+The bank lives on the GPU as fp16 rows of normalised frames (csrc/retrieval.hip: pack, search, blend; C ABI `jat_bank_*` in
+include/jat_hip.h).  `key="hr"` looks a frame up by its own (generated) content, `key="lr"` by the LR input at that position
+(the roadmap's `search_by_lr`); the blended-in value is the HR frame either way.
+
+    python -m jatsr_amd.retrieval build --data-dir data_processed --out bank.pt --max-frames 100000
+    python -m jatsr_amd.infer ... --index-bank bank.pt --index-rate 0.4
+
+Whether retrieval improves audio quality is not established here: nothing in this repository was run with trained weights.
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import glob
+import os
+
+import torch
+
+from . import _lib as L
+
+STAT_KEYS = ("hr_mean", "hr_std", "lr_mean", "lr_std")
+FORMAT = 1
+
+
+def frame_plan(lengths, max_frames):
+    """Which frames of each file enter a bank of at most `max_frames` rows -> [(first, stride, count)] per file.
+
+    One global stride s = ceil(total / max_frames); file f contributes the frames whose position in the concatenation of all
+    files is a multiple of s.  So sum(count) = ceil(total / s) <= max_frames, and the plan depends on the lengths alone."""
+    lengths = [int(n) for n in lengths]
+    max_frames = int(max_frames)
+    if max_frames < 1:
+        raise ValueError(f"max_frames {max_frames} must be at least 1")
+    if any(n < 0 for n in lengths):
+        raise ValueError("negative file length")
+    total = sum(lengths)
+    s = max(1, -(-total // max_frames))
+    plan, offset = [], 0
+    for n in lengths:
+        first = (-offset) % s
+        plan.append((first, s, 0 if first >= n else (n - 1 - first) // s + 1))
+        offset += n
+    return plan
+
+
+def check_index_rate(index_rate):
+    """The index rate as a float in [0, 1]; ValueError otherwise (a NaN is outside)."""
+    r = float(index_rate)
+    if not 0.0 <= r <= 1.0:
+        raise ValueError(f"index_rate {index_rate!r} outside [0, 1]")
+    return r
+
+
+def index_rate_arg(text):
+    """argparse type of --index-rate."""
+    try:
+        return check_index_rate(text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
+def _stats_cpu(stats, channels):
+    out = {}
+    for k in STAT_KEYS:
+        if k not in stats:
+            raise KeyError(f"statistics lack {k!r}")
+        v = torch.as_tensor(stats[k]).detach().to("cpu", torch.float32).reshape(-1).clone()
+        if v.numel() != channels:
+            raise ValueError(f"{k} has {v.numel()} entries, expected {channels}")
+        out[k] = v
+    return out
+
+
+def pack_state(keys, values, key, stats):
+    """The dictionary a bank file holds: fp16 rows [N, C] (`values` None unless key == "lr"), the key kind, the channel count
+    and the statistics the rows were normalised with.  Host code on CPU tensors."""
+    if key not in ("hr", "lr"):
+        raise ValueError(f"key {key!r} must be 'hr' or 'lr'")
+    if keys.dim() != 2 or keys.dtype != torch.float16:
+        raise ValueError(f"keys must be fp16 [N, C], got {keys.dtype} {tuple(keys.shape)}")
+    if (values is not None) != (key == "lr"):
+        raise ValueError("values are stored exactly when key == 'lr'")
+    if values is not None and (values.shape != keys.shape or values.dtype != torch.float16):
+        raise ValueError(f"values {values.dtype} {tuple(values.shape)} do not match keys {tuple(keys.shape)}")
+    channels = int(keys.shape[1])
+    return {"format": FORMAT, "keys": keys.detach().cpu().contiguous(),
+            "values": None if values is None else values.detach().cpu().contiguous(), "key": key, "channels": channels,
+            "stats": _stats_cpu(stats, channels)}
+
+
+def unpack_state(d):
+    """Validate a bank dictionary -> (keys, values, key, channels, stats)."""
+    for k in ("keys", "values", "key", "channels", "stats"):
+        if k not in d:
+            raise KeyError(f"bank file lacks {k!r} (keys: {sorted(d.keys())})")
+    st = pack_state(d["keys"], d["values"], d["key"], d["stats"])
+    if st["channels"] != int(d["channels"]):
+        raise ValueError(f"bank file: channels {d['channels']} but rows of {st['channels']}")
+    if st["keys"].shape[0] < 1:
+        raise ValueError("bank file holds no rows")
+    return st["keys"], st["values"], st["key"], st["channels"], st["stats"]
+
+
+def same_stats(a, b):
+    """Whether two statistics dictionaries hold the same fp32 values."""
+    return all(torch.equal(torch.as_tensor(a[k]).detach().to("cpu", torch.float32).reshape(-1),
+                           torch.as_tensor(b[k]).detach().to("cpu", torch.float32).reshape(-1)) for k in STAT_KEYS)
+
+
+class LatentBank:
+    """A GPU-resident bank of normalised fp16 latent frames with exact nearest-neighbour search and index-rate blend."""
+
+    def __init__(self, channels, capacity, key="hr", device="cuda"):
+        if key not in ("hr", "lr"):
+            raise ValueError(f"key {key!r} must be 'hr' or 'lr'")
+        L.require_gpu()
+        self.channels, self.capacity, self.key = int(channels), int(capacity), key
+        self.device = torch.device(device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.stats = None          # CPU fp32 copies of the statistics the rows were normalised with
+        self._dev_stats = None
+        self._work = None
+        self._h = C.c_void_p()
+        with torch.cuda.device(self.device):
+            L.check(L.lib().jat_bank_create(self.channels, self.capacity, 1 if key == "lr" else 0, C.byref(self._h)))
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            try:
+                L.lib().jat_bank_destroy(h)
+            except Exception:
+                pass
+
+    def __len__(self):
+        n = C.c_int32()
+        L.check(L.lib().jat_bank_size(self._h, C.byref(n)))
+        return n.value
+
+    def clear(self):
+        L.check(L.lib().jat_bank_clear(self._h))
+
+    # ---- statistics -----------------------------------------------------------------------------------------------------
+    def _set_stats(self, stats):
+        st = _stats_cpu(stats, self.channels)
+        if self.stats is None:
+            self.stats = st
+            self._dev_stats = {k: v.to(self.device) for k, v in st.items()}
+        elif not same_stats(self.stats, st):
+            raise ValueError("the bank's rows were normalised with other statistics than the ones given")
+
+    def check_stats(self, stats):
+        """ValueError unless `stats` are the statistics this bank was built with."""
+        if self.stats is None:
+            raise ValueError("the bank holds no statistics yet (nothing was added)")
+        if not same_stats(self.stats, _stats_cpu(stats, self.channels)):
+            raise ValueError("the bank's rows were normalised with other statistics than the ones given")
+
+    def _vec(self, v):
+        if v is None:
+            return None
+        v = torch.as_tensor(v).to(self.device, torch.float32).contiguous().view(-1)
+        if v.numel() != self.channels:
+            raise ValueError(f"statistics vector of {v.numel()} entries, expected {self.channels}")
+        return v
+
+    # ---- building -------------------------------------------------------------------------------------------------------
+    def add(self, hr_latent, stats, lr_latent=None, first=0, stride=1, count=None):
+        """Append frames first, first + stride, ... (`count` of them; default: to the end) of a [C, len] latent array,
+        fp16 or fp32, normalised with `stats`.  key == "lr" needs the LR array of the same shape: its frames are the keys."""
+        self._set_stats(stats)
+        if (lr_latent is not None) != (self.key == "lr"):
+            raise ValueError("lr_latent is given exactly when the bank's key is 'lr'")
+        if hr_latent.dim() != 2 or hr_latent.shape[0] != self.channels:
+            raise ValueError(f"latent {tuple(hr_latent.shape)}, expected [{self.channels}, len]")
+        if lr_latent is not None and lr_latent.shape != hr_latent.shape:
+            raise ValueError(f"lr_latent {tuple(lr_latent.shape)} does not match hr_latent {tuple(hr_latent.shape)}")
+        n = int(hr_latent.shape[1])
+        first, stride = int(first), int(stride)
+        if count is None:
+            count = 0 if first >= n or stride < 1 else (n - 1 - first) // stride + 1
+        dt = torch.float16 if hr_latent.dtype == torch.float16 else torch.float32
+        hr = hr_latent.to(self.device, dt).contiguous()
+        lr = None if lr_latent is None else lr_latent.to(self.device, dt).contiguous()
+        s = self._dev_stats
+        with torch.cuda.device(self.device):
+            if self.key == "lr":
+                rc = L.lib().jat_bank_add(self._h, L.ptr(lr), L.ptr(hr), int(dt == torch.float16), n, first, stride, int(count),
+                                          L.ptr(s["lr_mean"]), L.ptr(s["lr_std"]), L.ptr(s["hr_mean"]), L.ptr(s["hr_std"]),
+                                          L.stream_ptr())
+            else:
+                rc = L.lib().jat_bank_add(self._h, L.ptr(hr), None, int(dt == torch.float16), n, first, stride, int(count),
+                                          L.ptr(s["hr_mean"]), L.ptr(s["hr_std"]), None, None, L.stream_ptr())
+        L.check(rc)
+        hr.record_stream(torch.cuda.current_stream(self.device))
+        if lr is not None:
+            lr.record_stream(torch.cuda.current_stream(self.device))
+        return int(count)
+
+    def rows(self, which="keys", full=False):
+        """The stored fp16 rows as a tensor VIEW of the bank's memory ([size, C]; full: all `capacity` rows) and, for the
+        keys, the fp32 norms.  `which`: "keys" or "values"."""
+        p, q = C.c_void_p(), C.c_void_p()
+        L.check(L.lib().jat_bank_rows(self._h, L.BANK_KEYS if which == "keys" else L.BANK_VALUES, C.byref(p), C.byref(q)))
+        n = self.capacity if full else len(self)
+        rows = _device_view(p.value, (n, self.channels), torch.float16, self.device, self)
+        norms = _device_view(q.value, (n,), torch.float32, self.device, self) if q.value else None
+        return rows, norms
+
+    def load_rows(self, keys, values=None):
+        """Append ready fp16 rows [N, C] (values exactly when key == "lr"); the norms are recomputed on the device."""
+        keys = keys.to(self.device, torch.float16).contiguous()
+        values = None if values is None else values.to(self.device, torch.float16).contiguous()
+        if keys.dim() != 2 or keys.shape[1] != self.channels or (values is not None and values.shape != keys.shape):
+            raise ValueError(f"rows {tuple(keys.shape)}, expected [N, {self.channels}]")
+        with torch.cuda.device(self.device):
+            L.check(L.lib().jat_bank_load_rows(self._h, L.ptr(keys), L.ptr(values), int(keys.shape[0]), L.stream_ptr()))
+        keys.record_stream(torch.cuda.current_stream(self.device))
+        if values is not None:
+            values.record_stream(torch.cuda.current_stream(self.device))
+
+    # ---- use ------------------------------------------------------------------------------------------------------------
+    def _x(self, x, name="x"):
+        if x.dim() != 3 or x.shape[1] != self.channels or x.dtype != torch.float32 or not x.is_cuda:
+            raise ValueError(f"{name}: expected a CUDA fp32 [B, {self.channels}, T] tensor, got {x.dtype} {tuple(x.shape)}")
+        return x.contiguous()
+
+    def workspace_bytes(self, n_queries):
+        n = C.c_size_t()
+        L.check(L.lib().jat_bank_search_workspace_bytes(self._h, int(n_queries), C.byref(n)))
+        return n.value
+
+    def search(self, x, mean=None, std=None):
+        """x fp32 [B, C, T] (normalised, or un-normalised with the key statistics given) -> (idx int32 [B, T], dist2 fp32
+        [B, T]): the nearest key row of every frame, the lowest index on equal distance, and its squared distance."""
+        x = self._x(x)
+        B, _, T = x.shape
+        if B < 1 or T < 1:
+            raise ValueError(f"x {tuple(x.shape)}: B and T must be positive")
+        need = self.workspace_bytes(B * T)
+        if self._work is None or self._work.numel() < need:
+            self._work = torch.empty(need, dtype=torch.uint8, device=self.device)
+        idx = torch.empty(B, T, dtype=torch.int32, device=self.device)
+        dist2 = torch.empty(B, T, dtype=torch.float32, device=self.device)
+        mean, std = self._vec(mean), self._vec(std)
+        with torch.cuda.device(self.device):
+            L.check(L.lib().jat_bank_search(self._h, L.ptr(x), L.ptr(mean), L.ptr(std), B, T, L.ptr(idx), L.ptr(dist2),
+                                            L.ptr(self._work), self._work.numel(), L.stream_ptr()))
+        return idx, dist2
+
+    def blend(self, x, idx, index_rate, mean=None, std=None, out=None):
+        """(1 - index_rate) * x + index_rate * value[idx]; with the value statistics the value is de-normalised first.
+        out: where to write ([B, C, T] fp32 contiguous; may be x)."""
+        r = check_index_rate(index_rate)
+        if out is None:
+            x = self._x(x)
+            out = torch.empty_like(x)
+        else:
+            if not x.is_contiguous() or not out.is_contiguous() or out.shape != x.shape or out.dtype != torch.float32:
+                raise ValueError("blend(out=...): x and out must be contiguous fp32 tensors of one shape")
+            x = self._x(x)
+        B, _, T = x.shape
+        if idx.shape != (B, T) or idx.dtype != torch.int32 or not idx.is_cuda:
+            raise ValueError(f"idx: expected CUDA int32 [{B}, {T}], got {idx.dtype} {tuple(idx.shape)}")
+        idx = idx.contiguous()
+        mean, std = self._vec(mean), self._vec(std)
+        with torch.cuda.device(self.device):
+            L.check(L.lib().jat_bank_blend(self._h, L.ptr(x), L.ptr(idx), L.ptr(mean), L.ptr(std), r, L.ptr(out), B, T,
+                                           L.stream_ptr()))
+        return out
+
+    def retrieve(self, x, index_rate, stats=None, query=None):
+        """Search + blend on a de-normalised HR latent x [B, C, T].  The query is x under the HR statistics (key == "hr") or
+        `query`, the un-normalised LR latent of the same shape, under the LR statistics (key == "lr"); the retrieved HR
+        frame is de-normalised in the blend.  stats: must be the statistics the bank was built with (default: those)."""
+        check_index_rate(index_rate)
+        if stats is not None:
+            self.check_stats(stats)
+        elif self.stats is None:
+            raise ValueError("the bank holds no statistics yet (nothing was added)")
+        s = self._dev_stats
+        if self.key == "lr":
+            if query is None:
+                raise ValueError("a bank keyed by LR frames needs the LR latent as `query`")
+            if query.shape != x.shape:
+                raise ValueError(f"query {tuple(query.shape)} does not match x {tuple(x.shape)}")
+            idx, _ = self.search(query.to(self.device, torch.float32), s["lr_mean"], s["lr_std"])
+        else:
+            idx, _ = self.search(x, s["hr_mean"], s["hr_std"])
+        return self.blend(x, idx, index_rate, s["hr_mean"], s["hr_std"])
+
+    # ---- files ----------------------------------------------------------------------------------------------------------
+    def state(self):
+        keys, _ = self.rows("keys")
+        values = self.rows("values")[0] if self.key == "lr" else None
+        if self.stats is None:
+            raise ValueError("an empty bank cannot be saved")
+        return pack_state(keys.cpu(), None if values is None else values.cpu(), self.key, self.stats)
+
+    def save(self, path):
+        torch.save(self.state(), path)
+
+    @classmethod
+    def from_state(cls, d, device="cuda", capacity=None):
+        keys, values, key, channels, stats = unpack_state(d)
+        bank = cls(channels, max(int(keys.shape[0]), int(capacity or 0)), key=key, device=device)
+        bank._set_stats(stats)
+        bank.load_rows(keys, values)
+        return bank
+
+    @classmethod
+    def load(cls, path, device="cuda"):
+        return cls.from_state(torch.load(path, map_location="cpu", weights_only=False), device=device)
+
+    @classmethod
+    def from_data_dir(cls, data_dir, stats, split="train", max_frames=100_000, key="hr", device="cuda"):
+        """A bank over the `split` of a prepared data set (`python -m jatsr_amd.prepare`): the frames `frame_plan` names,
+        files in sorted order, one file uploaded at a time."""
+        from .data import _load_fp16
+        folder = os.path.join(str(data_dir), split)
+        files = sorted(glob.glob(os.path.join(folder, "*.pt")))
+        if not files:
+            raise ValueError(f"No .pt files found in {folder}")
+        lengths, channels = [], None
+        for path in files:
+            hr, _ = _load_fp16(path)
+            if channels is None:
+                channels = int(hr.shape[0])
+            if hr.shape[0] != channels:
+                raise ValueError(f"{path}: {hr.shape[0]} channels, the files before it have {channels}")
+            lengths.append(int(hr.shape[1]))
+        plan = frame_plan(lengths, max_frames)
+        bank = cls(channels, sum(c for _, _, c in plan), key=key, device=device)
+        for path, (first, stride, count) in zip(files, plan):
+            if count == 0:
+                continue
+            hr, lr = _load_fp16(path)
+            bank.add(hr, stats, lr_latent=lr if key == "lr" else None, first=first, stride=stride, count=count)
+        return bank
+
+
+def _device_view(address, shape, dtype, device, owner):
+    """A tensor over device memory the library owns (`owner` keeps it alive)."""
+    n = 1
+    for v in shape:
+        n *= int(v)
+    if n == 0:
+        return torch.empty(shape, dtype=dtype, device=device)
+    typestr = {torch.float16: "<f2", torch.float32: "<f4"}[dtype]
+
+    class _Mem:
+        __cuda_array_interface__ = {"shape": tuple(int(v) for v in shape), "typestr": typestr, "data": (int(address), False),
+                                    "version": 2, "strides": None}
+        _owner = owner
+    return torch.as_tensor(_Mem(), device=device)
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description="latent retrieval banks (jatsr_amd.retrieval)")
+    sub = p.add_subparsers(dest="command", required=True)
+    b = sub.add_parser("build", help="build a bank file from a prepared data folder")
+    b.add_argument("--data-dir", required=True, help="prepared data folder (holds the split folders and the statistics)")
+    b.add_argument("--out", required=True, help="bank file to write (.pt)")
+    b.add_argument("--stats-file", default=None, help="normalisation statistics (default: DATA_DIR/global_stats_separated.json)")
+    b.add_argument("--split", default="train")
+    b.add_argument("--max-frames", type=int, default=100_000, help="upper bound on the rows of the bank")
+    b.add_argument("--key", default="hr", choices=["hr", "lr"], help="what a frame is looked up by")
+    b.add_argument("--device", default="cuda")
+    return p
+
+
+def main(argv=None):
+    from . import io as jio
+    args = build_parser().parse_args(argv)
+    folder = os.path.join(args.data_dir, args.split)
+    files = sorted(glob.glob(os.path.join(folder, "*.pt")))
+    if not files:
+        raise SystemExit(f"No .pt files found in {folder}")
+    channels = int(torch.load(files[0], map_location="cpu", mmap=True, weights_only=False)["hr_latent"].shape[0])
+    stats = jio.load_stats(args.stats_file or os.path.join(args.data_dir, "global_stats_separated.json"), channels=channels)
+    bank = LatentBank.from_data_dir(args.data_dir, stats, split=args.split, max_frames=args.max_frames, key=args.key,
+                                    device=args.device)
+    bank.save(args.out)
+    print(f"bank of {len(bank)} x {bank.channels} fp16 rows (key={bank.key}) from {len(files)} files -> {args.out}")
+    return args.out
+
+
+if __name__ == "__main__":
+    main()

@@ -221,14 +221,23 @@ def chunk_groups(lens, pad_short_chunks=True):
 
 @torch.no_grad()
 def sample_long(model, lr_latent, hr_mean, hr_std, lr_mean, lr_std, num_steps=50, cfg_scale=1.0,
-                chunk_frames=1378, overlap_frames=172, noise=None, pad_short_chunks=True, solver="euler", timesteps=None):
+                chunk_frames=1378, overlap_frames=172, noise=None, pad_short_chunks=True, solver="euler", timesteps=None,
+                bank=None, index_rate=0.0):
     """Chunked long-sequence inference == the chunk loop of infer_test_v3m2.py:340-404, with the chunks of a file
     BATCHED into one sampler launch instead of the reference's serial B=1 loop (pad_short_chunks=False: one launch
     per distinct chunk length, the round-1 behaviour).
 
     lr_latent: [C, T_total] un-normalised latent.  noise: optional list of per-chunk z0 tensors [1,C,T_i].
     Returns [1, C, T_total] de-normalised generated latent.
+
+    bank (a `jatsr_amd.retrieval.LatentBank`) with index_rate > 0: latent retrieval on the whole cross-faded output, once —
+    every frame is looked up in the bank (by its own content under the HR statistics, or by the LR input under the LR
+    statistics when the bank is keyed by LR frames) and index_rate of the retrieved HR frame is mixed in.  Without a bank, or
+    at index_rate 0, nothing more is launched.
     """
+    index_rate = float(index_rate)
+    if not 0.0 <= index_rate <= 1.0:
+        raise ValueError(f"index_rate {index_rate!r} outside [0, 1]")
     Cc, total = lr_latent.shape
     plan = chunk_plan(total, chunk_frames, overlap_frames)
     lr = lr_latent.unsqueeze(0)
@@ -264,4 +273,8 @@ def sample_long(model, lr_latent, hr_mean, hr_std, lr_mean, lr_std, num_steps=50
         gen = channel_affine(gen, hr_mean, hr_std, inverse=True)
         for j, i in enumerate(idxs):
             outs[i] = gen[j:j + 1, :, :lens[i]].contiguous()
-    return crossfade_chunks(outs, overlap_frames)
+    out = crossfade_chunks(outs, overlap_frames)
+    if bank is None or index_rate == 0.0:
+        return out
+    stats = {"hr_mean": hr_mean, "hr_std": hr_std, "lr_mean": lr_mean, "lr_std": lr_std}
+    return bank.retrieve(out, index_rate, stats=stats, query=lr.float() if bank.key == "lr" else None)
