@@ -116,6 +116,7 @@ extern "C" int jat_model_create(const jat_config* c, jat_model** out) {
     if (sscanf(v, "%d,%d,%d,%d,%d", &x[0], &x[1], &x[2], &x[3], &x[4]) == 5)
       for (int i = 0; i < 5; ++i) m->variants[i] = x[i];
   }
+  jat_describe_params(m);
   *out = m;
   return JAT_OK;
 }
@@ -141,175 +142,97 @@ extern "C" void jat_model_destroy(jat_model* m) {
 
 extern "C" int jat_model_load_weights(jat_model* m, const jat_tensor_ref* named, int32_t n, void* stream_) {
   if (!m || !named) return fail(JAT_E_INVALID, "null argument");
-  return jat_pack_weights(m, named, n, (hipStream_t)stream_, true);
+  return jat_pack_weights(m, named, n, (hipStream_t)stream_);
 }
 
-// build_tables == false: re-pack after an optimiser step (jat_train.cpp) — conversions only, no host synchronisation
-int jat_pack_weights(jat_model* m, const jat_tensor_ref* named, int32_t n, hipStream_t s, bool build_tables) {
+int jat_pack_weights(jat_model* m, const jat_tensor_ref* named, int32_t n, hipStream_t s) {
   std::unordered_map<std::string, const jat_tensor_ref*> by_name;
   for (int i = 0; i < n; ++i) by_name[named[i].name] = &named[i];
-  const int D = m->D, kvD = m->kvD, mlp = m->mlp, bott = m->bott, depth = m->depth;
-  const bool rms = m->cfg.norm_mode == JAT_NORM_RMS_W;
-
-  // ---- layout of the packed blob ----
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes, 256); return o; };
-  const size_t o_pe_w1 = take((size_t)bott * m->Kp * 2), o_pe_w2 = take((size_t)D * bott * 2);
-  const size_t o_wada = take((size_t)depth * 6 * D * D * 2), o_wfinal = take((size_t)m->Fout * D * 2);
-  std::vector<size_t> o_qkv(depth), o_wo(depth), o_w1(depth), o_w2(depth), o_n1(depth), o_n2(depth), o_b1(depth),
-      o_b2(depth), o_qkvg(depth), o_q32(depth), o_k32(depth), o_v32(depth), o_w132(depth);
-  const bool keep32 = rms;   // fold sources (RMSNorm models only)
-  const bool group5 = m->Hq / m->Hkv == 5;
-  for (int l = 0; l < depth; ++l) {
-    o_qkv[l] = take((size_t)(D + 2 * kvD) * D * 2); o_wo[l] = take((size_t)D * D * 2);
-    o_qkvg[l] = group5 ? take((size_t)(D + 2 * kvD) * D * 2) : 0;
-    o_w1[l] = take((size_t)mlp * D * 2); o_w2[l] = take((size_t)D * mlp * 2);
-    o_n1[l] = take((size_t)D * 4); o_n2[l] = take((size_t)D * 4);
-    o_b1[l] = take((size_t)mlp * 4); o_b2[l] = take((size_t)D * 4);
-    if (keep32) {
-      o_q32[l] = take((size_t)D * D * 4); o_k32[l] = take((size_t)kvD * D * 4); o_v32[l] = take((size_t)kvD * D * 4);
-      o_w132[l] = take((size_t)mlp * D * 4);
-    }
+  // every parameter present and of the expected size, before anything is allocated or converted
+  std::vector<const float*> src(m->params.size(), nullptr);
+  for (size_t i = 0; i < m->params.size(); ++i) {
+    const ParamDesc& e = m->params[i];
+    if (!m->has(e)) continue;
+    auto it = by_name.find(e.name);
+    if (it == by_name.end()) return fail(JAT_E_STATE, "missing parameter '%s'", e.name.c_str());
+    if (it->second->numel != e.numel())
+      return fail(JAT_E_INVALID, "parameter '%s' has %lld elements, expected %lld", e.name.c_str(),
+                  (long long)it->second->numel, (long long)e.numel());
+    src[i] = it->second->data;
   }
-  const size_t o_wfinal32 = keep32 ? take((size_t)m->Fout * D * 4) : 0;
-  const size_t o_pe_b1 = take((size_t)bott * 4), o_pe_b2 = take((size_t)D * 4);
-  const size_t o_te_w1 = take((size_t)D * D * 4), o_te_b1 = take((size_t)D * 4);
-  const size_t o_te_w2 = take((size_t)D * D * 4), o_te_b2 = take((size_t)D * 4);
-  const size_t o_bada = take((size_t)depth * 6 * D * 4), o_fn = take((size_t)D * 4), o_bfinal = take((size_t)m->Fout * 4);
-  const size_t o_cos = take((size_t)MAX_LEN * 32 * 4), o_sin = take((size_t)MAX_LEN * 32 * 4), o_invf = take(32 * 4);
+  auto source = [&](int id, int block) -> const float* {
+    for (size_t i = 0; i < src.size(); ++i)
+      if (m->params[i].id == id && m->params[i].block == block) return src[i];
+    return nullptr;
+  };
   if (!m->blob) {
-    HIPCHK(hipMalloc((void**)&m->blob, off));
-    m->blob_bytes = off;
-  }
-  char* base = m->blob;
-  m->pe_w1 = (bf16_t*)(base + o_pe_w1); m->pe_w2 = (bf16_t*)(base + o_pe_w2);
-  m->wada = (bf16_t*)(base + o_wada); m->wfinal = (bf16_t*)(base + o_wfinal);
-  m->pe_b1 = (float*)(base + o_pe_b1); m->pe_b2 = (float*)(base + o_pe_b2);
-  m->te_w1 = (float*)(base + o_te_w1); m->te_b1 = (float*)(base + o_te_b1);
-  m->te_w2 = (float*)(base + o_te_w2); m->te_b2 = (float*)(base + o_te_b2);
-  m->bada = (float*)(base + o_bada); m->final_norm = (float*)(base + o_fn); m->bfinal = (float*)(base + o_bfinal);
-  m->rope_cos = (float*)(base + o_cos); m->rope_sin = (float*)(base + o_sin); m->rope_invf = (float*)(base + o_invf);
-  m->layers.resize(depth);
-  for (int l = 0; l < depth; ++l) {
-    LayerW& L = m->layers[l];
-    L.wqkv = (bf16_t*)(base + o_qkv[l]); L.wo = (bf16_t*)(base + o_wo[l]);
-    L.wqkv_g = group5 ? (bf16_t*)(base + o_qkvg[l]) : nullptr;
-    L.w1 = (bf16_t*)(base + o_w1[l]); L.w2 = (bf16_t*)(base + o_w2[l]);
-    L.norm1 = (float*)(base + o_n1[l]); L.norm2 = (float*)(base + o_n2[l]);
-    L.b1 = (float*)(base + o_b1[l]); L.b2 = (float*)(base + o_b2[l]);
-    if (keep32) {
-      L.q32 = (float*)(base + o_q32[l]); L.k32 = (float*)(base + o_k32[l]); L.v32 = (float*)(base + o_v32[l]);
-      L.w132 = (float*)(base + o_w132[l]);
+    HIPCHK(hipMalloc((void**)&m->blob, m->blob_bytes));
+    for (const BlobSlot& t : m->slots) {
+      if (t.h) *t.h = (bf16_t*)(m->blob + t.off);
+      else *t.f = (float*)(m->blob + t.off);
     }
   }
-  m->wfinal32 = keep32 ? (float*)(base + o_wfinal32) : nullptr;
   m->fold_cache.clear();   // folded tables belong to the previous weights (samplers that still hold one keep it alive)
   m->fold_src_ok = false;
 
-  // ---- copy / convert ----
-  int rc = JAT_OK;
-  auto find = [&](const std::string& name, int64_t numel) -> const float* {
-    auto it = by_name.find(name);
-    if (it == by_name.end()) { rc = fail(JAT_E_STATE, "missing parameter '%s'", name.c_str()); return nullptr; }
-    if (it->second->numel != numel) {
-      rc = fail(JAT_E_INVALID, "parameter '%s' has %lld elements, expected %lld", name.c_str(),
-                (long long)it->second->numel, (long long)numel);
-      return nullptr;
+  // ---- the parameters: copy / convert each to its operand copy ----
+  for (size_t i = 0; i < m->params.size(); ++i) {
+    const ParamDesc& e = m->params[i];
+    if (e.form == F_BF16_ROPE) {
+      KCHK(launch_cast_bf16_rope_rows(src[i], m->at<bf16_t>(e), e.rows, e.cols, s));
+    } else if (e.form == F_BF16) {
+      KCHK(launch_cast_bf16(src[i], m->at<bf16_t>(e), e.numel(), s));
+    } else if (m->has(e)) {
+      HIPCHK(hipMemcpyAsync(m->at<float>(e), src[i], e.numel() * 4, hipMemcpyDeviceToDevice, s));
     }
-    return it->second->data;
-  };
-  auto to_bf16 = [&](const std::string& name, bf16_t* dst, int64_t numel) {
-    const float* src = find(name, numel);
-    if (!src) return;
-    if (launch_cast_bf16(src, dst, numel, s) != hipSuccess) rc = fail(JAT_E_HIP, "cast kernel launch failed");
-  };
-  auto to_bf16_rope = [&](const std::string& name, bf16_t* dst, int rows, int cols) {
-    const float* src = find(name, (int64_t)rows * cols);
-    if (!src) return;
-    if (launch_cast_bf16_rope_rows(src, dst, rows, cols, s) != hipSuccess) rc = fail(JAT_E_HIP, "cast kernel launch failed");
-  };
-  auto to_f32 = [&](const std::string& name, float* dst, int64_t numel) {
-    const float* src = find(name, numel);
-    if (!src) return;
-    if (hipMemcpyAsync(dst, src, numel * 4, hipMemcpyDeviceToDevice, s) != hipSuccess)
-      rc = fail(JAT_E_HIP, "memcpy failed for '%s'", name.c_str());
-  };
-  auto ones = [&](float* dst, int64_t numel) {
-    if (!build_tables) return;  // constants: written once at load time
-    std::vector<float> h(numel, 1.0f);
-    if (hipMemcpyAsync(dst, h.data(), numel * 4, hipMemcpyHostToDevice, s) != hipSuccess) rc = fail(JAT_E_HIP, "memcpy");
-    (void)hipStreamSynchronize(s);
-  };
-  to_bf16("patch_embed.proj.0.weight", m->pe_w1, (int64_t)bott * m->Kp);
-  to_f32("patch_embed.proj.0.bias", m->pe_b1, bott);
-  to_bf16("patch_embed.proj.2.weight", m->pe_w2, (int64_t)D * bott);
-  to_f32("patch_embed.proj.2.bias", m->pe_b2, D);
-  to_f32("t_embedder.1.weight", m->te_w1, (int64_t)D * D);
-  to_f32("t_embedder.1.bias", m->te_b1, D);
-  to_f32("t_embedder.3.weight", m->te_w2, (int64_t)D * D);
-  to_f32("t_embedder.3.bias", m->te_b2, D);
-  for (int l = 0; l < depth && rc == JAT_OK; ++l) {
-    const std::string p = "blocks." + std::to_string(l) + ".";
-    LayerW& L = m->layers[l];
-    if (rms) { to_f32(p + "norm1.weight", L.norm1, D); to_f32(p + "norm2.weight", L.norm2, D); }
-    else { ones(L.norm1, D); ones(L.norm2, D); }
-    // fused [Wq; Wk; Wv]; q/k rows pair-interleaved per head so that RoPE pairs share a lane (gemm.hip)
-    to_bf16_rope(p + "attn.q_proj.weight", L.wqkv, D, D);
-    to_bf16_rope(p + "attn.k_proj.weight", L.wqkv + (int64_t)D * D, kvD, D);
-    to_bf16(p + "attn.v_proj.weight", L.wqkv + (int64_t)(D + kvD) * D, (int64_t)kvD * D);
-    if (group5 && rc == JAT_OK) {  // group-major copy: per KV head g: 5 q heads, its k head, its v head
-      const float* wq = find(p + "attn.q_proj.weight", (int64_t)D * D);
-      const float* wk = find(p + "attn.k_proj.weight", (int64_t)kvD * D);
-      const float* wv = find(p + "attn.v_proj.weight", (int64_t)kvD * D);
-      for (int g = 0; g < m->Hkv && wq && wk && wv; ++g) {
-        bf16_t* dst = L.wqkv_g + (int64_t)g * 448 * D;
-        if (launch_cast_bf16_rope_rows(wq + (int64_t)g * 320 * D, dst, 320, D, s) != hipSuccess ||
-            launch_cast_bf16_rope_rows(wk + (int64_t)g * 64 * D, dst + (int64_t)320 * D, 64, D, s) != hipSuccess ||
-            launch_cast_bf16(wv + (int64_t)g * 64 * D, dst + (int64_t)384 * D, (int64_t)64 * D, s) != hipSuccess)
-          rc = fail(JAT_E_HIP, "group-major qkv pack failed");
-      }
-    }
-    if (keep32 && build_tables) {   // fold sources: refreshed on a full load only (a training re-pack leaves them stale)
-      to_f32(p + "attn.q_proj.weight", L.q32, (int64_t)D * D);
-      to_f32(p + "attn.k_proj.weight", L.k32, (int64_t)kvD * D);
-      to_f32(p + "attn.v_proj.weight", L.v32, (int64_t)kvD * D);
-      to_f32(p + "mlp.0.weight", L.w132, (int64_t)mlp * D);
-    }
-    to_bf16(p + "attn.out_proj.weight", L.wo, (int64_t)D * D);
-    to_bf16(p + "mlp.0.weight", L.w1, (int64_t)mlp * D);
-    to_f32(p + "mlp.0.bias", L.b1, mlp);
-    to_bf16(p + "mlp.3.weight", L.w2, (int64_t)D * mlp);
-    to_f32(p + "mlp.3.bias", L.b2, D);
-    to_bf16(p + "adaLN_modulation.1.weight", m->wada + (int64_t)l * 6 * D * D, (int64_t)6 * D * D);
-    to_f32(p + "adaLN_modulation.1.bias", m->bada + (int64_t)l * 6 * D, (int64_t)6 * D);
   }
-  if (rms) to_f32("final_layer.0.weight", m->final_norm, D); else ones(m->final_norm, D);
-  to_bf16("final_layer.1.weight", m->wfinal, (int64_t)m->Fout * D);
-  if (keep32 && build_tables) to_f32("final_layer.1.weight", m->wfinal32, (int64_t)m->Fout * D);
-  to_f32("final_layer.1.bias", m->bfinal, m->Fout);
-  if (rc != JAT_OK) return rc;
 
-  // RoPE tables in fp32 exactly as RoPE.__init__ builds them (jat_audiosr_v3.py:77-85); only the first half
-  // of `emb = cat([freqs, freqs])` is distinct.
-  if (build_tables) {
-    std::vector<float> hc((size_t)MAX_LEN * 32), hs((size_t)MAX_LEN * 32), hf(32);
-    for (int i = 0; i < 32; ++i) {
-      const float inv_freq = 1.0f / powf(10000.0f, (float)(2 * i) / 64.0f);
-      hf[i] = inv_freq;
-      for (int pos = 0; pos < MAX_LEN; ++pos) {
-        const float a = (float)pos * inv_freq;
-        hc[(size_t)pos * 32 + i] = cosf(a);
-        hs[(size_t)pos * 32 + i] = sinf(a);
-      }
-    }
-    HIPCHK(hipMemcpyAsync(m->rope_cos, hc.data(), hc.size() * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(m->rope_sin, hs.data(), hs.size() * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(m->rope_invf, hf.data(), hf.size() * 4, hipMemcpyHostToDevice, s));
+  // ---- what is not a parameter: constant-ones norm weights (LayerNorm models), group-major QKV (group5), fold sources (keep32) ----
+  const int D = m->D, kvD = m->kvD;
+  const bool group5 = m->layers[0].wqkv_g != nullptr, keep32 = m->wfinal32 != nullptr;   // as laid out by jat_describe_params
+  for (const ParamDesc& e : m->params) {
+    if (m->has(e)) continue;
+    const std::vector<float> ones(e.numel(), 1.0f);
+    HIPCHK(hipMemcpyAsync(m->at<float>(e), ones.data(), e.numel() * 4, hipMemcpyHostToDevice, s));
     HIPCHK(hipStreamSynchronize(s));
   }
-  if (build_tables) HIPCHK(hipStreamSynchronize(s));
+  for (int l = 0; l < m->depth; ++l) {
+    const LayerW& L = m->layers[l];
+    const float *wq = source(P_Q, l), *wk = source(P_K, l), *wv = source(P_V, l);
+    if (group5) {     // group-major copy: per KV head g: 5 q heads, its k head, its v head
+      for (int g = 0; g < m->Hkv; ++g) {
+        bf16_t* dst = L.wqkv_g + (int64_t)g * 448 * D;
+        KCHK(launch_cast_bf16_rope_rows(wq + (int64_t)g * 320 * D, dst, 320, D, s));
+        KCHK(launch_cast_bf16_rope_rows(wk + (int64_t)g * 64 * D, dst + (int64_t)320 * D, 64, D, s));
+        KCHK(launch_cast_bf16(wv + (int64_t)g * 64 * D, dst + (int64_t)384 * D, (int64_t)64 * D, s));
+      }
+    }
+    if (keep32) {     // fold sources: refreshed on a full load only (a training re-pack leaves them stale)
+      HIPCHK(hipMemcpyAsync(L.q32, wq, (size_t)D * D * 4, hipMemcpyDeviceToDevice, s));
+      HIPCHK(hipMemcpyAsync(L.k32, wk, (size_t)kvD * D * 4, hipMemcpyDeviceToDevice, s));
+      HIPCHK(hipMemcpyAsync(L.v32, wv, (size_t)kvD * D * 4, hipMemcpyDeviceToDevice, s));
+      HIPCHK(hipMemcpyAsync(L.w132, source(P_W1, l), (size_t)m->mlp * D * 4, hipMemcpyDeviceToDevice, s));
+    }
+  }
+  if (keep32) HIPCHK(hipMemcpyAsync(m->wfinal32, source(P_WF, m->depth), (size_t)m->Fout * D * 4, hipMemcpyDeviceToDevice, s));
+  // RoPE tables in fp32 exactly as RoPE.__init__ builds them (jat_audiosr_v3.py:77-85); only the first half
+  // of `emb = cat([freqs, freqs])` is distinct.
+  std::vector<float> hc((size_t)MAX_LEN * 32), hs((size_t)MAX_LEN * 32), hf(32);
+  for (int i = 0; i < 32; ++i) {
+    const float inv_freq = 1.0f / powf(10000.0f, (float)(2 * i) / 64.0f);
+    hf[i] = inv_freq;
+    for (int pos = 0; pos < MAX_LEN; ++pos) {
+      const float a = (float)pos * inv_freq;
+      hc[(size_t)pos * 32 + i] = cosf(a);
+      hs[(size_t)pos * 32 + i] = sinf(a);
+    }
+  }
+  HIPCHK(hipMemcpyAsync(m->rope_cos, hc.data(), hc.size() * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(m->rope_sin, hs.data(), hs.size() * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(m->rope_invf, hf.data(), hf.size() * 4, hipMemcpyHostToDevice, s));
+  HIPCHK(hipStreamSynchronize(s));
   m->group_copy_stale = false;
-  m->fold_src_ok = keep32 && build_tables;
+  m->fold_src_ok = keep32;
   m->loaded = true;
   return JAT_OK;
 }

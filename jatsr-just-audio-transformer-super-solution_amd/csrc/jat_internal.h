@@ -34,6 +34,34 @@ static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; 
 static constexpr int MAX_LEN = 2048;  // jat_audiosr_v3.py:361
 static constexpr int HEAD_DIM = 64;
 
+// One model parameter, described once (jat_params.cpp): its name in the reference's state_dict, its size, the form the kernels
+// read it in, where that operand copy lives in the packed allocation, the block it belongs to.  The loader, the trainer's table
+// validation and the trainer's re-pack all walk jat_model::params.
+enum ParamId {
+  P_PE_W1, P_PE_B1, P_PE_W2, P_PE_B2, P_TE_W1, P_TE_B1, P_TE_W2, P_TE_B2,                   // head: patch embed, t_embedder
+  P_N1, P_N2, P_Q, P_K, P_V, P_O, P_W1, P_B1, P_W2, P_B2, P_ADA_W, P_ADA_B,                 // one of each per block
+  P_FN, P_WF, P_BF,                                                                         // final layer
+  P_COUNT
+};
+enum ParamForm { F_F32, F_BF16, F_BF16_ROPE };   // fp32 copy, operand-dtype cast, cast with q/k rows pair-interleaved per head (RoPE pairs share a lane)
+struct ParamDesc {
+  int id;             // ParamId
+  int block;          // -1: head, 0 .. depth-1: that block, depth: final layer
+  std::string name;
+  int rows, cols;     // numel = rows * cols (a vector: cols == 1)
+  ParamForm form;
+  size_t dst;         // byte offset of the operand copy in jat_model::blob (a slice of a shared tensor: K and V inside wqkv,
+                      // block l's rows of wada / bada)
+  bool rms_only;      // a norm weight: no source tensor in a LayerNorm model, whose copy is constant ones
+  int64_t numel() const { return (int64_t)rows * cols; }
+};
+// a pointer of jat_model / LayerW into the packed allocation: *field = blob + off once the blob exists
+struct BlobSlot {
+  size_t off;
+  bf16_t** h;
+  float** f;
+};
+
 struct LayerW {
   bf16_t *wqkv, *wo, *w1, *w2;  // [D+2kvD, D], [D, D], [mlp, D], [D, mlp]
   bf16_t* wqkv_g = nullptr;     // group-major copy [Hkv][5*64 + 64 + 64][D] for the fused QKV+attention kernel (Hq/Hkv == 5)
@@ -80,15 +108,19 @@ struct jat_model {
   mutable GemmProf prof;
   int D, depth, Hq, Hkv, kvD, mlp, bott, Cin, Cc, P, Kp, Fout;
   bool loaded = false;
-  char* blob = nullptr;  // one device allocation holding every packed tensor
+  char* blob = nullptr;  // one device allocation holding every packed tensor (allocated by the first load)
   size_t blob_bytes = 0;
+  std::vector<ParamDesc> params;   // head, blocks 0 .. depth-1, final layer; built with the blob's layout by jat_describe_params
+  std::vector<BlobSlot> slots;
+  bool has(const ParamDesc& e) const { return !e.rms_only || cfg.norm_mode == JAT_NORM_RMS_W; }
+  template <class T> T* at(const ParamDesc& e) const { return (T*)(blob + e.dst); }
   bf16_t *pe_w1, *pe_w2, *wada, *wfinal;
   float *pe_b1, *pe_b2, *te_w1, *te_b1, *te_w2, *te_b2, *bada, *final_norm, *bfinal, *rope_cos, *rope_sin, *rope_invf;
   std::vector<LayerW> layers;
   // GEMM tile/pipeline variant per call site: qkv, out_proj, fc1, fc2, everything else (gemm_variants.h)
   int variants[5] = {-1, -1, -1, -1, -1};  // -1: choose by shape (gemm_plan.h)
   mutable int last_fold_np = 0;            // partial-sum slots per row written by the latest folding producer
-  float* wfinal32 = nullptr;               // fp32 copy of final_layer.1.weight (fold source)
+  float* wfinal32 = nullptr;               // fp32 copy of the final Linear's weight (fold source)
   bool fold_src_ok = false;                // fp32 copies match the packed weights (false after a training re-pack)
   std::map<std::vector<uint32_t>, std::shared_ptr<FoldTable>> fold_cache;   // by the list of distinct evaluation times (fp32 bits); dropped whenever the weights change
   bool group_copy_stale = false;           // the training re-pack skips wqkv_g: the fused QKV+attention kernel is off until
@@ -101,8 +133,13 @@ enum { G_QKV = 0, G_OUT = 1, G_FC1 = 2, G_FC2 = 3, G_OTHER = 4 };
 struct GemmPlan;
 int jat_gemm(const jat_model* m, int site, const bf16_t* A, int64_t lda, const bf16_t* W, int64_t ldw, int M, int N, int K,
              int epi, GemmArgs extra, hipStream_t s, const GemmPlan* plan = nullptr);
-// (re)pack the bf16 / fp32 device copies of the model from named fp32 tensors; sync_tables: also (re)build the RoPE tables
-int jat_pack_weights(jat_model* m, const jat_tensor_ref* named, int32_t n, hipStream_t s, bool build_tables);
+// jat_params.cpp: lay out the packed allocation (m->blob_bytes, m->slots) and describe every parameter (m->params) from the
+// configuration alone; allocates and launches nothing.  Called once, by jat_model_create.
+void jat_describe_params(jat_model* m);
+// Full load (jat_model_load_weights): every parameter of m->params looked up by name, checked and converted to its operand
+// copy, then the derived copies (group-major QKV, fold sources, constant-ones norm weights, RoPE tables); synchronises `s`.
+// The trainer's re-pack after an optimiser step is jat_train.cpp's repack(), which walks the same table.
+int jat_pack_weights(jat_model* m, const jat_tensor_ref* named, int32_t n, hipStream_t s);
 
 // One weight gradient dW[out,in] = dY^T X (+ db[out] = column sums of dY when db) from token-major dY [tokens,out], X [tokens,in]
 // (gemm_tn.hip): the GEMM, the ordered sum of its K slices when ksplit > 1, the column sum.  acc: added into dW / db, in the GEMM's

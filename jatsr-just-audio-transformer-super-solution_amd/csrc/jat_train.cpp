@@ -27,8 +27,7 @@ struct TLayer {
   float *x_mid, *lse;
   bf16_t *xn1, *q, *k, *vt, *ao, *y_attn, *xn2, *h_pre, *h_post, *y_mlp;
   bf16_t *wqkvT, *woT, *w1T, *w2T;
-  // gradient / master-parameter offsets (floats) into the flat buffers
-  int64_t o_n1, o_n2, o_q, o_k, o_v, o_o, o_w1, o_b1, o_w2, o_b2, o_ada_w, o_ada_b;
+  int64_t off[P_COUNT];   // by ParamId: where this block's parameters (and their gradients) start in the flat buffers, in floats
 };
 
 }  // namespace
@@ -40,8 +39,6 @@ struct jat_trainer {
   float* ema = nullptr;                // caller-owned moving average of P (jat_trainer_set_ema); nullptr: off
   float ema_decay = 0.f;
   int64_t total = 0;
-  std::vector<std::string> names;
-  std::vector<jat_tensor_ref> prefs;   // name -> pointer into P (for the re-pack)
   char* blob = nullptr;
   size_t blob_bytes = 0;
   std::vector<float*> x;               // depth + 1 residual-stream snapshots [M, D]
@@ -51,7 +48,8 @@ struct jat_trainer {
   // backward scratch
   float *dx, *dpred, *dmod, *part, *red_part, *scal, *delta, *dwqkv, *dt_emb, *du1, *small_part;
   bf16_t *dy, *dh, *dxn, *dao, *dqkv, *dyf;
-  int64_t o_pe_w1, o_pe_b1, o_pe_w2, o_pe_b2, o_te_w1, o_te_b1, o_te_w2, o_te_b2, o_fn, o_wf, o_bf;
+  int64_t off[P_COUNT];                // by ParamId: the head's and the final layer's parameters in the flat buffers (floats)
+  int64_t& offset_of(const ParamDesc& e) { return (e.block >= 0 && e.block < (int)L.size() ? L[e.block].off : off)[e.id]; }
   bool rms = true;
   // gradient-ready hook (DDP overlap): called on the host, during enqueue, once the last kernel writing the slice
   // grads_flat[off, off + n) has been enqueued — final layer first, then blocks depth-1 .. 0, then patch embed + t_embedder
@@ -112,25 +110,15 @@ int build_transposes(jat_trainer* tr, hipStream_t s) {
 // The group-major QKV copy of the fused inference kernel is NOT rebuilt (m->group_copy_stale).
 int repack(jat_trainer* tr, hipStream_t s) {
   jat_model* m = tr->m;
-  const float* P = tr->P;
-  const int D = m->D, kvD = m->kvD, mlp = m->mlp;
   m->group_copy_stale = true;
   m->fold_src_ok = false;    // the sampler's folded-weight tables (jat_api.cpp FoldTable) describe the previous weights:
   m->fold_cache.clear();     // samplers created from now on run the norm kernels until the next full load
-  KCHK(launch_multi_copy(tr->copy_jobs, tr->n_copy_jobs, s));
-  KCHK(launch_cast_bf16(P + tr->o_pe_w1, m->pe_w1, (int64_t)m->bott * m->Kp, s));
-  KCHK(launch_cast_bf16(P + tr->o_pe_w2, m->pe_w2, (int64_t)D * m->bott, s));
-  KCHK(launch_cast_bf16(P + tr->o_wf, m->wfinal, (int64_t)m->Fout * D, s));
-  for (int l = 0; l < m->depth; ++l) {
-    const LayerW& W = m->layers[l];
-    const TLayer& L = tr->L[l];
-    KCHK(launch_cast_bf16_rope_rows(P + L.o_q, W.wqkv, D, D, s));
-    KCHK(launch_cast_bf16_rope_rows(P + L.o_k, W.wqkv + (int64_t)D * D, kvD, D, s));
-    KCHK(launch_cast_bf16(P + L.o_v, W.wqkv + (int64_t)(D + kvD) * D, (int64_t)kvD * D, s));
-    KCHK(launch_cast_bf16(P + L.o_o, W.wo, (int64_t)D * D, s));
-    KCHK(launch_cast_bf16(P + L.o_w1, W.w1, (int64_t)mlp * D, s));
-    KCHK(launch_cast_bf16(P + L.o_w2, W.w2, (int64_t)D * mlp, s));
-    KCHK(launch_cast_bf16(P + L.o_ada_w, m->wada + (int64_t)l * 6 * D * D, (int64_t)6 * D * D, s));
+  KCHK(launch_multi_copy(tr->copy_jobs, tr->n_copy_jobs, s));   // the fp32 parameters
+  for (const ParamDesc& e : m->params) {
+    if (e.form == F_F32) continue;
+    const float* src = tr->P + tr->offset_of(e);
+    if (e.form == F_BF16_ROPE) KCHK(launch_cast_bf16_rope_rows(src, m->at<bf16_t>(e), e.rows, e.cols, s));
+    else KCHK(launch_cast_bf16(src, m->at<bf16_t>(e), e.numel(), s));
   }
   if (tr->dw_async) {
     // the transposed copies are read by the NEXT backward only (dX = dY W): rebuilt on the second stream, under the next forward
@@ -300,10 +288,10 @@ int backward_train(jat_trainer* tr, const float* target, const float* cond_clean
     if (tr->dw_async) HIPCHK(hipStreamWaitEvent(s, tr->ev_wt, 0));   // the transposed weight copies of the last re-pack (repack())
     JCHK(input_grad(tr, tr->dyf, m->Fout, tr->wfinalT, D, tr->dxn, s));
     if (tr->dw_async) { HIPCHK(hipEventRecord(tr->ev_join, s)); HIPCHK(hipStreamWaitEvent(ws, tr->ev_join, 0)); }
-    JCHK(weight_grad(tr, tr->dyf, m->Fout, tr->xnf, D, G + tr->o_wf, G + tr->o_bf, acc, ws));
+    JCHK(weight_grad(tr, tr->dyf, m->Fout, tr->xnf, D, G + tr->off[P_WF], G + tr->off[P_BF], acc, ws));
     if (tr->dw_async) HIPCHK(hipEventRecord(tr->ev_layer[m->depth], ws));
     KCHK(launch_norm_bwd(tr->x[m->depth], tr->dxn, m->final_norm, nullptr, 0, tr->dx, 0, tr->part, tr->dw_part, nullptr, nullptr, 0,
-                         tr->rms ? G + tr->o_fn : nullptr, acc, B, D, ntok, mode, s));
+                         tr->rms ? G + tr->off[P_FN] : nullptr, acc, B, D, ntok, mode, s));
     if (tr->dw_async) pending_hook = m->depth; else JCHK(fire_hook(m->depth));
     for (int l = m->depth - 1; l >= 0; --l) {
       TLayer& L = tr->L[l];
@@ -318,22 +306,22 @@ int backward_train(jat_trainer* tr, const float* target, const float* cond_clean
       JCHK(before_write(tr->ev_done[1][par]));
       JCHK(input_grad(tr, dy_m, D, L.w2T, m->mlp, dh, s));
       JCHK(dw_begin(tr->ev_ready[0][par]));
-      JCHK(weight_grad(tr, dy_m, D, L.h_post, m->mlp, G + L.o_w2, G + L.o_b2, acc, ws));
+      JCHK(weight_grad(tr, dy_m, D, L.h_post, m->mlp, G + L.off[P_W2], G + L.off[P_B2], acc, ws));
       JCHK(dw_end(tr->ev_done[0][par]));
       KCHK(launch_gelu_bwd(L.h_pre, dh, (int64_t)M * m->mlp, site(tr, l, 2), s));
       JCHK(input_grad(tr, dh, m->mlp, L.w1T, D, tr->dxn, s));
       JCHK(dw_begin(tr->ev_ready[1][par]));
-      JCHK(weight_grad(tr, dh, m->mlp, L.xn2, D, G + L.o_w1, G + L.o_b1, acc, ws));
+      JCHK(weight_grad(tr, dh, m->mlp, L.xn2, D, G + L.off[P_W1], G + L.off[P_B1], acc, ws));
       JCHK(dw_end(tr->ev_done[1][par]));
       KCHK(launch_norm_bwd(L.x_mid, tr->dxn, m->layers[l].norm2, mod + 4 * D, mstride, tr->dx, 1, tr->part, tr->dw_part, dmod + 3 * D,
-                           dmod + 4 * D, mstride, tr->rms ? G + L.o_n2 : nullptr, acc, B, D, ntok, mode, s));
+                           dmod + 4 * D, mstride, tr->rms ? G + L.off[P_N2] : nullptr, acc, B, D, ntok, mode, s));
       // x_mid = x_in + gate_msa * out_proj(attn(norm1(x_in) * (1 + scale_msa) + shift_msa))   :297-300
       JCHK(before_write(tr->ev_done[2][par]));
       KCHK(launch_gate_bwd(tr->dx, L.y_attn, mod + 2 * D, mstride, dy_a, tr->part, dmod + 2 * D, mstride, B, D, ntok,
                            site(tr, l, 1), kNoDrop, s));
       JCHK(input_grad(tr, dy_a, D, L.woT, D, tr->dao, s));
       JCHK(dw_begin(tr->ev_ready[2][par]));
-      JCHK(weight_grad(tr, dy_a, D, L.ao, D, G + L.o_o, nullptr, acc, ws));
+      JCHK(weight_grad(tr, dy_a, D, L.ao, D, G + L.off[P_O], nullptr, acc, ws));
       JCHK(dw_end(tr->ev_done[2][par]));
       JCHK(before_write(tr->ev_done[3][par]));
       KCHK(launch_attention_bwd(L.q, L.k, L.vt, L.ao, tr->dao, L.lse, tr->delta, dq, m->rope_cos, m->rope_sin, B, ntok,
@@ -341,14 +329,14 @@ int backward_train(jat_trainer* tr, const float* target, const float* cond_clean
       JCHK(input_grad(tr, dq, Nqkv, L.wqkvT, D, tr->dxn, s));
       JCHK(dw_begin(tr->ev_ready[3][par]));
       JCHK(weight_grad(tr, dq, Nqkv, L.xn1, D, tr->dwqkv, nullptr, false, ws));   // scratch: the unpack below is what accumulates
-      KCHK(launch_unpack_qkv_grad(tr->dwqkv, G + L.o_q, G + L.o_k, G + L.o_v, D, m->kvD, D, acc, ws));
+      KCHK(launch_unpack_qkv_grad(tr->dwqkv, G + L.off[P_Q], G + L.off[P_K], G + L.off[P_V], D, m->kvD, D, acc, ws));
       JCHK(dw_end(tr->ev_done[3][par]));
       KCHK(launch_norm_bwd(tr->x[l], tr->dxn, m->layers[l].norm1, mod + 1 * D, mstride, tr->dx, 1, tr->part, tr->dw_part, dmod + 0 * D,
-                           dmod + 1 * D, mstride, tr->rms ? G + L.o_n1 : nullptr, acc, B, D, ntok, mode, s));
+                           dmod + 1 * D, mstride, tr->rms ? G + L.off[P_N1] : nullptr, acc, B, D, ntok, mode, s));
       // adaLN modulation Linear(SiLU(t_emb)) of this block (:275-278): its six dmod slices are complete now (a weight gradient
       // like the others: nothing in the chain reads it)
       JCHK(dw_begin(tr->ev_mod[par]));
-      KCHK(launch_small_dw(dmod, mstride, tr->t_emb, D, G + L.o_ada_w, G + L.o_ada_b, B, 6 * D, D, 1, acc, ws));
+      KCHK(launch_small_dw(dmod, mstride, tr->t_emb, D, G + L.off[P_ADA_W], G + L.off[P_ADA_B], B, 6 * D, D, 1, acc, ws));
       if (tr->dw_async) HIPCHK(hipEventRecord(tr->ev_layer[l], ws));
       if (tr->dw_async) {
         if (pending_hook >= 0) JCHK(fire_hook(pending_hook));
@@ -372,15 +360,15 @@ int backward_train(jat_trainer* tr, const float* target, const float* cond_clean
   // patch embed: Linear(Kp -> bott) - GELU - Linear(bott -> D)   (jat_audiosr_v3.py:221-225); no gradient to the input
   KCHK(launch_cast_bf16(tr->dx, tr->dy, (int64_t)M * D, s));
   JCHK(input_grad(tr, tr->dy, D, tr->pe_w2T, m->bott, tr->dh, s));
-  JCHK(weight_grad(tr, tr->dy, D, tr->pe_h, m->bott, G + tr->o_pe_w2, G + tr->o_pe_b2, acc, s));
+  JCHK(weight_grad(tr, tr->dy, D, tr->pe_h, m->bott, G + tr->off[P_PE_W2], G + tr->off[P_PE_B2], acc, s));
   KCHK(launch_gelu_bwd(tr->pe_pre, tr->dh, (int64_t)M * m->bott, kNoDrop, s));
-  JCHK(weight_grad(tr, tr->dh, m->bott, tr->a_patch, m->Kp, G + tr->o_pe_w1, G + tr->o_pe_b1, acc, s));
+  JCHK(weight_grad(tr, tr->dh, m->bott, tr->a_patch, m->Kp, G + tr->off[P_PE_W1], G + tr->off[P_PE_B1], acc, s));
   // the t_embedder MLP (:364-369) behind all adaLN Linears; fp32, B rows
   // d silu(t_emb) = dmod [B, depth*6D] @ W_ada (the packed bf16 copy the forward multiplied with), all layers at once
   KCHK(launch_small_dx(tr->dmod, mstride, m->wada, 1, tr->small_part, tr->dt_emb, B, (int)mstride, D, 0, tr->t_emb, s));
-  KCHK(launch_small_dw(tr->dt_emb, D, tr->t_h, D, G + tr->o_te_w2, G + tr->o_te_b2, B, D, D, 0, acc, s));
-  KCHK(launch_small_dx(tr->dt_emb, D, tr->P + tr->o_te_w2, 0, tr->small_part, tr->du1, B, D, D, 0, tr->u1, s));
-  KCHK(launch_small_dw(tr->du1, D, tr->e_sin, D, G + tr->o_te_w1, G + tr->o_te_b1, B, D, D, 0, acc, s));
+  KCHK(launch_small_dw(tr->dt_emb, D, tr->t_h, D, G + tr->off[P_TE_W2], G + tr->off[P_TE_B2], B, D, D, 0, acc, s));
+  KCHK(launch_small_dx(tr->dt_emb, D, tr->P + tr->off[P_TE_W2], 0, tr->small_part, tr->du1, B, D, D, 0, tr->u1, s));
+  KCHK(launch_small_dw(tr->du1, D, tr->e_sin, D, G + tr->off[P_TE_W1], G + tr->off[P_TE_B1], B, D, D, 0, acc, s));
   if (tr->hook && !tr->no_hook) tr->hook(0, tr->block_lo[0], tr->hook_user);
   return JAT_OK;
 }
@@ -452,65 +440,41 @@ extern "C" int jat_trainer_create(jat_model* m, const jat_tensor_ref* params, in
     }
 
   // ---- parameter table: every tensor must lie inside the flat buffer, 16-B aligned, with the expected size ----
-  std::unordered_map<std::string, int64_t> off;
-  tr->names.reserve(n);
+  std::unordered_map<std::string, const jat_tensor_ref*> given;
   for (int i = 0; i < n; ++i) {
     const int64_t o = params[i].data - params_flat;
     if (o < 0 || o + params[i].numel > total || o % 4 != 0) {
       delete tr;
       return fail(JAT_E_INVALID, "parameter '%s' is not a 16-byte aligned slice of the flat buffer", params[i].name);
     }
-    tr->names.emplace_back(params[i].name);
-    off[tr->names.back()] = o;
+    given[params[i].name] = &params[i];
   }
-  tr->prefs.resize(n);
-  for (int i = 0; i < n; ++i) tr->prefs[i] = jat_tensor_ref{tr->names[i].c_str(), params[i].data, params[i].numel};
+  // every parameter of the model resolved to its offset; per group (head, block l, final layer = block `depth`) the range it
+  // covers: block l = [block_lo[l], block_lo[l+1]) is what the gradient-ready hook reports
   int rc = JAT_OK;
   size_t used = 0;
-  auto need = [&](const std::string& name) -> int64_t {
-    auto it = off.find(name);
-    if (it == off.end()) { rc = fail(JAT_E_STATE, "missing parameter '%s'", name.c_str()); return 0; }
-    ++used;
-    return it->second;
-  };
-  tr->o_pe_w1 = need("patch_embed.proj.0.weight"); tr->o_pe_b1 = need("patch_embed.proj.0.bias");
-  tr->o_pe_w2 = need("patch_embed.proj.2.weight"); tr->o_pe_b2 = need("patch_embed.proj.2.bias");
-  tr->o_te_w1 = need("t_embedder.1.weight"); tr->o_te_b1 = need("t_embedder.1.bias");
-  tr->o_te_w2 = need("t_embedder.3.weight"); tr->o_te_b2 = need("t_embedder.3.bias");
-  tr->o_fn = tr->rms ? need("final_layer.0.weight") : 0;
-  tr->o_wf = need("final_layer.1.weight"); tr->o_bf = need("final_layer.1.bias");
+  int64_t head_hi = -1;
   tr->L.resize(depth);
-  for (int l = 0; l < depth; ++l) {
-    const std::string p = "blocks." + std::to_string(l) + ".";
-    TLayer& L = tr->L[l];
-    L.o_n1 = tr->rms ? need(p + "norm1.weight") : 0; L.o_n2 = tr->rms ? need(p + "norm2.weight") : 0;
-    L.o_q = need(p + "attn.q_proj.weight"); L.o_k = need(p + "attn.k_proj.weight"); L.o_v = need(p + "attn.v_proj.weight");
-    L.o_o = need(p + "attn.out_proj.weight");
-    L.o_w1 = need(p + "mlp.0.weight"); L.o_b1 = need(p + "mlp.0.bias");
-    L.o_w2 = need(p + "mlp.3.weight"); L.o_b2 = need(p + "mlp.3.bias");
-    L.o_ada_w = need(p + "adaLN_modulation.1.weight"); L.o_ada_b = need(p + "adaLN_modulation.1.bias");
+  tr->block_lo.assign(depth + 1, total);
+  for (const ParamDesc& e : m->params) {
+    if (!m->has(e)) continue;
+    auto it = given.find(e.name);
+    if (it == given.end()) { rc = fail(JAT_E_STATE, "missing parameter '%s'", e.name.c_str()); break; }
+    if (it->second->numel != e.numel()) {
+      rc = fail(JAT_E_INVALID, "parameter '%s' has %lld elements, expected %lld", e.name.c_str(), (long long)it->second->numel,
+                (long long)e.numel());
+      break;
+    }
+    ++used;
+    const int64_t o = tr->offset_of(e) = it->second->data - params_flat;
+    if (e.block < 0) head_hi = std::max(head_hi, o);
+    else tr->block_lo[e.block] = std::min(tr->block_lo[e.block], o);
   }
-  // contiguous parameter ranges per block for the gradient-ready hook: block l = [block_lo[l], block_lo[l+1])
-  tr->block_lo.assign(depth + 1, 0);
-  for (int l = 0; l < depth && rc == JAT_OK; ++l) {
-    const TLayer& L = tr->L[l];
-    int64_t lo = std::min(std::min(L.o_q, L.o_k), std::min(L.o_v, L.o_o));
-    lo = std::min(lo, std::min(std::min(L.o_w1, L.o_b1), std::min(L.o_w2, L.o_b2)));
-    lo = std::min(lo, std::min(L.o_ada_w, L.o_ada_b));
-    if (tr->rms) lo = std::min(lo, std::min(L.o_n1, L.o_n2));
-    tr->block_lo[l] = lo;
-  }
-  tr->block_lo[depth] = std::min(tr->o_wf, tr->o_bf);
-  if (tr->rms) tr->block_lo[depth] = std::min(tr->block_lo[depth], tr->o_fn);
   for (int l = 0; l < depth && rc == JAT_OK; ++l)
     if (tr->block_lo[l] >= tr->block_lo[l + 1])
       rc = fail(JAT_E_INVALID, "parameters of block %d are not laid out before those of block %d / the final layer", l, l + 1);
-  {
-    const int64_t head_hi = std::max(std::max(tr->o_pe_w1, tr->o_pe_b1), std::max(std::max(tr->o_pe_w2, tr->o_pe_b2),
-                            std::max(std::max(tr->o_te_w1, tr->o_te_b1), std::max(tr->o_te_w2, tr->o_te_b2))));
-    if (rc == JAT_OK && head_hi >= tr->block_lo[0])
-      rc = fail(JAT_E_INVALID, "patch_embed / t_embedder parameters must precede the blocks in the flat buffer");
-  }
+  if (rc == JAT_OK && head_hi >= tr->block_lo[0])
+    rc = fail(JAT_E_INVALID, "patch_embed / t_embedder parameters must precede the blocks in the flat buffer");
   if (rc == JAT_OK && used != (size_t)n)
     rc = fail(JAT_E_INVALID, "%d parameters given, %zu belong to this model: every trainable tensor must be known", n, used);
   if (rc != JAT_OK) { delete tr; return rc; }
@@ -533,6 +497,7 @@ extern "C" int jat_trainer_create(jat_model* m, const jat_tensor_ref* params, in
     if (!ok) { jat_trainer_destroy(tr); return fail(JAT_E_HIP, "stream / event creation for the weight-gradient stream failed"); }
   }
   // ---- one allocation: transposed weights, saved activations, backward scratch ----
+  const size_t n_f32 = std::count_if(m->params.begin(), m->params.end(), [](const ParamDesc& e) { return e.form == F_F32; });
   for (int pass = 0; pass < 2; ++pass) {
     size_t o = 0;
     char* base = tr->blob;
@@ -588,7 +553,7 @@ extern "C" int jat_trainer_create(jat_model* m, const jat_tensor_ref* params, in
     }
     tr->dw_split = (float*)take(split_f * 4);
     tr->zero_cell = take(256);
-    tr->copy_jobs = (CopyJob*)take((size_t)(8 + 5 * depth + 2) * sizeof(CopyJob));
+    tr->copy_jobs = (CopyJob*)take(n_f32 * sizeof(CopyJob));
     tr->dy = (bf16_t*)take(MD2); tr->dh = (bf16_t*)take((size_t)M * std::max(mlp, bott) * 2);
     tr->dxn = (bf16_t*)take(MD2); tr->dao = (bf16_t*)take(MD2); tr->dqkv = (bf16_t*)take((size_t)M * Nqkv * 2);
     tr->dy_m[0] = tr->dy_a[0] = tr->dy; tr->dy_m[1] = tr->dy_a[1] = tr->dy;   // one stream: every operand has one home
@@ -611,19 +576,9 @@ extern "C" int jat_trainer_create(jat_model* m, const jat_tensor_ref* params, in
     }
   }
   {
-    std::vector<CopyJob> jobs;
-    auto job = [&](int64_t o, float* dst, int64_t cnt) { jobs.push_back(CopyJob{params_flat + o, dst, cnt}); };
-    job(tr->o_pe_b1, m->pe_b1, bott); job(tr->o_pe_b2, m->pe_b2, D);
-    job(tr->o_te_w1, m->te_w1, (int64_t)D * D); job(tr->o_te_b1, m->te_b1, D);
-    job(tr->o_te_w2, m->te_w2, (int64_t)D * D); job(tr->o_te_b2, m->te_b2, D);
-    job(tr->o_bf, m->bfinal, m->Fout);
-    if (tr->rms) job(tr->o_fn, m->final_norm, D);
-    for (int l = 0; l < depth; ++l) {
-      const TLayer& L = tr->L[l];
-      if (tr->rms) { job(L.o_n1, m->layers[l].norm1, D); job(L.o_n2, m->layers[l].norm2, D); }
-      job(L.o_b1, m->layers[l].b1, mlp); job(L.o_b2, m->layers[l].b2, D);
-      job(L.o_ada_b, m->bada + (int64_t)l * 6 * D, (int64_t)6 * D);
-    }
+    std::vector<CopyJob> jobs;   // the re-pack's fp32 copies: master slice -> the model's operand tensor
+    for (const ParamDesc& e : m->params)
+      if (e.form == F_F32 && m->has(e)) jobs.push_back(CopyJob{params_flat + tr->offset_of(e), m->at<float>(e), e.numel()});
     tr->n_copy_jobs = (int)jobs.size();
     if (hipMemcpyAsync(tr->copy_jobs, jobs.data(), jobs.size() * sizeof(CopyJob), hipMemcpyHostToDevice, s) != hipSuccess ||
         hipStreamSynchronize(s) != hipSuccess) {

@@ -62,6 +62,44 @@ def test_forward_vs_reference_golden(name):
     assert abs(np.linalg.norm(o.astype(np.float64)) / float(z["out_l2"]) - 1) < 1e-2
 
 
+def test_loader_rejects_a_missing_or_missized_tensor_and_the_handle_recovers():
+    """jat_model_load_weights on a handle of its own: a missing name and a wrong element count are refused with their code and
+    text, before and after a correct load, and the forward through that handle equals the forward of a model that was only ever
+    loaded correctly, bit for bit."""
+    from jatsr_amd.model import _Handle
+    z, meta = load_golden("fwd_micro_T24")
+    cfg, x_t, t, x_c = fwd_inputs(meta)
+    good = build(meta["cfg"], meta["norm"], meta["salt"])
+    want = good(cuda(x_t), cuda(t), cuda(x_c))
+    m = type(good)(**cfg)
+    m.load_state_dict({k: v.detach().cpu().clone() for k, v in good.state_dict().items()}, strict=False)
+    m = m.to("cuda").eval()
+    named = m._named_for_pack()
+    h = _Handle(*m._handle_cfg())
+
+    def load(tensors, numel={}):
+        refs = (L.JatTensorRef * len(tensors))()
+        for i, (k, v) in enumerate(tensors.items()):
+            refs[i] = L.JatTensorRef(k.encode(), v.data_ptr(), numel.get(k, v.numel()))
+        rc = L.lib().jat_model_load_weights(h.ptr, refs, len(tensors), L.stream_ptr())
+        return rc, L.lib().jat_last_error().decode()
+
+    def rejections():
+        for name in ("final_layer.1.bias", "blocks.1.mlp.0.bias"):
+            rc, msg = load({k: v for k, v in named.items() if k != name})
+            assert rc == L.JAT_E_STATE and f"missing parameter '{name}'" in msg
+        name = "blocks.0.mlp.3.weight"
+        n = named[name].numel()
+        rc, msg = load(named, {name: n // 2})
+        assert rc == L.JAT_E_INVALID and f"parameter '{name}' has {n // 2} elements, expected {n}" in msg
+
+    rejections()                               # nothing loaded yet
+    m.__dict__["_jat_handle"] = h              # the model's forward loads `named` into h and runs on it
+    assert torch.equal(m(cuda(x_t), cuda(t), cuda(x_c)), want)
+    rejections()                               # a refused load leaves the loaded weights as they are
+    assert torch.equal(m(cuda(x_t), cuda(t), cuda(x_c)), want)
+
+
 def test_forward_at_the_benchmarked_batch_vs_reference_golden():
     """BASELINE configs[1] at its full size: the eval forward at B = 28, T = 512 (M = 3584 rows: other tile variants than any
     small test — un-fused QKV GEMM + attn_group_kernel, per-sample adaLN modulation, 57 norm kernels).  Rows 0-1 are the two

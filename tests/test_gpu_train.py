@@ -764,6 +764,27 @@ def test_sampler_follows_trained_weights():
     assert torch.equal(b, c)
 
 
+def test_repack_equals_a_fresh_load_for_a_layernorm_model():
+    """The re-pack after an optimiser step against a full load of the same weights, where the model has no norm weights: their
+    operand copies are the constant ones the first load wrote, and the re-pack's fp32 copies are the biases alone.  The forward
+    after the step equals, bit for bit, the forward of a fresh model loaded from the stepped model's state_dict."""
+    z, meta = load_golden("train_micro_ln_T24")
+    assert meta["norm"] == "ln" and (meta["B"], meta["T"]) == (2, 24)
+    m, tr = make_trainer(meta, use_grad_scaler=False, condition_noise_ratio=0.0)
+    m.eval()
+    hr, lr, noise, t, mask = step_inputs(meta)
+    C = hr.shape[1]
+    a = m(noise, t, lr)
+    tr.base_lr = 1e-2
+    mean, std = torch.zeros(C, device="cuda"), torch.ones(C, device="cuda")
+    tr.train_step(hr, lr, mean, std, mean, std)
+    b = m(noise, t, lr)
+    assert torch.isfinite(b).all() and not torch.equal(a, b)
+    m2 = type(m)(**recipe.CONFIGS[meta["cfg"]], dropout=0.0, drop_path_rate=0.0)
+    m2.load_state_dict({k: v.detach().cpu().clone() for k, v in m.state_dict().items()}, strict=False)
+    assert torch.equal(b, m2.to("cuda").eval()(noise, t, lr))
+
+
 def test_held_sampler_and_checkpoint_resume_follow_the_weights(tmp_path):
     """(i) a `Sampler` object the caller HOLDS across an optimiser step must not mix its old modulation table /
     folded weights with the new packed weights — `run` rebuilds it; (ii) `load_checkpoint` followed immediately by sampling
