@@ -5,6 +5,8 @@ as a fully resident one; `jat_train_monitor` is within the fp64 summation bound 
 import ctypes as C
 import math
 import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -18,6 +20,7 @@ from jatsr_amd.data import LatentStore  # noqa: E402
 from jatsr_amd.sampler import channel_affine  # noqa: E402
 from jatsr_amd.train import monitor_figures, train_monitor  # noqa: E402
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PAD = 64            # floats of canary either side of an output tensor (keeps it 256-byte aligned)
 CANARY = -1234.5
 
@@ -192,6 +195,44 @@ def test_store_host_resident_files_give_the_same_bits(data_dir):
         full.batch([0], [45], stats)
     with pytest.raises(ValueError, match="No .pt files"):
         LatentStore(data_dir, "val", T, "cuda")
+
+
+def both_builds_outputs():
+    """what the child on libjat_hip_fp16.so and this process both compute: one gathered batch of the ragged layout (every
+    alignment case of `batch_layout`, the special values of `make_src`) and one monitor call"""
+    T, B, C_ = 37, 7, 32
+    lengths, starts = batch_layout(B, T)
+    hr_src = [make_src(C_, n, 100 + i).cuda() for i, n in enumerate(lengths)]
+    lr_src = [make_src(C_, n, 500 + i).cuda() for i, n in enumerate(lengths)]
+    hr, lr = gather(hr_src, lr_src, starts, T, make_stats(C_))
+    g = torch.Generator().manual_seed(11)
+    target = torch.randn((3, 5, 1031), generator=g) * 1.1 + 0.05
+    pred = target + torch.randn((3, 5, 1031), generator=g) * 0.3 - 0.02
+    cond = torch.randn((3, 5, 1031), generator=g) * 1.3 + 0.1
+    sums = train_monitor(pred.cuda(), target.cuda(), cond.cuda())
+    return {k: v.cpu().numpy() for k, v in dict(hr=hr, lr=lr, sums=sums).items()}
+
+
+def test_fp16_library_gives_the_same_bits(tmp_path):
+    """data.hip is fp32 in both builds (csrc/Makefile): libjat_hip_fp16.so, in a child process, computes the bits this process
+    computes"""
+    code = ("import sys, numpy as np\n"
+            "sys.path.insert(0, 'tests')\n"
+            "import jatsr_amd._lib as L\n"
+            "from test_gpu_data import both_builds_outputs\n"
+            "assert L.operand_dtype() == 'fp16'\n"
+            "np.savez(sys.argv[1], **both_builds_outputs())\n")
+    env = dict(os.environ, JAT_OPERAND_DTYPE="fp16")
+    env.pop("JAT_LIB_PATH", None)
+    path = str(tmp_path / "fp16.npz")
+    out = subprocess.run([sys.executable, "-c", code, path], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, (out.stdout + out.stderr)[-2000:]
+    got, mine = dict(np.load(path)), both_builds_outputs()
+    assert sorted(got) == sorted(mine) == ["hr", "lr", "sums"]
+    for k, v in mine.items():
+        assert v.dtype == got[k].dtype and np.isfinite(v).all() and np.abs(v).max() > 0, k
+        assert np.array_equal(v, got[k]) and v.tobytes() == got[k].tobytes(), k
+    assert mine["hr"].shape == (7, 32, 37) and mine["sums"].shape == (6,) and mine["sums"].dtype == np.float64
 
 
 def np_sums(p, h, l):

@@ -8,6 +8,11 @@ than max(|p_new|, |e|): 3 * 2^-24 * max(|p_new|, |e0|) against the fp64 formula 
 that AdamW's own rounding does not enter.  Over N updates the errors add (each later update scales an earlier error by
 d <= 1): 3 * 2^-24 * S * N with S the largest |p| or |e| seen.  The decay handed to the C ABI is a float, so the fp64
 recurrence uses the float value of `ema_decay_at`.
+
+The fp16-operand library (tests/test_gpu_fp16.py runs a selection of this file on it): `make_trainer` of tests/test_gpu_train.py
+gives a trainer without the dynamic scaler the fixed loss scale FP16_TEST_SCALE, and the fixture with the scaler on starts from
+it too.  Nothing here compares a gradient with a reference, so the scale is nowhere divided out: the trainers whose bits
+are compared run at the same one, and the fp64 recurrence is applied to the parameters the GPU produced.
 """
 import ctypes
 import math
@@ -26,7 +31,7 @@ import jatsr_amd.recipe as recipe  # noqa: E402
 from helpers import load_golden  # noqa: E402
 from jatsr_amd import fit as F  # noqa: E402
 from test_gpu_fit import BATCH, TRAIN_LENGTHS, VAL_LENGTHS, fit_args, read_log, write_folder  # noqa: E402
-from test_gpu_train import make_trainer, step_inputs  # noqa: E402
+from test_gpu_train import FP16, FP16_TEST_SCALE, cuda, make_trainer, step_inputs  # noqa: E402
 from test_gpu_train_kernels import F32, call, dev, gen, guarded, guards_intact, work  # noqa: E402
 
 HYPER = (1e-3, 0.9, 0.999, 1e-8, 0.01)     # lr, beta1, beta2, eps, weight decay: those of test_adamw
@@ -196,6 +201,8 @@ def run_steps(tr, meta, steps, first=0, record=None):
 def six_steps():
     meta, m, tr = micro(use_grad_scaler=True, ema_decay=0.99, seed=5)
     _, m0, tr0 = micro(use_grad_scaler=True, seed=5)
+    if FP16:          # the fp16-operand library: the dynamic scaler stays on, from a start that fp16 gradients do not overflow at
+        tr.scaler.scale = tr0.scaler.scale = FP16_TEST_SCALE
     assert tr0.ema is None and same_bits(tr.params, tr0.params) and same_bits(tr.ema, tr.params)
     e = tr.ema.double().cpu().numpy()
     state = dict(e=e, S=float(np.abs(e).max()), N=0, skipped=[])
@@ -226,6 +233,55 @@ def test_trainer_ema_follows_the_fp64_recurrence_and_does_not_perturb_training(s
     assert err.max() <= bound
     assert float((tr.ema - tr.params).abs().max()) > 1e-3          # the average is not the last iterate
     assert same_bits(tr.params, tr0.params) and same_bits(tr.exp_avg, tr0.exp_avg) and same_bits(tr.exp_avg_sq, tr0.exp_avg_sq)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 5b. the average across steps the arithmetic itself skips
+# ---------------------------------------------------------------------------------------------------------------------
+def test_average_across_real_overflow_skips():
+    """The loss scaler's skips made by the arithmetic, not by a planted inf: fp16 operands above 65504 at a 2^30 loss scale (the
+    fp16 library; the bf16 one overflows nowhere at 2^16 and must take every step).  Until four steps are taken: a skipped step
+    leaves the average bit for bit alone and does not count as an update; the average is the fp64 recurrence over the
+    parameter snapshots of the taken steps alone, within 3 * 2^-24 * S per update (the bound of section 5)."""
+    fp16 = L.operand_dtype() == "fp16"
+    meta = dict(cfg="micro", norm="rms", salt=95, B=2, T=24, lr=1e-4, wd=0.1, clip=1.0)
+    m, tr = make_trainer(meta, use_grad_scaler=True, condition_noise_ratio=0.0, ema_decay=0.99)
+    tr.scaler.scale = 2.0 ** 30 if fp16 else 65536.0
+    Cc = recipe.CONFIGS["micro"]["input_channels"]
+    z_t, cond, target = (cuda(recipe.gaussian(n, (2, Cc, 24), 95 + i)) for i, n in enumerate(("zt", "cond", "target")))
+    t = cuda(np.asarray([0.2, 0.8], np.float32))
+    # the overflow skips all come before the first taken step, while a fresh average still equals the weights and an update on a
+    # skipped step would change nothing: start from an average that is not the weights
+    tr.ema.mul_(0.75)
+    assert not same_bits(tr.ema, tr.params)
+    e = tr.ema.double().cpu().numpy()
+    S, N, skipped = float(np.abs(e).max()), 0, 0
+    for step in range(40):
+        if tr.opt_step == 4:
+            break
+        e0, s0 = tr.ema.clone(), tr.scaler.scale
+        tr.forward_backward(z_t, t, cond, target)
+        _, gn = tr.optimizer_step(lr=LR)
+        if math.isfinite(gn):
+            N += 1
+            p = tr.params.double().cpu().numpy()
+            e = R.ema_update(e, p, f32(R.ema_decay_at(N, 0.99, True)))
+            S = max(S, float(np.abs(p).max()), float(np.abs(e).max()))
+            assert tr.scaler.scale == s0 and not same_bits(tr.ema, e0)
+        else:
+            skipped += 1
+            assert same_bits(tr.ema, e0) and tr.scaler.scale == s0 * 0.5
+        assert tr.ema_updates == tr.opt_step == N and tr.global_step == N + skipped
+    assert tr.ema_updates == tr.opt_step == N == 4
+    err = np.abs(tr.ema.double().cpu().numpy() - e)
+    bound = 3 * F32 * S * N
+    print(f"{'fp16' if fp16 else 'bf16'}: {skipped} skipped, 4 taken; worst ema error {err.max():.3e}, bound {bound:.3e} (S {S:.3f})")
+    assert err.max() <= bound
+    assert float((tr.ema - tr.params).abs().max()) > 1e-3          # the average is not the last iterate
+    if fp16:
+        assert skipped >= 1, "a 2^30 loss scale must overflow fp16 operands at least once"
+    else:
+        assert skipped == 0
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -252,6 +252,67 @@ def test_a_non_finite_micro_batch_skips_the_whole_step():
     assert not torch.equal(tr.params, before[0]) and tr.scaler.scale == s0 * 0.5
 
 
+def test_real_overflow_inside_an_accumulated_step_skips_it_once(monkeypatch):
+    """torch's GradScaler under accumulation, with the overflow made by the arithmetic and not planted: fp16 operands above 65504
+    at a 2^30 loss scale (the fp16 library; the bf16 one overflows nowhere at 2^16 and must take every step).  One scale for the
+    k micro-batches of a step; a step with an overflowed micro-batch changes no optimiser state, halves the scale once and counts
+    as a batch but not as an update; the step after it starts by overwriting."""
+    salt, B, T, k = 91, 2, 24, 3
+    fp16 = L.operand_dtype() == "fp16"
+    m, tr = build("micro", "rms", salt, B, T, use_grad_scaler=True, grad_accum_steps=k)
+    tr.scaler.scale = 2.0 ** 30 if fp16 else 65536.0
+    xs = [tuple(cuda(a) for a in micro_inputs("micro", B, T, salt, j)) for j in range(k)]
+    passed = []                                   # the loss scale of every launch, as the C ABI receives it
+    real = L.lib().jat_trainer_fwd_bwd_ex
+
+    def spy(*args):
+        passed.append(args[6])
+        return real(*args)
+    monkeypatch.setattr(L.lib(), "jat_trainer_fwd_bwd_ex", spy)
+
+    def finite(x):
+        return bool(torch.isfinite(x).all())
+    taken, skipped, after_skip, clean_restarts = [], 0, False, 0
+    for step in range(40):
+        if tr.opt_step == 4:
+            break
+        before = (tr.params.clone(), tr.exp_avg.clone(), tr.exp_avg_sq.clone())
+        s0, counts = tr.scaler.scale, (tr.global_step, tr.opt_step)
+        del passed[:]
+        overflowed = False
+        for j, x in enumerate(xs):
+            tr.forward_backward(*x)
+            if j == 0 and after_skip:
+                # what this call leaves is what it leaves in a zeroed buffer: nothing of the skipped step's inf survives
+                got = tr.grads.clone()
+                tr.grads.zero_()
+                fwd_bwd_c(tr, x, tr.step_seed(micro=0), L.FB_NO_HOOK)       # overwrite mode again (no dropout: the seed is not read)
+                assert torch.equal(got.view(torch.int32), tr.grads.view(torch.int32))
+                clean_restarts += finite(got)
+            overflowed = overflowed or not finite(tr.grads)
+        assert len(passed) == k + int(after_skip) and set(passed) == {s0}, (passed, s0)
+        loss, gnorm = tr.optimizer_step(lr=1e-3)
+        assert overflowed == (not math.isfinite(gnorm)), (step, overflowed, gnorm)
+        if overflowed:
+            skipped += 1
+            assert all(torch.equal(a, b) for a, b in zip((tr.params, tr.exp_avg, tr.exp_avg_sq), before)), step
+            assert tr.scaler.scale == s0 * 0.5                              # once, not once per micro-batch
+            assert (tr.global_step, tr.opt_step) == (counts[0] + 1, counts[1])
+        else:
+            taken.append((loss, gnorm))
+            assert tr.scaler.scale == s0 and (tr.global_step, tr.opt_step) == (counts[0] + 1, counts[1] + 1)
+            assert not torch.equal(tr.params, before[0])
+        after_skip = overflowed
+    print(f"{'fp16' if fp16 else 'bf16'}: {skipped} skipped, {len(taken)} taken, final scale {tr.scaler.scale}, taken {taken}")
+    assert tr.opt_step == 4 == len(taken) and tr.global_step == 4 + skipped
+    assert all(math.isfinite(a) and math.isfinite(b) and b > 0 for a, b in taken)
+    if fp16:
+        assert skipped >= 1 and clean_restarts >= 1, "a 2^30 loss scale must overflow fp16 operands at least once"
+        assert tr.scaler.scale == 2.0 ** (30 - skipped)
+    else:
+        assert skipped == 0 and tr.scaler.scale == 65536.0
+
+
 # ---- 6. the gradient-ready hook -----------------------------------------------------------------------------------------
 def test_hook_fires_only_in_the_last_micro_batch_single_rank_rccl():
     import socket

@@ -232,6 +232,54 @@ def test_rejections_launch_nothing():
     run_and_check(35, "T=35 after the rejections")
 
 
+BOTH_BUILDS_T = (35, 257)            # a factored and a direct-DFT length of the table
+
+
+def both_builds_outputs():
+    """what the child on libjat_hip_fp16.so and this process both compute: `jat_k_latent_loss_ex` at a factored and a direct
+    length, as the v3mod2 loss (recon_eps = 0: the base instances) and as the v3mod3 loss (recon_eps = 1e-6: the general ones)"""
+    out = {}
+    w, c = K.WEIGHTS, K.CUTS
+    for T in BOTH_BUILDS_T:
+        assert plan(T)[0] == {"direct": 1, "fft": 2}[K.PATH[T][0]] or DIRECT
+        pred, target, lr = (torch.tensor(a[0], device="cuda") for a in case_inputs(T))
+        rows = pred.shape[0]
+        work = torch.zeros(work_bytes(T, rows), dtype=torch.uint8, device="cuda")
+        for eps in (0.0, 1e-6):
+            dpred, out6 = torch.full((rows, T), NAN, device="cuda"), torch.full((6,), NAN, device="cuda")
+            L.check(L.lib().jat_k_latent_loss_ex(L.ptr(pred), L.ptr(target), L.ptr(lr), L.ptr(dpred), L.ptr(out6), rows, T, eps, 1.0,
+                                                 w["latent_weight"], w["freq_weight"], w["ms_weight"], w["consistency_weight"],
+                                                 c["low_freq_phase_ratio"], c["strict_cutoff"], c["soft_cutoff"], 1.0, L.ptr(work),
+                                                 work.numel(), L.stream_ptr()))
+            torch.cuda.synchronize()
+            out[f"dpred_T{T}_eps{eps}"], out[f"out6_T{T}_eps{eps}"] = dpred.cpu().numpy(), out6.cpu().numpy()
+    return out
+
+
+def test_fp16_library_gives_the_same_bits(tmp_path):
+    """latent_loss_kernel / latent_loss_fft_kernel are fp32 kernels inside train.hip, which the fp16 build compiles with
+    -DJAT_FP16: libjat_hip_fp16.so, in a child process, computes the bits this process computes (also the entry of
+    tests/test_gpu_mod3_loss.py in tests/fp16_matrix.py)"""
+    code = ("import sys, numpy as np\n"
+            "sys.path.insert(0, 'tests')\n"
+            "import jatsr_amd._lib as L\n"
+            "from test_gpu_loss_paths import both_builds_outputs\n"
+            "assert L.operand_dtype() == 'fp16'\n"
+            "np.savez(sys.argv[1], **both_builds_outputs())\n")
+    env = dict(os.environ, JAT_OPERAND_DTYPE="fp16")
+    env.pop("JAT_LIB_PATH", None)
+    path = str(tmp_path / "fp16.npz")
+    out = subprocess.run([sys.executable, "-c", code, path], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, (out.stdout + out.stderr)[-2000:]
+    got, mine = dict(np.load(path)), both_builds_outputs()
+    assert sorted(got) == sorted(mine) and len(mine) == 8
+    for k, v in mine.items():
+        assert v.dtype == np.float32 and np.isfinite(v).all() and np.abs(v).max() > 0, k
+        assert np.array_equal(v, got[k]) and v.tobytes() == got[k].tobytes(), k
+    for T in BOTH_BUILDS_T:                 # the two losses differ: the Charbonnier instances did run
+        assert not np.array_equal(mine[f"dpred_T{T}_eps0.0"], mine[f"dpred_T{T}_eps1e-06"])
+
+
 AB_LENGTHS = (1378, 128)
 
 

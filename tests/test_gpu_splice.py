@@ -12,6 +12,8 @@ closest any case comes to its gate).  The other shapes: DESIGN 14."""
 import functools
 import json
 import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -27,6 +29,7 @@ import jatsr_amd.recipe as recipe  # noqa: E402
 import jatsr_amd.splice as splice  # noqa: E402
 from jatsr_amd import _lib as L  # noqa: E402
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = [pytest.param(n_fft, hop, n, B, id=f"{n_fft}-{hop}-{n}-B{B}") for n_fft, hop, n in S.GPU_SHAPES for B in (1, 3)]
 
 
@@ -190,6 +193,39 @@ def test_refusals():
     assert lib.jat_band_splice(h.ptr, L.ptr(x), L.ptr(x), 2, 5000, 5000, None, L.ptr(y), L.ptr(work), work.numel(),
                                L.stream_ptr()) == L.JAT_E_INVALID
     torch.cuda.synchronize()
+
+
+# ---- the fp16-operand library ------------------------------------------------------------------------------------------------
+def both_builds_outputs():
+    """what the child on libjat_hip_fp16.so and this process both compute: shape (512, 128, 1301), B = 3"""
+    n_fft, hop, n = 512, 128, 1301
+    f = fixture(n_fft, hop, n)
+    out = dict(istft=splice.istft(cuda(f["X"]), n, n_fft, hop),
+               splice=splice.splice_gain(cuda(f["g"]), cuda(f["s"]), torch.from_numpy(f["a"].copy()), n_fft, hop),
+               ltas=splice.ltas(cuda(f["x"]), n_fft, hop))
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
+def test_fp16_library_gives_the_same_bits(tmp_path):
+    """splice.hip is fp32 in both builds (csrc/Makefile): libjat_hip_fp16.so, in a child process, computes the bits this process
+    computes"""
+    code = ("import sys, numpy as np\n"
+            "sys.path.insert(0, 'tests')\n"
+            "import jatsr_amd._lib as L\n"
+            "from test_gpu_splice import both_builds_outputs\n"
+            "assert L.operand_dtype() == 'fp16'\n"
+            "np.savez(sys.argv[1], **both_builds_outputs())\n")
+    env = dict(os.environ, JAT_OPERAND_DTYPE="fp16")
+    env.pop("JAT_LIB_PATH", None)
+    path = str(tmp_path / "fp16.npz")
+    out = subprocess.run([sys.executable, "-c", code, path], cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, (out.stdout + out.stderr)[-2000:]
+    got, mine = dict(np.load(path)), both_builds_outputs()
+    assert sorted(got) == sorted(mine) == ["istft", "ltas", "splice"]
+    for k, v in mine.items():
+        assert v.dtype == got[k].dtype and np.isfinite(v).all() and np.abs(v).max() > 0, k
+        assert np.array_equal(v, got[k]) and v.tobytes() == got[k].tobytes(), k
+    assert mine["istft"].shape == (3, 1301) and mine["splice"].shape == (3, 1338) and mine["ltas"].shape == (3, 257)
 
 
 # ---- command lines -----------------------------------------------------------------------------------------------------------
