@@ -722,6 +722,41 @@ int jat_bank_search(jat_bank* bank, const float* x, const float* mean, const flo
 int jat_bank_blend(jat_bank* bank, const float* x, const int32_t* idx, const float* value_mean, const float* value_std,
                    float rate, float* y, int32_t B, int32_t T, void* stream);
 
+/* ---- pitch tracking (YIN) and F0-preservation counts ------------------------------------------------ */
+/* Steps 1-5 of de Cheveigne & Kawahara (2002) on mono fp32 audio x[B, L], framed as the STFT above frames it:
+ * W = frame_length / 2, frames = 1 + L / hop_length, frame f = x_pad[f hop : f hop + frame_length] with frame_length / 2
+ * zeros a side; min_period = floor(sr / fmax), max_period = min(ceil(sr / fmin), frame_length - W - 1).  Per frame:
+ *   d(tau) = sum_{j < W} (x[j] - x[j + tau])^2, tau = 1 .. max_period, summed in this direct form
+ *   c(tau) = d(tau) / ((1 / tau) sum_{u = 1 .. tau} d(u) + FLT_MIN);   y[i] = c(min_period + i), i = 0 .. max_period - min_period
+ *   trough: y[i] < y[i - 1] && y[i] <= y[i + 1] inside, y[0] < y[1] at i = 0, never at the last index
+ *   voiced = some trough has y < trough_threshold;  k = the first such trough, else the lowest-index minimum of y
+ *   shift = -b / a with a = y[k + 1] + y[k - 1] - 2 y[k], b = (y[k + 1] - y[k - 1]) / 2 when |b| < |a|, else 0; 0 at either end
+ *   f0 = sr / (min_period + k + shift) (reported for every frame),  aperiodicity = y[k]
+ * A frame of zeros is unvoiced.  fp32 in both operand-dtype builds, every sum in one fixed order, no atomics: the same
+ * bits from run to run, for a row alone or in a batch, whatever the launch shape.  Samples outside [0, L) of a row are
+ * never read. */
+typedef struct {
+  double fmin, fmax;
+  int32_t sr, frame_length, hop_length;
+  float trough_threshold;
+} jat_yin_params;
+/* [host, no GPU needed] the period range above.  Fails on sr < 1, a frame_length that is odd or outside 16..8192, fmin <= 0,
+ * fmax <= fmin, fmax >= sr / 2, or max_period - min_period < 2. */
+int jat_yin_periods(int32_t sr, double fmin, double fmax, int32_t frame_length, int32_t* min_period, int32_t* max_period);
+/* x fp32 [B, L] (device) -> f0, aperiodicity fp32 [B, frames], voiced uint8 [B, frames].  Optional outputs for unit tests
+ * (NULL: not written): index int32 [B, frames] = k; d and cmndf fp32 [B, frames, max_period + 1] with d[0] = 0, cmndf[0] = 1.
+ * Fails (never faults) on what the period range refuses, hop_length < 1, a threshold that is not finite, L < 1, B outside
+ * 1..65535, or a frame count or frames * (max_period + 1) beyond 31 bits. */
+int jat_yin(const jat_yin_params* params, const float* x, int32_t B, int64_t L, float* f0, float* aperiodicity, uint8_t* voiced,
+            int32_t* index, float* d, float* cmndf, void* stream);
+/* Two tracks (f0 fp32, voiced uint8) [B, frames] -> out fp64 [B, 6] (device), b being the reference track:
+ *   n_ref_voiced (voiced_b), n_both_voiced, n_voicing_errors (the flags differ), n_gross (both voiced, |cents| > gross_cents),
+ *   sum |cents| over the both-voiced frames, sum |cents| over the both-voiced frames that are not gross,
+ * cents = 1200 log2(f0_a / f0_b) in fp64.  One block per row adds in a fixed order; no atomics.  A frame voiced in both
+ * tracks must carry positive f0 in both. */
+int jat_f0_compare(const float* f0_a, const uint8_t* voiced_a, const float* f0_b, const uint8_t* voiced_b, int32_t B,
+                   int32_t frames, double gross_cents, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

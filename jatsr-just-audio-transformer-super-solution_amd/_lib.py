@@ -42,6 +42,11 @@ class JatDacEncoderConfig(C.Structure):
                 ("n_codebooks", C.c_int32), ("codebook_size", C.c_int32), ("codebook_dim", C.c_int32)]
 
 
+class JatYinParams(C.Structure):
+    _fields_ = [("fmin", C.c_double), ("fmax", C.c_double), ("sr", C.c_int32), ("frame_length", C.c_int32),
+                ("hop_length", C.c_int32), ("trough_threshold", C.c_float)]
+
+
 class JatTensorRef(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("numel", C.c_int64)]
 
@@ -169,6 +174,9 @@ SIGNATURES = {
     "jat_bank_search_workspace_bytes": (C.c_int, [_VP, _I64, C.POINTER(_SZ)]),
     "jat_bank_search": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _VP, _VP, _VP, _SZ, _VP]),
     "jat_bank_blend": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _F32, _VP, _I32, _I32, _VP]),
+    "jat_yin_periods": (C.c_int, [_I32, C.c_double, C.c_double, _I32, C.POINTER(_I32), C.POINTER(_I32)]),
+    "jat_yin": (C.c_int, [C.POINTER(JatYinParams), _VP, _I32, _I64] + [_VP] * 7),
+    "jat_f0_compare": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, C.c_double, _VP, _VP]),
 }
 MONITOR_WORK_BYTES = 49152   # JAT_MONITOR_WORK_BYTES
 LTAS_SLICES = 64             # JAT_LTAS_SLICES

@@ -14,6 +14,8 @@ per-channel normalisation (:381-394).  Differences, all outside the hot path's s
   * `--metrics` (with `--dac-weights`, where an HR ground truth exists: `--simulate-lr`, or a latent file with `hr_latent`)
     evaluates the decoded generated / HR / LR audio as the reference's calculate_metrics.py does (jatsr_amd.metrics) and
     writes `{stem}_metrics.json` (with the `_cfgX` suffix of the generated files, if any) next to the WAVs;
+  * `--f0-metrics` (valid where `--metrics` is) adds an `"f0"` entry to that JSON: how far the YIN pitch tracks of the decoded
+    generated and LR audio agree with the HR audio's (jatsr_amd.pitch); without `--metrics` the JSON holds that entry alone;
   * `--lf-replace [HZ]` (with `--dac-weights`) also writes `{stem}_generated{suffix}_lf.wav`: the decoded audio with its
     band below HZ (bare flag: the detected band limit of the source) replaced by the source's own (jatsr_amd.splice,
     csrc/splice.hip).  The source is the 44.1 kHz waveform that was encoded (`--input-audio`), the whole file taken through
@@ -73,6 +75,9 @@ def build_parser():
     p.add_argument("--metrics", action="store_true",
                    help="LSD and mel losses of the decoded generated and LR audio against the HR ground truth, written as "
                         "{stem}_metrics.json (needs --dac-weights and a ground truth: --simulate-lr or a latent file with hr_latent)")
+    p.add_argument("--f0-metrics", action="store_true",
+                   help="YIN pitch tracks of the decoded generated and LR audio against the HR ground truth's: an \"f0\" entry in "
+                        "{stem}_metrics.json (valid where --metrics is; jatsr_amd.pitch)")
     p.add_argument("--lf-replace", type=str, nargs="?", const="auto", default=None, metavar="HZ",
                    help="also write {stem}_generated_lf.wav: the decoded audio with the band below HZ (bare flag: the "
                         "detected band limit of the source) taken from the source waveform (needs --dac-weights).  With a "
@@ -103,6 +108,9 @@ def run(args):
         raise SystemExit("--resample and --simulate-lr need --input-audio")
     if args.metrics and (not args.dac_weights or (args.input_audio and args.simulate_lr is None)):
         raise SystemExit("--metrics needs --dac-weights and an HR ground truth (--simulate-lr, or a latent file with hr_latent)")
+    f0_metrics = getattr(args, "f0_metrics", False)
+    if f0_metrics and (not args.dac_weights or (args.input_audio and args.simulate_lr is None)):
+        raise SystemExit("--f0-metrics needs --dac-weights and an HR ground truth (--simulate-lr, or a latent file with hr_latent)")
     index_bank = getattr(args, "index_bank", None)
     index_rate = index_rate_arg(getattr(args, "index_rate", 0.4)) if index_bank else 0.0
     device = torch.device(args.device)
@@ -123,6 +131,8 @@ def run(args):
         hr, lr = jio.load_latent_file(path)
     if args.metrics and hr is None:
         raise SystemExit(f"--metrics: {path} holds no hr_latent, so there is no ground truth to compare with")
+    if f0_metrics and hr is None:
+        raise SystemExit(f"--f0-metrics: {path} holds no hr_latent, so there is no ground truth to compare with")
     C = model.input_channels
     stats = jio.load_stats(args.stats_file, channels=C, device=device)
 
@@ -229,7 +239,8 @@ def decode_to_wav(args, gen, hr, lr, total, stem, suffix, device, codec=None, so
         outs.append((f"{stem}_hr_gt.wav", hr[None, :, :total].to(device)))
     outs.append((f"{stem}_lr_input.wav", lr[None, :, :total].to(device)))
     decoded = []
-    keep = args.metrics or args.lf_replace is not None
+    f0_metrics = getattr(args, "f0_metrics", False)
+    keep = args.metrics or f0_metrics or args.lf_replace is not None
     for name, z in outs:
         audio = codec.decode(z)                      # [1, 1, frames * 512]
         jio.write_wav_float32(os.path.join(args.output_dir, name), audio[0, 0], codec.sample_rate)
@@ -246,18 +257,26 @@ def decode_to_wav(args, gen, hr, lr, total, stem, suffix, device, codec=None, so
         jio.write_wav_float32(os.path.join(args.output_dir, name), spliced, codec.sample_rate)
         print(f"low band below {hz:.1f} Hz ({'detected' if args.lf_replace == 'auto' else 'given'}) taken from the "
               f"{'decoded LR latent' if source is None else 'input waveform'} -> {name}")
-    if args.metrics:
+    if args.metrics or f0_metrics:
         import json
 
-        from . import metrics
         generated, hr_gt, lr_input = decoded
-        rep = metrics.evaluate(generated, hr_gt, lr_input, sr=codec.sample_rate)
-        print(metrics.format_report(rep))
-        if spliced is not None:
-            lf = metrics.evaluate(spliced, hr_gt, sr=codec.sample_rate)
-            rep["generated_lf"] = lf["generated"]
-            print("low band replaced (generated_lf) vs GT:")
-            print(metrics.format_report(lf))
+        rep = {}
+        if args.metrics:
+            from . import metrics
+            rep = metrics.evaluate(generated, hr_gt, lr_input, sr=codec.sample_rate)
+            print(metrics.format_report(rep))
+            if spliced is not None:
+                lf = metrics.evaluate(spliced, hr_gt, sr=codec.sample_rate)
+                rep["generated_lf"] = lf["generated"]
+                print("low band replaced (generated_lf) vs GT:")
+                print(metrics.format_report(lf))
+        if f0_metrics:
+            from . import pitch
+            rep["f0"] = pitch.f0_metrics(generated, hr_gt, lr_input, sr=codec.sample_rate)
+            print(pitch.format_report(rep["f0"]))
+            if spliced is not None:
+                rep["f0"]["generated_lf"] = pitch.f0_metrics(spliced, hr_gt, sr=codec.sample_rate)["generated"]
         out = os.path.join(args.output_dir, f"{stem}_metrics{suffix}.json")
         with open(out, "w") as f:
             json.dump(rep, f, indent=2)

@@ -12,7 +12,10 @@ the GPU (csrc/resample.hip, csrc/dac_enc.hip).  Differences:
   * the statistics are kept separately for HR and LR (2048 channels: HR first, then LR), over the fp16-rounded values that
     the latent files hold;
   * the encoder runs in the codec's precision (bf16x3 by default), not under fp16 autocast;
-  * consecutive chunks are batched only where their lengths are equal (the reference pads a batch to its first chunk).
+  * consecutive chunks are batched only where their lengths are equal (the reference pads a batch to its first chunk);
+  * `--f0` also stores a pitch track of the HR recording, one value per latent frame (jatsr_amd.pitch: YIN at the codec's
+    44.1 kHz with hop 512 over the whole file, so frame t is centred on the first sample of latent frame t): `hr_f0` fp32 [T]
+    and `hr_voiced` uint8 [T] beside the latents.  Without the flag the files are what they were.
 
     python -m jatsr_amd.prepare --source-dir wavs --output-dir data --dac-weights dac.pth
 """
@@ -73,10 +76,29 @@ def to_codec_rate(x, codec):
     return resample(x, HIGH_SR, codec.sample_rate, CODEC_LOWPASS_WIDTH, CODEC_ROLLOFF)
 
 
-def prepare_audio(audio, sr: int, codec, low_sr: int = 16000, batch: int = 8, device="cuda", timings: dict | None = None):
+def hr_pitch_track(x, sr: int, codec, frames: int):
+    """The peak-normalised mono recording x [L] at `sr` -> (hr_f0 fp32 [frames], hr_voiced uint8 [frames]) on the GPU: YIN
+    (jatsr_amd.pitch defaults, hop 512) on the whole recording at the codec's rate, cut to the latent frame count; frames the
+    track does not reach are f0 = 0 and unvoiced."""
+    import torch
+
+    from .pitch import yin
+    from .resample import resample
+    hr48 = resample(x[None], sr, HIGH_SR) if sr != HIGH_SR else x[None]
+    f0, voiced, _ = yin(to_codec_rate(hr48, codec)[0].contiguous(), sr=codec.sample_rate, hop_length=512)
+    n = min(frames, f0.shape[0])
+    hr_f0 = torch.zeros(frames, dtype=torch.float32, device=f0.device)
+    hr_voiced = torch.zeros(frames, dtype=torch.uint8, device=f0.device)
+    hr_f0[:n], hr_voiced[:n] = f0[:n], voiced[:n].view(torch.uint8)
+    return hr_f0, hr_voiced
+
+
+def prepare_audio(audio, sr: int, codec, low_sr: int = 16000, batch: int = 8, device="cuda", timings: dict | None = None,
+                  f0: bool = False):
     """One recording -> dict(hr_latent fp32 [1024, T], lr_latent, sum fp64 [2048], sq_sum, count, metadata), tensors on the
     GPU; None for a recording shorter than 1 s.  `audio`: [L] or [channels, L], array or tensor; `codec`: a DacCodec with an
-    encoder.  sum / sq_sum: HR channels first, then LR, over the values rounded to fp16; count: T (frames of each)."""
+    encoder.  sum / sq_sum: HR channels first, then LR, over the values rounded to fp16; count: T (frames of each).
+    With `f0` also hr_f0 fp32 [T] and hr_voiced uint8 [T] (hr_pitch_track)."""
     import torch
 
     from . import _lib as L
@@ -138,9 +160,12 @@ def prepare_audio(audio, sr: int, codec, low_sr: int = 16000, batch: int = 8, de
         channel_stats(hr, s[:C], q[:C])
         channel_stats(lr, s[C:], q[C:])
     clock.run("stats", stats)
-    return {"hr_latent": hr, "lr_latent": lr, "sum": s, "sq_sum": q, "count": hr.shape[-1],
-            "metadata": {"duration": duration, "sr": sr, "chunks": len(chunks), "frames": hr.shape[-1],
-                         "hop_48k": hop48, "trim_frames": trim, "valid_frames": valid}}
+    out = {"hr_latent": hr, "lr_latent": lr, "sum": s, "sq_sum": q, "count": hr.shape[-1],
+           "metadata": {"duration": duration, "sr": sr, "chunks": len(chunks), "frames": hr.shape[-1],
+                        "hop_48k": hop48, "trim_frames": trim, "valid_frames": valid}}
+    if f0:
+        out["hr_f0"], out["hr_voiced"] = clock.run("f0", lambda: hr_pitch_track(x, sr, codec, hr.shape[-1]))
+    return out
 
 
 def final_stats(sum_, sq_sum, count, channels: int = 1024) -> dict:
@@ -166,6 +191,8 @@ def build_parser():
     p.add_argument("--low-sr", type=int, default=16000, help="sample rate of the simulated low-resolution audio")
     p.add_argument("--dac-precision", default="bf16x3", choices=["bf16x3", "bf16"], help="DAC encoder arithmetic")
     p.add_argument("--batch", type=int, default=8, help="chunks per resampler / encoder call")
+    p.add_argument("--f0", action="store_true",
+                   help="also store hr_f0 / hr_voiced: a YIN pitch track of the HR recording, one value per latent frame")
     p.add_argument("--device", default="cuda", help="an AMD GPU; there is no CPU path")
     return p
 
@@ -208,13 +235,15 @@ def run(args):
         if codec is None:
             codec = load_dac_codec(args.dac_weights, device=args.device, precision=args.dac_precision)
         x, sr = jio.read_wav(path)
-        res = prepare_audio(x, sr, codec, low_sr=args.low_sr, batch=args.batch, device=args.device)
+        want_f0 = getattr(args, "f0", False)
+        res = prepare_audio(x, sr, codec, low_sr=args.low_sr, batch=args.batch, device=args.device, f0=want_f0)
         if res is None:
             print(f"skipped {path}: shorter than {MIN_SECONDS:g} s")
             report["skipped"].append(path)
             continue
         jio.save_latent_file(out_path, hr_latent=res["hr_latent"], lr_latent=res["lr_latent"],
-                             metadata={"name": stem, "path": path, "duration": res["metadata"]["duration"], "sr": sr})
+                             metadata={"name": stem, "path": path, "duration": res["metadata"]["duration"], "sr": sr},
+                             **({"hr_f0": res["hr_f0"].cpu(), "hr_voiced": res["hr_voiced"].cpu()} if want_f0 else {}))
         s, q = res["sum"].cpu(), res["sq_sum"].cpu()
         total_sum = s if total_sum is None else total_sum + s
         total_sq = q if total_sq is None else total_sq + q
