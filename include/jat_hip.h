@@ -757,6 +757,83 @@ int jat_yin(const jat_yin_params* params, const float* x, int32_t B, int64_t L, 
 int jat_f0_compare(const float* f0_a, const uint8_t* voiced_a, const float* f0_b, const uint8_t* voiced_b, int32_t B,
                    int32_t frames, double gross_cents, double* out, void* stream);
 
+/* ---- pYIN: threshold prior and Viterbi decoding on YIN's normalised difference ----------------------- */
+/* Mauch & Dixon (2014), arranged as librosa.pyin arranges it; the fp64 statement is tests/pyin_ref.py, and equality with
+ * librosa is not claimed.  Departures from librosa are marked (D).  c is the cmndf above, y[i] = c[min_period + i].
+ *  1 candidates: every trough of y by the rule above, each with its parabolic shift(y, i) (taken in fp64 on the fp32 y).
+ *  2 threshold prior: theta_m = fp32(m / N), m = 1 .. N = n_thresholds; beta_m = the Beta(beta_a, beta_b) mass on
+ *    ((m - 1) / N, m / N].  Trough i of height h_i is under threshold m when h_i < theta_m; n(m) = troughs under m,
+ *    p_i(m) = those of them with a smaller lag;
+ *      P_i = sum_{m: h_i < theta_m} beta_m (1 - e^-lambda) e^(-lambda p_i(m)) / (1 - e^(-lambda n(m))),  lambda = boltzmann_parameter,
+ *    and the lowest-index trough of minimum height also receives no_trough_prob * sum_{m: h_i >= theta_m} beta_m.  A frame
+ *    without troughs contributes nothing.  The factors come from fp32 tables made in fp64 (values under FLT_MIN are 0);
+ *    the sum over m runs in one fixed order.
+ *  3 pitch bins: bps = ceil(1 / resolution), n_bins = floor(12 bps log2(fmax / fmin)) + 1; a trough's bin is
+ *    clip(rint(12 bps log2(f0_i / fmin)), 0, n_bins - 1) with f0_i = sr / (min_period + i + shift), in fp64.  (D) librosa
+ *    clips to n_bins, which lands in the unvoiced half and is overwritten.  Where troughs of a frame share a bin the largest
+ *    lag wins.  obs[f, b] is that P;  voiced_prob[f] = clip(sum_b obs[f, b], 0, 1);  every unvoiced state observes
+ *    (1 - voiced_prob) / n_bins.
+ *  4 transition: H = round_half_even(max_transition_rate * 12 * hop_length / sr) * bps;  w(d) = 1 - |d| / (H + 1), |d| <= H;
+ *    from bin r to bin s: w(s - r) / Z_r with Z_r summed over the s inside [0, n_bins); times 1 - switch_prob inside a half
+ *    (voiced / unvoiced), switch_prob across.  (D) a move outside the band is impossible, not log(tiny).  Every one of the
+ *    2 n_bins states is equally likely at the start.
+ *  5 Viterbi in fp32 on the tables logw[2 H + 1], logZ[n_bins], lk = log(1 - switch_prob), ls = log(switch_prob),
+ *    logpi = log(1 / (2 n_bins)), made in fp64 and rounded once:  lo_f[s] = log(obs + FLT_MIN), one value per frame for
+ *    the unvoiced half;  V_0 = lo_0 + logpi;  per frame and half h: U_h[r] = V[r] - logZ[r],
+ *    M_h[s] = max_r (U_h[r] + logw[s - r]) with the lowest r on a tie;  V'[s] = lo_f[s] + max(M_same[s] + lk, M_other[s] + ls),
+ *    the voiced source on a tie;  V' -= max_s V'.  Every step is one rounded fp32 add, subtract or max; nothing is
+ *    contracted or reassociated, so a numpy fp32 replica follows it bit for bit.  The last state is the lowest-index
+ *    maximum (voiced half first), followed back through the back-pointers.
+ *  6 per frame: voiced = state < n_bins;  f0 = freqs[state] where voiced with the host table fp32(fmin 2^(b / (12 bps))),
+ *    (D) 0 where unvoiced (librosa: NaN);  voiced_prob.  f0 is quantised to bins of 100 resolution cents.
+ * The same bits from run to run, for a row alone or in a batch, and from both operand-dtype builds. */
+typedef struct {
+  double fmin, fmax;
+  int32_t sr, frame_length, hop_length, n_thresholds;
+  double beta_a, beta_b, boltzmann_parameter, resolution, max_transition_rate, switch_prob, no_trough_prob;
+} jat_pyin_params;
+typedef struct jat_pyin jat_pyin;
+/* [host, no GPU needed] out[m - 1] = beta_m, m = 1 .. n: the regularised incomplete beta function by its continued fraction,
+ * fp64.  Fails on a or b that is not positive and finite, n outside 1..65536. */
+int jat_pyin_beta_probs(double a, double b, int32_t n, double* out);
+/* [host, no GPU needed]  A handle serves ONE device and one thread at a time: the first track or decode allocates the
+ * tables on the device that is current then and copies them with a synchronous hipMalloc + hipMemcpy (so that first call
+ * must not lie inside a stream capture), and every later call on another current device fails with JAT_E_STATE before
+ * anything is launched.  The profile switch and its events are state of the handle too.  Fails with JAT_E_INVALID on everything the
+ * period range and the YIN entry point refuse, n_thresholds outside 1..256, beta_a, beta_b, boltzmann_parameter or
+ * max_transition_rate that is not positive and finite, switch_prob or no_trough_prob outside (0, 1), resolution outside
+ * (0, 1], and beyond the sizes the kernels are built for: n_bins <= 1024, H <= 128, max_period - min_period + 1 <= 4096
+ * candidates (every frame_length up to 8192 stays inside). */
+int jat_pyin_create(const jat_pyin_params* params, jat_pyin** out);
+void jat_pyin_destroy(jat_pyin* h);
+/* each output may be NULL */
+int jat_pyin_shape(const jat_pyin* h, int32_t* n_bins, int32_t* H, int32_t* min_period, int32_t* max_period);
+/* [host] copies of the tables, each may be NULL: beta fp64 [n_thresholds]; logw fp32 [2 H + 1] (index d + H); logZ and freqs
+ * fp32 [n_bins]; scalars fp32 [3] = lk, ls, logpi */
+int jat_pyin_tables(const jat_pyin* h, double* beta, float* logw, float* logZ, float* freqs, float* scalars);
+/* Fails as the track does on B, L and sizes beyond 31 bits. */
+int jat_pyin_workspace_bytes(const jat_pyin* h, int32_t B, int64_t L, size_t* bytes);
+/* x fp32 [B, L] (device) -> f0 fp32, voiced uint8, voiced_prob fp32, each [B, frames], frames = 1 + L / hop_length.
+ * Optional outputs for unit tests (NULL: not written): cmndf fp32 [B, frames, max_period + 1]; prob fp32 [B, frames, ny]
+ * (0 where there is no trough) and bin int32 [B, frames, ny] (-1 where there is none), ny = max_period - min_period + 1;
+ * obs fp32 [B, frames, n_bins]; log_obs fp32 [B, frames, n_bins + 1] (the last entry is the unvoiced value); state int32
+ * [B, frames] in 0 .. 2 n_bins - 1, the voiced half first.  work: 16-byte aligned device memory of at least the bytes the
+ * query above returns (the difference function, the log observations, 16-bit back-pointers).
+ * Fails, writing nothing, with JAT_E_INVALID on B outside 1..65535, L < 1, a frame count or frames times the values per
+ * frame beyond 31 bits, a NULL x, f0, voiced, voiced_prob or work; with JAT_E_STATE on a workspace that is too small. */
+int jat_pyin_track(jat_pyin* h, const float* x, int32_t B, int64_t L, float* f0, uint8_t* voiced, float* voiced_prob, float* cmndf,
+                   float* prob, int32_t* bin, float* obs, float* log_obs, int32_t* state, void* work, size_t work_bytes,
+                   void* stream);
+/* Stages 5 and 6 alone, on log observations the caller supplies (the decoder's unit tests drive it with constructed ties):
+ * log_obs fp32 [B, frames, n_bins + 1] (device) -> state int32, f0 fp32, voiced uint8, each [B, frames].  work: 16-byte
+ * aligned, at least B * frames * n_bins * 4 bytes (the back-pointers).  Fails as the track does. */
+int jat_pyin_decode(jat_pyin* h, const float* log_obs, int32_t B, int32_t frames, int32_t* state, float* f0, uint8_t* voiced,
+                    void* work, size_t work_bytes, void* stream);
+/* measurement aid (tools/pyin_bench.py): with on != 0 every track records device events around its four launches */
+int jat_pyin_set_profile(jat_pyin* h, int32_t on);
+/* waits for the latest profiled track; us[4] = difference function, observation, Viterbi forward, back-trace, in microseconds */
+int jat_pyin_profile(jat_pyin* h, float* us);
+
 #ifdef __cplusplus
 }
 #endif

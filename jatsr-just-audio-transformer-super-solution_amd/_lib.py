@@ -47,6 +47,13 @@ class JatYinParams(C.Structure):
                 ("hop_length", C.c_int32), ("trough_threshold", C.c_float)]
 
 
+class JatPyinParams(C.Structure):
+    _fields_ = [("fmin", C.c_double), ("fmax", C.c_double), ("sr", C.c_int32), ("frame_length", C.c_int32),
+                ("hop_length", C.c_int32), ("n_thresholds", C.c_int32), ("beta_a", C.c_double), ("beta_b", C.c_double),
+                ("boltzmann_parameter", C.c_double), ("resolution", C.c_double), ("max_transition_rate", C.c_double),
+                ("switch_prob", C.c_double), ("no_trough_prob", C.c_double)]
+
+
 class JatTensorRef(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("numel", C.c_int64)]
 
@@ -177,6 +184,16 @@ SIGNATURES = {
     "jat_yin_periods": (C.c_int, [_I32, C.c_double, C.c_double, _I32, C.POINTER(_I32), C.POINTER(_I32)]),
     "jat_yin": (C.c_int, [C.POINTER(JatYinParams), _VP, _I32, _I64] + [_VP] * 7),
     "jat_f0_compare": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, C.c_double, _VP, _VP]),
+    "jat_pyin_beta_probs": (C.c_int, [C.c_double, C.c_double, _I32, _VP]),
+    "jat_pyin_create": (C.c_int, [C.POINTER(JatPyinParams), C.POINTER(_VP)]),
+    "jat_pyin_destroy": (None, [_VP]),
+    "jat_pyin_shape": (C.c_int, [_VP] + [C.POINTER(_I32)] * 4),
+    "jat_pyin_tables": (C.c_int, [_VP] * 6),
+    "jat_pyin_workspace_bytes": (C.c_int, [_VP, _I32, _I64, C.POINTER(_SZ)]),
+    "jat_pyin_track": (C.c_int, [_VP, _VP, _I32, _I64] + [_VP] * 10 + [_SZ, _VP]),
+    "jat_pyin_decode": (C.c_int, [_VP, _VP, _I32, _I32, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "jat_pyin_set_profile": (C.c_int, [_VP, _I32]),
+    "jat_pyin_profile": (C.c_int, [_VP, _VP]),
 }
 MONITOR_WORK_BYTES = 49152   # JAT_MONITOR_WORK_BYTES
 LTAS_SLICES = 64             # JAT_LTAS_SLICES

@@ -16,6 +16,7 @@ per-channel normalisation (:381-394).  Differences, all outside the hot path's s
     writes `{stem}_metrics.json` (with the `_cfgX` suffix of the generated files, if any) next to the WAVs;
   * `--f0-metrics` (valid where `--metrics` is) adds an `"f0"` entry to that JSON: how far the YIN pitch tracks of the decoded
     generated and LR audio agree with the HR audio's (jatsr_amd.pitch); without `--metrics` the JSON holds that entry alone;
+    `--f0-method pyin` takes the tracks with pYIN instead and records `"method": "pyin"` inside that entry;
   * `--lf-replace [HZ]` (with `--dac-weights`) also writes `{stem}_generated{suffix}_lf.wav`: the decoded audio with its
     band below HZ (bare flag: the detected band limit of the source) replaced by the source's own (jatsr_amd.splice,
     csrc/splice.hip).  The source is the 44.1 kHz waveform that was encoded (`--input-audio`), the whole file taken through
@@ -78,6 +79,8 @@ def build_parser():
     p.add_argument("--f0-metrics", action="store_true",
                    help="YIN pitch tracks of the decoded generated and LR audio against the HR ground truth's: an \"f0\" entry in "
                         "{stem}_metrics.json (valid where --metrics is; jatsr_amd.pitch)")
+    p.add_argument("--f0-method", choices=("yin", "pyin"), default="yin",
+                   help="with --f0-metrics: the tracker; pyin adds \"method\": \"pyin\" to the \"f0\" entry")
     p.add_argument("--lf-replace", type=str, nargs="?", const="auto", default=None, metavar="HZ",
                    help="also write {stem}_generated_lf.wav: the decoded audio with the band below HZ (bare flag: the "
                         "detected band limit of the source) taken from the source waveform (needs --dac-weights).  With a "
@@ -273,10 +276,12 @@ def decode_to_wav(args, gen, hr, lr, total, stem, suffix, device, codec=None, so
                 print(metrics.format_report(lf))
         if f0_metrics:
             from . import pitch
-            rep["f0"] = pitch.f0_metrics(generated, hr_gt, lr_input, sr=codec.sample_rate)
-            print(pitch.format_report(rep["f0"]))
+            f0_kw = {"method": "pyin"} if getattr(args, "f0_method", "yin") == "pyin" else {}
+            rep["f0"] = pitch.f0_metrics(generated, hr_gt, lr_input, sr=codec.sample_rate, **f0_kw)
+            print(pitch.format_report(rep["f0"], **f0_kw))
             if spliced is not None:
-                rep["f0"]["generated_lf"] = pitch.f0_metrics(spliced, hr_gt, sr=codec.sample_rate)["generated"]
+                rep["f0"]["generated_lf"] = pitch.f0_metrics(spliced, hr_gt, sr=codec.sample_rate, **f0_kw)["generated"]
+            rep["f0"].update(f0_kw)
         out = os.path.join(args.output_dir, f"{stem}_metrics{suffix}.json")
         with open(out, "w") as f:
             json.dump(rep, f, indent=2)

@@ -15,7 +15,8 @@ the GPU (csrc/resample.hip, csrc/dac_enc.hip).  Differences:
   * consecutive chunks are batched only where their lengths are equal (the reference pads a batch to its first chunk);
   * `--f0` also stores a pitch track of the HR recording, one value per latent frame (jatsr_amd.pitch: YIN at the codec's
     44.1 kHz with hop 512 over the whole file, so frame t is centred on the first sample of latent frame t): `hr_f0` fp32 [T]
-    and `hr_voiced` uint8 [T] beside the latents.  Without the flag the files are what they were.
+    and `hr_voiced` uint8 [T] beside the latents.  Without the flag the files are what they were.  `--f0-method pyin` takes
+    the track with pYIN (f0 quantised to 10-cent bins, 0 where unvoiced) and also stores `hr_voiced_prob` fp32 [T].
 
     python -m jatsr_amd.prepare --source-dir wavs --output-dir data --dac-weights dac.pth
 """
@@ -76,29 +77,37 @@ def to_codec_rate(x, codec):
     return resample(x, HIGH_SR, codec.sample_rate, CODEC_LOWPASS_WIDTH, CODEC_ROLLOFF)
 
 
-def hr_pitch_track(x, sr: int, codec, frames: int):
+def hr_pitch_track(x, sr: int, codec, frames: int, method: str = "yin"):
     """The peak-normalised mono recording x [L] at `sr` -> (hr_f0 fp32 [frames], hr_voiced uint8 [frames]) on the GPU: YIN
     (jatsr_amd.pitch defaults, hop 512) on the whole recording at the codec's rate, cut to the latent frame count; frames the
-    track does not reach are f0 = 0 and unvoiced."""
+    track does not reach are f0 = 0 and unvoiced.  method "pyin": the pYIN track instead, and a third value, hr_voiced_prob
+    fp32 [frames] (0 where the track does not reach)."""
     import torch
 
-    from .pitch import yin
+    from .pitch import pyin, yin
     from .resample import resample
+    if method not in ("yin", "pyin"):
+        raise ValueError(f"prepare: f0 method must be 'yin' or 'pyin', got {method!r}")
     hr48 = resample(x[None], sr, HIGH_SR) if sr != HIGH_SR else x[None]
-    f0, voiced, _ = yin(to_codec_rate(hr48, codec)[0].contiguous(), sr=codec.sample_rate, hop_length=512)
+    f0, voiced, third = (yin if method == "yin" else pyin)(to_codec_rate(hr48, codec)[0].contiguous(), sr=codec.sample_rate,
+                                                           hop_length=512)
     n = min(frames, f0.shape[0])
     hr_f0 = torch.zeros(frames, dtype=torch.float32, device=f0.device)
     hr_voiced = torch.zeros(frames, dtype=torch.uint8, device=f0.device)
     hr_f0[:n], hr_voiced[:n] = f0[:n], voiced[:n].view(torch.uint8)
-    return hr_f0, hr_voiced
+    if method == "yin":
+        return hr_f0, hr_voiced
+    hr_prob = torch.zeros(frames, dtype=torch.float32, device=f0.device)
+    hr_prob[:n] = third[:n]
+    return hr_f0, hr_voiced, hr_prob
 
 
 def prepare_audio(audio, sr: int, codec, low_sr: int = 16000, batch: int = 8, device="cuda", timings: dict | None = None,
-                  f0: bool = False):
+                  f0: bool = False, f0_method: str = "yin"):
     """One recording -> dict(hr_latent fp32 [1024, T], lr_latent, sum fp64 [2048], sq_sum, count, metadata), tensors on the
     GPU; None for a recording shorter than 1 s.  `audio`: [L] or [channels, L], array or tensor; `codec`: a DacCodec with an
     encoder.  sum / sq_sum: HR channels first, then LR, over the values rounded to fp16; count: T (frames of each).
-    With `f0` also hr_f0 fp32 [T] and hr_voiced uint8 [T] (hr_pitch_track)."""
+    With `f0` also hr_f0 fp32 [T] and hr_voiced uint8 [T] (hr_pitch_track), and with f0_method "pyin" hr_voiced_prob fp32 [T]."""
     import torch
 
     from . import _lib as L
@@ -163,8 +172,11 @@ def prepare_audio(audio, sr: int, codec, low_sr: int = 16000, batch: int = 8, de
     out = {"hr_latent": hr, "lr_latent": lr, "sum": s, "sq_sum": q, "count": hr.shape[-1],
            "metadata": {"duration": duration, "sr": sr, "chunks": len(chunks), "frames": hr.shape[-1],
                         "hop_48k": hop48, "trim_frames": trim, "valid_frames": valid}}
-    if f0:
+    if f0 and f0_method == "yin":
         out["hr_f0"], out["hr_voiced"] = clock.run("f0", lambda: hr_pitch_track(x, sr, codec, hr.shape[-1]))
+    elif f0:
+        out["hr_f0"], out["hr_voiced"], out["hr_voiced_prob"] = clock.run(
+            "f0", lambda: hr_pitch_track(x, sr, codec, hr.shape[-1], f0_method))
     return out
 
 
@@ -193,6 +205,8 @@ def build_parser():
     p.add_argument("--batch", type=int, default=8, help="chunks per resampler / encoder call")
     p.add_argument("--f0", action="store_true",
                    help="also store hr_f0 / hr_voiced: a YIN pitch track of the HR recording, one value per latent frame")
+    p.add_argument("--f0-method", choices=("yin", "pyin"), default="yin",
+                   help="with --f0: the tracker; pyin also stores hr_voiced_prob fp32 [T]")
     p.add_argument("--device", default="cuda", help="an AMD GPU; there is no CPU path")
     return p
 
@@ -236,14 +250,16 @@ def run(args):
             codec = load_dac_codec(args.dac_weights, device=args.device, precision=args.dac_precision)
         x, sr = jio.read_wav(path)
         want_f0 = getattr(args, "f0", False)
-        res = prepare_audio(x, sr, codec, low_sr=args.low_sr, batch=args.batch, device=args.device, f0=want_f0)
+        f0_method = getattr(args, "f0_method", "yin")
+        res = prepare_audio(x, sr, codec, low_sr=args.low_sr, batch=args.batch, device=args.device, f0=want_f0,
+                            **({"f0_method": f0_method} if f0_method != "yin" else {}))
         if res is None:
             print(f"skipped {path}: shorter than {MIN_SECONDS:g} s")
             report["skipped"].append(path)
             continue
         jio.save_latent_file(out_path, hr_latent=res["hr_latent"], lr_latent=res["lr_latent"],
                              metadata={"name": stem, "path": path, "duration": res["metadata"]["duration"], "sr": sr},
-                             **({"hr_f0": res["hr_f0"].cpu(), "hr_voiced": res["hr_voiced"].cpu()} if want_f0 else {}))
+                             **({k: res[k].cpu() for k in ("hr_f0", "hr_voiced", "hr_voiced_prob") if k in res} if want_f0 else {}))
         s, q = res["sum"].cpu(), res["sq_sum"].cpu()
         total_sum = s if total_sum is None else total_sum + s
         total_sq = q if total_sq is None else total_sq + q
