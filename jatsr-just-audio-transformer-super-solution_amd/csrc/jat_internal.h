@@ -149,3 +149,22 @@ struct DwScratch { size_t split_floats, colsum_floats; };
 DwScratch jat_weight_grad_scratch(int tokens, int out, int in, int ksplit, bool with_db);
 int jat_weight_grad(const bf16_t* dY, const bf16_t* X, float* dW, float* db, int tokens, int out, int in, int ksplit,
                     const void* zeros, float* split, float* colsum, bool acc, hipStream_t s);
+
+// ---- the training loss (jat_loss.cpp): rw * recon + lw * (fw * freq + mw * ms + cw * cons), recon = Charbonnier(recon_eps) for
+// recon_eps > 0, MSE for 0.  Defaults: the V3 trainer's plain MSE.  A new loss variant is a field here and a branch in run_loss.
+struct LossSpec {
+  double recon_eps = 0.0, rw = 1.0, lw = 0.0, fw = 0.5, mw = 0.5, cw = 0.1, phase_ratio = 0.3, strict_cut = 0.30, soft_cut = 0.36;
+  bool has_latent() const { return lw != 0.0; }
+};
+// the argument checks of the loss setters and entry points: JAT_OK, or JAT_E_INVALID with its text set
+int check_band_ratios(const LossSpec& l), check_recon_eps(const LossSpec& l), check_loss_weights(const LossSpec& l);
+// One loss launch on [rows, T], host arithmetic only (ratios that passed check_band_ratios): the latent kernels (they hold the
+// reconstruction term too) or the reconstruction kernel alone; band edges in rfft bins; the latent kernels' path at T; scratch bytes:
+// recon = train_red_blocks() partial sums + the 2-float result, latent = tw_bytes ([T] twiddles padded to 256 B) + rows * 8 partials
+struct LossLaunch { bool latent; int low, strict, soft; LatentLossPlan path; size_t recon_bytes, tw_bytes, latent_bytes; };
+LossLaunch plan_loss(const LossSpec& l, int64_t rows, int T);
+std::vector<float2> make_twiddles(int T);   // (cos, sin)(2 pi i / T)
+// The one place a loss is launched: dpred = d(loss * loss_scale)/d pred and out = {rw * recon, scratch} (reconstruction; lr, tw unused)
+// or the six terms {total, recon, freq, ms, cons, latent} (latent; lr may be null when cw == 0); part: the family's partial sums
+int run_loss(const LossSpec& l, const LossLaunch& p, const float* pred, const float* target, const float* lr, const float2* tw,
+             float* dpred, float* part, float* out, int64_t rows, int T, float loss_scale, hipStream_t s);

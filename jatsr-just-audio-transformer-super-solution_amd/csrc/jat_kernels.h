@@ -202,16 +202,14 @@ hipError_t launch_norm_bwd(const float* x, const bf16_t* dy, const float* w, con
 hipError_t launch_attention_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* vt, const bf16_t* o, const bf16_t* dout,
                                 const float* lse, float* delta, bf16_t* dqkv, const float* rope_cos, const float* rope_sin,
                                 int B, int N, int Hq, int Hkv, int npad, DropSpec drop, float* dkv_part, hipStream_t s);
-// rw: weight of the loss (the v3mod3 trainer's reconstruction_weight): loss2[0] = rw * mse and its gradient, by host arithmetic
-hipError_t launch_mse_grad(const float* pred, const float* target, float* dpred, float* part, float* loss2, int64_t n,
-                           float loss_scale, float rw, hipStream_t s);
-// Charbonnier loss mean(sqrt((pred - target)^2 + eps)) (train_ddp_v3m2mod1.py:72-101) and d(loss * loss_scale)/d pred;
-// part: train_red_blocks() floats, loss2[0] = rw * loss
-hipError_t launch_charbonnier_grad(const float* pred, const float* target, float* dpred, float* part, float* loss2, int64_t n,
-                                   float eps, float loss_scale, float rw, hipStream_t s);
+// reconstruction loss and d(loss * loss_scale)/d pred: eps > 0 the Charbonnier loss mean(sqrt((pred - target)^2 + eps))
+// (train_ddp_v3m2mod1.py:72-101), else the MSE; part: train_red_blocks() floats.  rw: weight of the loss (the v3mod3 trainer's
+// reconstruction_weight): loss2[0] = rw * loss and its gradient, by host arithmetic
+hipError_t launch_recon_grad(const float* pred, const float* target, float* dpred, float* part, float* loss2, int64_t n, double eps,
+                             float loss_scale, float rw, hipStream_t s);
 // v3mod2 loss (MSE + lw * (fw*freq + mw*ms + cw*cons)): dpred = d(loss * loss_scale)/d pred, out6 = {total, mse, freq, ms,
 // cons, fw*freq + mw*ms + cw*cons}; part: rows*8 floats; tw: [T] (cos, sin)(2 pi m / T); lr may be null when cw == 0.
-// low / strict / soft band edges (in rfft bins) are computed by the caller exactly as the reference does (int(F * ratio)).
+// low / strict / soft: band edges in rfft bins (plan_loss).
 // recon_eps / recon_weight: the v3mod3 loss, recon_weight * recon + lw * (...), recon = Charbonnier(recon_eps) for recon_eps > 0,
 // MSE for 0; out6[1] is the un-weighted recon term.  (0, 1) is the v3mod2 loss on the kernels it always had.
 // The path launch_latent_loss takes at sequence length T (the one place that decides it): kind 0 = rejected (the direct LDS

@@ -11,10 +11,7 @@
 //   dW = dy^T x        jat_weight_grad below
 #include <algorithm>
 #include <array>
-#include <cmath>
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -61,10 +58,7 @@ struct jat_trainer {
   CopyJob* copy_jobs = nullptr;        // device table: fp32 master slices -> the model's fp32 operand tensors
   int n_copy_jobs = 0;
   float* dw_part = nullptr;
-  // v3mod2 latent perceptual loss (jat_trainer_set_latent_loss); lw == 0: plain MSE (the V3 trainer)
-  double lw = 0.0, fw = 0.5, mw = 0.5, cw = 0.1, phase_ratio = 0.3, strict_cut = 0.30, soft_cut = 0.36;
-  double charb_eps = 0.0;              // > 0: Charbonnier reconstruction loss (train_ddp_v3m2mod1.py:72-101) instead of MSE
-  double rw = 1.0;                     // weight of the reconstruction term (jat_trainer_set_loss_ex; train_ddp_v3mod3.py:416,966)
+  LossSpec loss;                       // the three jat_trainer_set_* loss setters; default: plain MSE (the V3 trainer)
   float2* tw = nullptr;                // [T] twiddles
   float *ll_part = nullptr, *terms = nullptr;
   float* dw_split = nullptr;           // split-K partial slices of the dW GEMMs
@@ -85,6 +79,18 @@ struct jat_trainer {
   // the call in flight (jat_trainer_fwd_bwd_ex flags): accum: every writer of grads_flat, and the loss cells, add to what is there;
   // no_hook: the gradient-ready hook stays silent (not the last micro-batch of the optimiser step)
   bool accum = false, no_hook = false;
+
+  // whatever jat_trainer_create got as far as making: the second stream (drained first: its work reads the workspace), the events,
+  // the workspace
+  ~jat_trainer() {
+    if (dw_stream) { (void)hipStreamSynchronize(dw_stream); (void)hipStreamDestroy(dw_stream); }
+    auto drop = [](hipEvent_t e) { if (e) (void)hipEventDestroy(e); };
+    for (int k = 0; k < 4; ++k)
+      for (int q = 0; q < 2; ++q) { drop(ev_ready[k][q]); drop(ev_done[k][q]); }
+    for (hipEvent_t e : {ev_join, ev_wt, ev_mod[0], ev_mod[1]}) drop(e);
+    for (hipEvent_t e : ev_layer) drop(e);
+    if (blob) (void)hipFree(blob);
+  }
 };
 
 namespace {
@@ -238,22 +244,12 @@ int backward_train(jat_trainer* tr, const float* target, const float* cond_clean
   float* G = tr->G;
   const bool acc = tr->accum;
   // the loss cells add up as the gradients do: kept aside here, added back in behind the loss kernels
-  float *terms = tr->lw != 0.0 ? tr->terms : nullptr, *terms_keep = tr->lw != 0.0 ? tr->terms + 8 : nullptr;
+  // the loss lands in scal[0]; a loss with a latent term writes its six terms and their total is copied there
+  float *terms = tr->loss.has_latent() ? tr->terms : nullptr, *terms_keep = terms ? terms + 8 : nullptr;
   if (acc) KCHK(launch_loss_carry(tr->scal, tr->scal + 12, terms, terms_keep, 0, s));
-  if (tr->lw != 0.0) {
-    const int F = T / 2 + 1;   // band edges exactly as the reference computes them: int(freq_bins * ratio) in double
-    KCHK(launch_latent_loss(tr->pred, target, cond_clean, tr->tw, tr->dpred, tr->ll_part, tr->terms, B * m->Cin, T,
-                            (float)tr->lw, (float)tr->fw, (float)tr->mw, (float)tr->cw, (int)((double)F * tr->phase_ratio),
-                            (int)((double)F * tr->strict_cut), (int)((double)F * tr->soft_cut), (float)tr->charb_eps,
-                            (float)tr->rw, loss_scale, s));
-    HIPCHK(hipMemcpyAsync(tr->scal, tr->terms, 4, hipMemcpyDeviceToDevice, s));
-  } else if (tr->charb_eps > 0.0) {
-    KCHK(launch_charbonnier_grad(tr->pred, target, tr->dpred, tr->red_part, tr->scal, (int64_t)B * m->Cin * T,
-                                 (float)tr->charb_eps, loss_scale, (float)tr->rw, s));
-  } else {
-    KCHK(launch_mse_grad(tr->pred, target, tr->dpred, tr->red_part, tr->scal, (int64_t)B * m->Cin * T, loss_scale,
-                         (float)tr->rw, s));
-  }
+  JCHK(run_loss(tr->loss, plan_loss(tr->loss, B * m->Cin, T), tr->pred, target, cond_clean, tr->tw, tr->dpred,
+                terms ? tr->ll_part : tr->red_part, terms ? terms : tr->scal, B * m->Cin, T, loss_scale, s));
+  if (terms) HIPCHK(hipMemcpyAsync(tr->scal, terms, 4, hipMemcpyDeviceToDevice, s));
   if (acc) KCHK(launch_loss_carry(tr->scal, tr->scal + 12, terms, terms_keep, 1, s));
   // Where a weight gradient runs: on `s` itself, or (dw_async) on the second stream behind an event of the kernel that
   // finished its gradient operand; `done` is what the next writer of that operand buffer waits for.
@@ -391,21 +387,7 @@ int jat_weight_grad(const bf16_t* dY, const bf16_t* X, float* dW, float* db, int
   return JAT_OK;
 }
 
-extern "C" void jat_trainer_destroy(jat_trainer* tr) {
-  if (!tr) return;
-  if (tr->dw_stream) { (void)hipStreamSynchronize(tr->dw_stream); (void)hipStreamDestroy(tr->dw_stream); }
-  for (int k = 0; k < 4; ++k)
-    for (int q = 0; q < 2; ++q) {
-      if (tr->ev_ready[k][q]) (void)hipEventDestroy(tr->ev_ready[k][q]);
-      if (tr->ev_done[k][q]) (void)hipEventDestroy(tr->ev_done[k][q]);
-    }
-  if (tr->ev_join) (void)hipEventDestroy(tr->ev_join);
-  if (tr->ev_wt) (void)hipEventDestroy(tr->ev_wt);
-  for (int q = 0; q < 2; ++q) if (tr->ev_mod[q]) (void)hipEventDestroy(tr->ev_mod[q]);
-  for (hipEvent_t e : tr->ev_layer) if (e) (void)hipEventDestroy(e);
-  if (tr->blob) (void)hipFree(tr->blob);
-  delete tr;
-}
+extern "C" void jat_trainer_destroy(jat_trainer* tr) { delete tr; }
 
 extern "C" int jat_trainer_create(jat_model* m, const jat_tensor_ref* params, int32_t n, float* params_flat,
                                   float* grads_flat, float* exp_avg, float* exp_avg_sq, int64_t total, int32_t B,
@@ -422,7 +404,8 @@ extern "C" int jat_trainer_create(jat_model* m, const jat_tensor_ref* params, in
   const int ntok = (T + 3) / 4;
   if (ntok > MAX_LEN) return fail(JAT_E_SEQLEN, "Sequence length %d exceeds max_len %d", ntok, MAX_LEN);
   hipStream_t s = (hipStream_t)stream;
-  jat_trainer* tr = new jat_trainer();
+  auto owner = std::make_unique<jat_trainer>();   // every error return below releases what was created so far
+  jat_trainer* tr = owner.get();
   tr->m = m; tr->B = B; tr->T = T; tr->ntok = ntok; tr->M = B * ntok;
   tr->npad = (int)align_up((size_t)ntok, 64);
   tr->P = params_flat; tr->G = grads_flat; tr->m1 = exp_avg; tr->m2 = exp_avg_sq; tr->total = total;
@@ -434,19 +417,15 @@ extern "C" int jat_trainer_create(jat_model* m, const jat_tensor_ref* params, in
   // every weight gradient runs on gemm_tn.hip.  jat_model_create's divisibility rules imply this; a model that broke it would
   // otherwise fail at its first backward launch
   for (auto& sh : dw_shapes(m))
-    if (!gemm_tn_supports(sh[0], sh[1])) {
-      delete tr;
+    if (!gemm_tn_supports(sh[0], sh[1]))
       return fail(JAT_E_INVALID, "weight [%d, %d]: the weight-gradient GEMM needs both widths to be multiples of 128", sh[0], sh[1]);
-    }
 
   // ---- parameter table: every tensor must lie inside the flat buffer, 16-B aligned, with the expected size ----
   std::unordered_map<std::string, const jat_tensor_ref*> given;
   for (int i = 0; i < n; ++i) {
     const int64_t o = params[i].data - params_flat;
-    if (o < 0 || o + params[i].numel > total || o % 4 != 0) {
-      delete tr;
+    if (o < 0 || o + params[i].numel > total || o % 4 != 0)
       return fail(JAT_E_INVALID, "parameter '%s' is not a 16-byte aligned slice of the flat buffer", params[i].name);
-    }
     given[params[i].name] = &params[i];
   }
   // every parameter of the model resolved to its offset; per group (head, block l, final layer = block `depth`) the range it
@@ -477,7 +456,7 @@ extern "C" int jat_trainer_create(jat_model* m, const jat_tensor_ref* params, in
     rc = fail(JAT_E_INVALID, "patch_embed / t_embedder parameters must precede the blocks in the flat buffer");
   if (rc == JAT_OK && used != (size_t)n)
     rc = fail(JAT_E_INVALID, "%d parameters given, %zu belong to this model: every trainable tensor must be known", n, used);
-  if (rc != JAT_OK) { delete tr; return rc; }
+  if (rc != JAT_OK) return rc;
 
   tr->dw_async = true;   // measured: 61.2 -> 58.5 ms per step at T = 1378, 33.3 -> 31.5 ms at T = 512 (profiles/r03/train_dw_stream_ab.log)
   if (const char* e = getenv("JAT_DW_STREAM")) tr->dw_async = atoi(e) != 0;
@@ -494,7 +473,7 @@ extern "C" int jat_trainer_create(jat_model* m, const jat_tensor_ref* params, in
     mk(&tr->ev_join); mk(&tr->ev_wt); mk(&tr->ev_mod[0]); mk(&tr->ev_mod[1]);
     tr->ev_layer.assign((size_t)depth + 1, nullptr);
     for (auto& e : tr->ev_layer) mk(&e);
-    if (!ok) { jat_trainer_destroy(tr); return fail(JAT_E_HIP, "stream / event creation for the weight-gradient stream failed"); }
+    if (!ok) return fail(JAT_E_HIP, "stream / event creation for the weight-gradient stream failed");
   }
   // ---- one allocation: transposed weights, saved activations, backward scratch ----
   const size_t n_f32 = std::count_if(m->params.begin(), m->params.end(), [](const ParamDesc& e) { return e.form == F_F32; });
@@ -567,12 +546,10 @@ extern "C" int jat_trainer_create(jat_model* m, const jat_tensor_ref* params, in
     tr->colsum_part = (float*)take(colsum_f * 4);
     if (pass == 0) {
       tr->blob_bytes = o;
-      if (hipMalloc((void**)&tr->blob, o) != hipSuccess) {
-        delete tr;
+      if (hipMalloc((void**)&tr->blob, o) != hipSuccess)
         return fail(JAT_E_HIP, "hipMalloc of %zu bytes for the training workspace failed", o);
-      }
       // zero once: the key padding of every V^T buffer must be 0 and is never written afterwards
-      if (hipMemsetAsync(tr->blob, 0, o, s) != hipSuccess) { jat_trainer_destroy(tr); return fail(JAT_E_HIP, "memset failed"); }
+      if (hipMemsetAsync(tr->blob, 0, o, s) != hipSuccess) return fail(JAT_E_HIP, "memset failed");
     }
   }
   {
@@ -581,27 +558,17 @@ extern "C" int jat_trainer_create(jat_model* m, const jat_tensor_ref* params, in
       if (e.form == F_F32 && m->has(e)) jobs.push_back(CopyJob{params_flat + tr->offset_of(e), m->at<float>(e), e.numel()});
     tr->n_copy_jobs = (int)jobs.size();
     if (hipMemcpyAsync(tr->copy_jobs, jobs.data(), jobs.size() * sizeof(CopyJob), hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess) {
-      jat_trainer_destroy(tr);
+        hipStreamSynchronize(s) != hipSuccess)
       return fail(JAT_E_HIP, "copy-table upload failed");
-    }
   }
-  {
-    std::vector<float2> tw(T);
-    for (int i = 0; i < T; ++i) {
-      const double th = 2.0 * M_PI * (double)i / (double)T;
-      tw[i] = float2{(float)cos(th), (float)sin(th)};
-    }
-    if (hipMemcpyAsync(tr->tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice, s) != hipSuccess ||
-        hipStreamSynchronize(s) != hipSuccess) {
-      jat_trainer_destroy(tr);
-      return fail(JAT_E_HIP, "twiddle upload failed");
-    }
-  }
+  const std::vector<float2> tw = make_twiddles(T);
+  if (hipMemcpyAsync(tr->tw, tw.data(), tw.size() * sizeof(float2), hipMemcpyHostToDevice, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return fail(JAT_E_HIP, "twiddle upload failed");
   rc = build_transposes(tr, s);   // the model's own copies were packed from these very tensors by jat_model_load_weights
-  if (rc != JAT_OK) { jat_trainer_destroy(tr); return rc; }
-  if (hipStreamSynchronize(s) != hipSuccess) { jat_trainer_destroy(tr); return fail(JAT_E_HIP, "trainer setup failed"); }
-  *out = tr;
+  if (rc != JAT_OK) return rc;
+  if (hipStreamSynchronize(s) != hipSuccess) return fail(JAT_E_HIP, "trainer setup failed");
+  *out = owner.release();
   return JAT_OK;
 }
 
@@ -627,22 +594,21 @@ extern "C" int jat_trainer_set_latent_loss(jat_trainer* tr, double latent_weight
                                            double consistency_weight, double low_freq_phase_ratio, double strict_cutoff,
                                            double soft_cutoff) {
   if (!tr) return fail(JAT_E_INVALID, "null argument");
-  if (!(low_freq_phase_ratio >= 0 && low_freq_phase_ratio <= 1 && strict_cutoff >= 0 && soft_cutoff >= strict_cutoff &&
-        soft_cutoff <= 1))
-    return fail(JAT_E_INVALID, "band ratios must satisfy 0 <= strict <= soft <= 1 and 0 <= phase ratio <= 1");
-  if (latent_weight != 0.0 && tr->charb_eps > 0.0)
+  const LossSpec l{tr->loss.recon_eps, tr->loss.rw, latent_weight, freq_weight, ms_weight, consistency_weight,
+                   low_freq_phase_ratio, strict_cutoff, soft_cutoff};
+  JCHK(check_band_ratios(l));
+  if (l.has_latent() && l.recon_eps > 0.0)
     return fail(JAT_E_STATE, "the latent perceptual loss is defined on top of the MSE loss only (train_ddp_v3mod2.py:889-896)");
-  tr->lw = latent_weight; tr->fw = freq_weight; tr->mw = ms_weight; tr->cw = consistency_weight;
-  tr->phase_ratio = low_freq_phase_ratio; tr->strict_cut = strict_cutoff; tr->soft_cut = soft_cutoff;
+  tr->loss = l;
   return JAT_OK;
 }
 
 extern "C" int jat_trainer_set_charbonnier(jat_trainer* tr, double eps) {
   if (!tr) return fail(JAT_E_INVALID, "null argument");
   if (!(eps >= 0.0)) return fail(JAT_E_INVALID, "eps must be >= 0 (0 selects the MSE loss)");
-  if (eps > 0.0 && tr->lw != 0.0)
+  if (eps > 0.0 && tr->loss.has_latent())
     return fail(JAT_E_STATE, "the latent perceptual loss is defined on top of the MSE loss only (train_ddp_v3mod2.py:889-896)");
-  tr->charb_eps = eps;
+  tr->loss.recon_eps = eps;
   return JAT_OK;
 }
 
@@ -653,23 +619,18 @@ extern "C" int jat_trainer_set_loss_ex(jat_trainer* tr, double recon_eps, double
                                        double freq_weight, double ms_weight, double consistency_weight,
                                        double low_freq_phase_ratio, double strict_cutoff, double soft_cutoff) {
   if (!tr) return fail(JAT_E_INVALID, "null argument");
-  if (!(recon_eps >= 0.0) || !std::isfinite(recon_eps) || (recon_eps > 0.0 && (float)recon_eps == 0.f))
-    return fail(JAT_E_INVALID, "recon_eps must be finite and >= 0 (0 selects the MSE loss) and, if positive, not below fp32's range");
-  if (!std::isfinite(recon_weight) || !std::isfinite(latent_weight) || !std::isfinite(freq_weight) || !std::isfinite(ms_weight) ||
-      !std::isfinite(consistency_weight))
-    return fail(JAT_E_INVALID, "loss weights must be finite");
-  if (!(low_freq_phase_ratio >= 0 && low_freq_phase_ratio <= 1 && strict_cutoff >= 0 && soft_cutoff >= strict_cutoff &&
-        soft_cutoff <= 1))
-    return fail(JAT_E_INVALID, "band ratios must satisfy 0 <= strict <= soft <= 1 and 0 <= phase ratio <= 1");
-  tr->charb_eps = recon_eps; tr->rw = recon_weight;
-  tr->lw = latent_weight; tr->fw = freq_weight; tr->mw = ms_weight; tr->cw = consistency_weight;
-  tr->phase_ratio = low_freq_phase_ratio; tr->strict_cut = strict_cutoff; tr->soft_cut = soft_cutoff;
+  const LossSpec l{recon_eps, recon_weight, latent_weight, freq_weight, ms_weight, consistency_weight,
+                   low_freq_phase_ratio, strict_cutoff, soft_cutoff};
+  JCHK(check_recon_eps(l));
+  JCHK(check_loss_weights(l));
+  JCHK(check_band_ratios(l));
+  tr->loss = l;
   return JAT_OK;
 }
 
 extern "C" int jat_trainer_loss_terms(jat_trainer* tr, float* out6, void* stream) {
   if (!tr || !out6) return fail(JAT_E_INVALID, "null argument");
-  if (tr->lw == 0.0) return fail(JAT_E_STATE, "the latent perceptual loss is off (jat_trainer_set_latent_loss)");
+  if (!tr->loss.has_latent()) return fail(JAT_E_STATE, "the latent perceptual loss is off (jat_trainer_set_latent_loss)");
   HIPCHK(hipMemcpyAsync(out6, tr->terms, 6 * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return JAT_OK;
 }
@@ -706,7 +667,7 @@ extern "C" int jat_trainer_fwd_bwd_ex(jat_trainer* tr, const float* z_t, const f
                                       float* loss_out, float* x_pred_out, int32_t flags, void* stream) {
   if (!tr || !z_t || !t || !x_cond || !target) return fail(JAT_E_INVALID, "null argument");
   if (flags & ~(JAT_FB_ACCUMULATE | JAT_FB_NO_HOOK)) return fail(JAT_E_INVALID, "unknown flag bits 0x%x", (unsigned)flags);
-  if (tr->lw != 0.0 && tr->cw != 0.0 && !cond_clean)
+  if (tr->loss.has_latent() && tr->loss.cw != 0.0 && !cond_clean)
     return fail(JAT_E_INVALID, "the consistency loss needs the clean condition latent (cond_clean)");
   if (!tr->m->loaded) return fail(JAT_E_STATE, "weights not loaded");
   hipStream_t s = (hipStream_t)stream;
@@ -753,17 +714,16 @@ extern "C" int jat_trainer_swap_ema(jat_trainer* tr, void* stream) {
 }
 
 // per-kernel entry point (unit parity, validation): reconstruction loss and d(loss * loss_scale)/d pred on n elements;
-// eps > 0: Charbonnier (train_ddp_v3m2mod1.py:72-101), eps == 0: MSE (train_ddp_v3m2.py:585); work: 1024 floats
+// eps > 0: Charbonnier (train_ddp_v3m2mod1.py:72-101), eps == 0: MSE (train_ddp_v3m2.py:585); work: 1024 + 2 floats
 extern "C" int jat_k_recon_loss(const float* pred, const float* target, float* dpred, float* loss_out, int64_t n, double eps,
                                 float loss_scale, void* work, size_t work_bytes, void* stream) {
   if (!pred || !target || !dpred || !loss_out || !work || n <= 0 || !(eps >= 0.0)) return fail(JAT_E_INVALID, "bad argument");
-  const size_t need = ((size_t)train_red_blocks() + 2) * 4;
-  if (work_bytes < need) return fail(JAT_E_STATE, "work buffer too small: %zu < %zu bytes", work_bytes, need);
+  const LossSpec l{eps};   // no latent term, weight 1
+  const LossLaunch pl = plan_loss(l, n, 1);
+  if (work_bytes < pl.recon_bytes) return fail(JAT_E_STATE, "work buffer too small: %zu < %zu bytes", work_bytes, pl.recon_bytes);
   hipStream_t s = (hipStream_t)stream;
-  float* part = (float*)work;
-  float* loss2 = part + train_red_blocks();
-  if (eps > 0.0) KCHK(launch_charbonnier_grad(pred, target, dpred, part, loss2, n, (float)eps, loss_scale, 1.0f, s));
-  else KCHK(launch_mse_grad(pred, target, dpred, part, loss2, n, loss_scale, 1.0f, s));
+  float *part = (float*)work, *loss2 = part + train_red_blocks();
+  JCHK(run_loss(l, pl, pred, target, nullptr, nullptr, dpred, part, loss2, n, 1, loss_scale, s));
   HIPCHK(hipMemcpyAsync(loss_out, loss2, 4, hipMemcpyDeviceToDevice, s));
   return JAT_OK;
 }
@@ -778,34 +738,22 @@ extern "C" int jat_k_latent_loss_plan(int32_t T, int32_t* kind, int32_t* a, int3
 
 // body of jat_k_latent_loss / jat_k_latent_loss_ex; `work` holds align_up(T*8, 256) + rows*32 bytes
 static int k_latent_loss(const float* pred, const float* target, const float* lr, float* dpred, float* out6, int32_t rows, int32_t T,
-                         double recon_eps, double recon_weight, double latent_weight, double freq_weight, double ms_weight,
-                         double consistency_weight, double low_freq_phase_ratio, double strict_cutoff, double soft_cutoff,
-                         float loss_scale, void* work, size_t work_bytes, void* stream) {
+                         const LossSpec& l, float loss_scale, void* work, size_t work_bytes, void* stream) {
   if (!pred || !target || !dpred || !out6 || !work || rows <= 0 || T <= 0) return fail(JAT_E_INVALID, "bad argument");
   // what launch_latent_loss would reject, before anything is copied or launched
-  if (!(low_freq_phase_ratio >= 0 && low_freq_phase_ratio <= 1 && strict_cutoff >= 0 && soft_cutoff >= strict_cutoff &&
-        soft_cutoff <= 1))
-    return fail(JAT_E_INVALID, "band ratios must satisfy 0 <= strict <= soft <= 1 and 0 <= phase ratio <= 1");
-  if (plan_latent_loss(T).kind == 0)
-    return fail(JAT_E_INVALID, "T %d is too long for the loss kernels: their LDS image needs %zu bytes", T, plan_latent_loss(T).lds);
-  const size_t need = align_up((size_t)T * sizeof(float2), 256) + (size_t)rows * 8 * 4;
-  if (work_bytes < need) return fail(JAT_E_STATE, "work buffer too small: %zu < %zu bytes", work_bytes, need);
+  JCHK(check_band_ratios(l));
+  LossLaunch pl = plan_loss(l, rows, T);
+  pl.latent = true;   // this entry point IS the latent kernels: latent_weight == 0 leaves their reconstruction term
+  if (pl.path.kind == 0)
+    return fail(JAT_E_INVALID, "T %d is too long for the loss kernels: their LDS image needs %zu bytes", T, pl.path.lds);
+  if (work_bytes < pl.latent_bytes) return fail(JAT_E_STATE, "work buffer too small: %zu < %zu bytes", work_bytes, pl.latent_bytes);
   hipStream_t s = (hipStream_t)stream;
   float2* tw = (float2*)work;
-  float* part = (float*)((char*)work + align_up((size_t)T * sizeof(float2), 256));
-  std::vector<float2> h(T);
-  for (int i = 0; i < T; ++i) {
-    const double th = 2.0 * M_PI * (double)i / (double)T;
-    h[i] = float2{(float)cos(th), (float)sin(th)};
-  }
+  float* part = (float*)((char*)work + pl.tw_bytes);
+  const std::vector<float2> h = make_twiddles(T);
   HIPCHK(hipMemcpyAsync(tw, h.data(), h.size() * sizeof(float2), hipMemcpyHostToDevice, s));
   HIPCHK(hipStreamSynchronize(s));
-  const int F = T / 2 + 1;
-  KCHK(launch_latent_loss(pred, target, lr, tw, dpred, part, out6, rows, T, (float)latent_weight, (float)freq_weight,
-                          (float)ms_weight, (float)consistency_weight, (int)((double)F * low_freq_phase_ratio),
-                          (int)((double)F * strict_cutoff), (int)((double)F * soft_cutoff), (float)recon_eps,
-                          (float)recon_weight, loss_scale, s));
-  return JAT_OK;
+  return run_loss(l, pl, pred, target, lr, tw, dpred, part, out6, rows, T, loss_scale, s);
 }
 
 // per-kernel entry point (unit parity): the v3mod2 loss on [rows, T] tensors
@@ -813,8 +761,8 @@ extern "C" int jat_k_latent_loss(const float* pred, const float* target, const f
                                  int32_t rows, int32_t T, double latent_weight, double freq_weight, double ms_weight,
                                  double consistency_weight, double low_freq_phase_ratio, double strict_cutoff,
                                  double soft_cutoff, float loss_scale, void* work, size_t work_bytes, void* stream) {
-  return k_latent_loss(pred, target, lr, dpred, out6, rows, T, 0.0, 1.0, latent_weight, freq_weight, ms_weight, consistency_weight,
-                       low_freq_phase_ratio, strict_cutoff, soft_cutoff, loss_scale, work, work_bytes, stream);
+  const LossSpec l{0.0, 1.0, latent_weight, freq_weight, ms_weight, consistency_weight, low_freq_phase_ratio, strict_cutoff, soft_cutoff};
+  return k_latent_loss(pred, target, lr, dpred, out6, rows, T, l, loss_scale, work, work_bytes, stream);
 }
 
 // the same with the v3mod3 reconstruction term (train_ddp_v3mod3.py:955-969): recon_weight * recon + latent_weight * (...), recon =
@@ -825,13 +773,11 @@ extern "C" int jat_k_latent_loss_ex(const float* pred, const float* target, cons
                                     double freq_weight, double ms_weight, double consistency_weight,
                                     double low_freq_phase_ratio, double strict_cutoff, double soft_cutoff, float loss_scale,
                                     void* work, size_t work_bytes, void* stream) {
-  if (!(recon_eps >= 0.0) || !std::isfinite(recon_eps) || (recon_eps > 0.0 && (float)recon_eps == 0.f))
-    return fail(JAT_E_INVALID, "recon_eps must be finite and >= 0 (0 selects the MSE loss) and, if positive, not below fp32's range");
-  if (!std::isfinite(recon_weight) || !std::isfinite(latent_weight) || !std::isfinite(freq_weight) || !std::isfinite(ms_weight) ||
-      !std::isfinite(consistency_weight))
-    return fail(JAT_E_INVALID, "loss weights must be finite");
-  return k_latent_loss(pred, target, lr, dpred, out6, rows, T, recon_eps, recon_weight, latent_weight, freq_weight, ms_weight,
-                       consistency_weight, low_freq_phase_ratio, strict_cutoff, soft_cutoff, loss_scale, work, work_bytes, stream);
+  const LossSpec l{recon_eps, recon_weight, latent_weight, freq_weight, ms_weight, consistency_weight,
+                   low_freq_phase_ratio, strict_cutoff, soft_cutoff};
+  JCHK(check_recon_eps(l));
+  JCHK(check_loss_weights(l));
+  return k_latent_loss(pred, target, lr, dpred, out6, rows, T, l, loss_scale, work, work_bytes, stream);
 }
 
 // ---- per-kernel entry points of the training step (unit parity against fp64 references; include/jat_hip.h) ------------

@@ -794,11 +794,18 @@ hipError_t launch_attention_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* 
   return hipGetLastError();
 }
 
-// ---- loss: mse_loss(pred, target) (mean over all elements) and its gradient ------------------------------------------
-// dpred = 2 (pred - target) / n * loss_scale; per-block partial sums of (pred - target)^2, finished in fixed order.
-__global__ void __launch_bounds__(256) mse_grad_kernel(const float* __restrict__ pred, const float* __restrict__ target,
-                                                       float* __restrict__ dpred, float* __restrict__ part, int64_t n,
-                                                       float gscale) {
+// ---- reconstruction loss and its gradient; per-block partial sums of the per-element term, finished in fixed order ------------
+// CHARB = false: mse_loss(pred, target) (mean over all elements), dpred = 2 (pred - target) / n * loss_scale (eps unused); true: Charbonnier,
+// mean(sqrt(d^2 + eps)), d = pred - target (train_ddp_v3m2mod1.py:72-101: eps is ADDED to the square), dpred = d / sqrt(d^2 + eps) / n * loss_scale
+template <bool CHARB>
+__device__ __forceinline__ float recon_term(float e, float eps, float gscale, float& acc) {
+  if constexpr (CHARB) { const float r = sqrtf(e * e + eps); acc += r; return e / r * gscale; }
+  else { acc += e * e; return e * gscale; }
+}
+template <bool CHARB>
+__global__ void __launch_bounds__(256) recon_grad_kernel(const float* __restrict__ pred, const float* __restrict__ target,
+                                                         float* __restrict__ dpred, float* __restrict__ part, int64_t n,
+                                                         float eps, float gscale) {
   __shared__ float red[4];
   float acc = 0.f;
   for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += (int64_t)gridDim.x * 1024) {
@@ -806,10 +813,10 @@ __global__ void __launch_bounds__(256) mse_grad_kernel(const float* __restrict__
       const f32x4_t a = *(const f32x4_t*)(pred + i), t = *(const f32x4_t*)(target + i);
       f32x4_t d;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) { const float e = a[j] - t[j]; acc += e * e; d[j] = e * gscale; }
+      for (int j = 0; j < 4; ++j) d[j] = recon_term<CHARB>(a[j] - t[j], eps, gscale, acc);
       *(f32x4_t*)(dpred + i) = d;
     } else {
-      for (int64_t k = i; k < n; ++k) { const float e = pred[k] - target[k]; acc += e * e; dpred[k] = e * gscale; }
+      for (int64_t k = i; k < n; ++k) dpred[k] = recon_term<CHARB>(pred[k] - target[k], eps, gscale, acc);
     }
   }
   acc = wave_sum_t(acc);
@@ -830,53 +837,14 @@ __global__ void __launch_bounds__(256) finish_sum_kernel(const float* __restrict
   }
   if (threadIdx.x == 0) { out[0] = (float)(red[0] * (double)scale); out[1] = (float)sqrt(red[0] * (double)scale); }
 }
-// ---- loss: Charbonnier, mean(sqrt((pred - target)^2 + eps)) (train_ddp_v3m2mod1.py:72-101: eps is ADDED to the squared
-// difference, not squared) and its gradient  dpred = (pred - target) / sqrt((pred - target)^2 + eps) / n * loss_scale.
-__global__ void __launch_bounds__(256) charbonnier_grad_kernel(const float* __restrict__ pred, const float* __restrict__ target,
-                                                               float* __restrict__ dpred, float* __restrict__ part, int64_t n,
-                                                               float eps, float gscale) {
-  __shared__ float red[4];
-  float acc = 0.f;
-  for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4; i < n; i += (int64_t)gridDim.x * 1024) {
-    if (i + 3 < n) {
-      const f32x4_t a = *(const f32x4_t*)(pred + i), t = *(const f32x4_t*)(target + i);
-      f32x4_t d;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const float e = a[j] - t[j], r = sqrtf(e * e + eps);
-        acc += r;
-        d[j] = e / r * gscale;
-      }
-      *(f32x4_t*)(dpred + i) = d;
-    } else {
-      for (int64_t k = i; k < n; ++k) {
-        const float e = pred[k] - target[k], r = sqrtf(e * e + eps);
-        acc += r;
-        dpred[k] = e / r * gscale;
-      }
-    }
-  }
-  acc = wave_sum_t(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) part[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
-}
 constexpr int RED_BLOCKS = 1024;
 int train_red_blocks() { return RED_BLOCKS; }
-// rw (the v3mod3 trainer's reconstruction_weight) is host arithmetic on both launchers: it multiplies the gradient scale and the
-// scale of the finished sum, so the kernels are the same for every weight and rw = 1 gives the bits it gave without it
-hipError_t launch_mse_grad(const float* pred, const float* target, float* dpred, float* part, float* loss2, int64_t n,
-                           float loss_scale, float rw, hipStream_t s) {
-  hipLaunchKernelGGL(mse_grad_kernel, dim3(RED_BLOCKS), dim3(256), 0, s, pred, target, dpred, part, n,
-                     2.0f * loss_scale / (float)n * rw);
-  hipLaunchKernelGGL(finish_sum_kernel, dim3(1), dim3(256), 0, s, part, RED_BLOCKS, 1.0f / (float)n * rw, loss2);
-  return hipGetLastError();
-}
-
-hipError_t launch_charbonnier_grad(const float* pred, const float* target, float* dpred, float* part, float* loss2, int64_t n,
-                                   float eps, float loss_scale, float rw, hipStream_t s) {
-  hipLaunchKernelGGL(charbonnier_grad_kernel, dim3(RED_BLOCKS), dim3(256), 0, s, pred, target, dpred, part, n, eps,
-                     loss_scale / (float)n * rw);
+// eps > 0: Charbonnier, else MSE (the 2 of its gradient is in the scale).  rw (the v3mod3 trainer's reconstruction_weight) is host arithmetic
+// on the gradient scale and the scale of the finished sum: the kernels are the same for every weight and rw = 1 gives the bits it gave without it
+hipError_t launch_recon_grad(const float* pred, const float* target, float* dpred, float* part, float* loss2, int64_t n, double eps,
+                             float loss_scale, float rw, hipStream_t s) {
+  hipLaunchKernelGGL(eps > 0.0 ? recon_grad_kernel<true> : recon_grad_kernel<false>, dim3(RED_BLOCKS), dim3(256), 0, s, pred, target,
+                     dpred, part, n, (float)eps, (eps > 0.0 ? 1.0f : 2.0f) * loss_scale / (float)n * rw);
   hipLaunchKernelGGL(finish_sum_kernel, dim3(1), dim3(256), 0, s, part, RED_BLOCKS, 1.0f / (float)n * rw, loss2);
   return hipGetLastError();
 }
@@ -1290,7 +1258,7 @@ __device__ __forceinline__ void time_terms(const LatentLossArgs& a, const float*
   float dr = 0.f;            // RECON_GENERAL: d recon / d pred of this sample, before the 1 / n
   if constexpr (RM == RECON_MSE1) {
     acc[0] += e * e;
-  } else if (eps > 0.f) {    // as charbonnier_grad_kernel
+  } else if (eps > 0.f) {    // as recon_grad_kernel<true>
     const float r = sqrtf(e * e + eps);
     acc[0] += r;
     dr = e / r;

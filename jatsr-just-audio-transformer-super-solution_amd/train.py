@@ -17,6 +17,7 @@ from __future__ import annotations
 
 import contextlib
 import ctypes as C
+import dataclasses
 import math
 import warnings
 import weakref
@@ -157,8 +158,34 @@ def _check_norm_batch(x, device):
 LOSSES = ("mse", "charbonnier", "charbonnier_latent")
 
 
-def check_loss_arguments(loss, latent_loss_weight, reconstruction_weight=1.0, charbonnier_eps=1e-6, sub_weights=()):
-    """The argument errors of a loss selection, raised as ValueError before anything touches the GPU (`Trainer`, `fit.run`)."""
+@dataclasses.dataclass(frozen=True)
+class LossConfig:
+    """The training loss as `Trainer` keeps it (built by `check_loss_arguments`): its name, the eps argument as passed, then the
+    nine values of `jat_trainer_set_loss_ex` / `jat_k_latent_loss_ex` in their order (`recon_eps`: 0 selects MSE)."""
+    name: str
+    charbonnier_eps: float
+    recon_eps: float
+    reconstruction_weight: float = 1.0
+    latent_weight: float = 0.0
+    freq_weight: float = 0.5
+    ms_weight: float = 0.5
+    consistency_weight: float = 0.1
+    low_freq_phase_ratio: float = 0.3
+    strict_cutoff: float = 0.30
+    soft_cutoff: float = 0.36
+    has_latent = property(lambda self: self.latent_weight != 0.0)
+
+    def abi(self):
+        return dataclasses.astuple(self)[2:]
+
+    # `work` bytes of jat_k_recon_loss (1024 partial sums + 2 floats) / jat_k_latent_loss_ex (twiddles padded to 256 B + 8 sums per row)
+    recon_work_bytes = staticmethod(lambda: (1024 + 2) * 4)
+    latent_work_bytes = staticmethod(lambda rows, T: (T * 8 + 255) // 256 * 256 + rows * 32)
+
+
+def check_loss_arguments(loss, latent_loss_weight, reconstruction_weight=1.0, charbonnier_eps=1e-6, sub_weights=(), bands=()):
+    """The argument errors of a loss selection, raised as ValueError before anything touches the GPU (`Trainer`, `fit.run`);
+    -> LossConfig.  sub_weights: (freq, ms, consistency), bands: (phase ratio, strict, soft cut-off); empty: the defaults."""
     if loss not in LOSSES:
         raise ValueError(f"loss must be 'mse', 'charbonnier' or 'charbonnier_latent', got {loss!r}")
     weights = (latent_loss_weight, reconstruction_weight) + tuple(sub_weights)
@@ -172,6 +199,10 @@ def check_loss_arguments(loss, latent_loss_weight, reconstruction_weight=1.0, ch
         raise ValueError("loss='charbonnier_latent' needs latent_loss_weight != 0; the Charbonnier loss alone is loss='charbonnier'")
     if loss == "charbonnier_latent" and not (math.isfinite(float(charbonnier_eps)) and float(charbonnier_eps) > 0.0):
         raise ValueError(f"charbonnier_eps must be finite and > 0, got {charbonnier_eps!r}")
+    eps = float(charbonnier_eps)
+    rest = dict(zip(("freq_weight", "ms_weight", "consistency_weight"), map(float, sub_weights)))
+    rest.update(zip(("low_freq_phase_ratio", "strict_cutoff", "soft_cutoff"), map(float, bands)))
+    return LossConfig(loss, eps, eps if loss != "mse" else 0.0, float(reconstruction_weight), float(latent_loss_weight), **rest)
 
 
 class Trainer:
@@ -215,8 +246,9 @@ class Trainer:
         choice (JAT_OPERAND_DTYPE=fp16 loads libjat_hip_fp16.so).  None: whatever the library is."""
         # argument errors first: nothing below (the release of the model's previous trainer, 15-28 GB of new workspace) has
         # happened when a mistyped flag is reported
-        check_loss_arguments(loss, latent_loss_weight, reconstruction_weight, charbonnier_eps,
-                             (freq_loss_weight, ms_loss_weight, consistency_weight))
+        self.loss_config = check_loss_arguments(loss, latent_loss_weight, reconstruction_weight, charbonnier_eps,
+                                                (freq_loss_weight, ms_loss_weight, consistency_weight),
+                                                (low_freq_phase_ratio, strict_cutoff, soft_cutoff))
         if ema_decay is not None and not 0.0 <= float(ema_decay) < 1.0:
             raise ValueError(f"ema_decay must be in [0, 1), got {ema_decay!r}")
         if int(grad_accum_steps) != grad_accum_steps or int(grad_accum_steps) < 1:
@@ -295,19 +327,7 @@ class Trainer:
         self.mask_seed = 0x9E3779B97F4A7C15 if seed is None else int(seed)
         self.set_regularisers([getattr(b, "dropout_rate", 0.0) for b in model.blocks],
                               [getattr(b, "drop_path_rate", 0.0) for b in model.blocks])
-        self.latent_loss = dict(latent_weight=float(latent_loss_weight), freq_weight=float(freq_loss_weight),
-                                ms_weight=float(ms_loss_weight), consistency_weight=float(consistency_weight),
-                                low_freq_phase_ratio=float(low_freq_phase_ratio), strict_cutoff=float(strict_cutoff),
-                                soft_cutoff=float(soft_cutoff))
-        self.loss, self.charbonnier_eps = loss, float(charbonnier_eps)
-        self.reconstruction_weight = float(reconstruction_weight)
-        self.recon_eps = self.charbonnier_eps if loss != "mse" else 0.0      # what the library is given: 0 selects MSE
-        if loss == "charbonnier_latent" or self.reconstruction_weight != 1.0:
-            L.check(L.lib().jat_trainer_set_loss_ex(self.ptr, self.recon_eps, self.reconstruction_weight,
-                                                    *self.latent_loss.values()))
-        else:
-            L.check(L.lib().jat_trainer_set_latent_loss(self.ptr, *self.latent_loss.values()))
-            L.check(L.lib().jat_trainer_set_charbonnier(self.ptr, self.recon_eps))
+        L.check(L.lib().jat_trainer_set_loss_ex(self.ptr, *self.loss_config.abi()))
         self._terms = torch.zeros(6, dtype=torch.float32, device=dev)
         # moving average of the weights: taken after the broadcast above, so every rank starts from the same copy and, as all
         # ranks apply the same all-reduced step, stays equal without a collective of its own
@@ -324,6 +344,13 @@ class Trainer:
         self._comm_stream = torch.cuda.Stream(device=dev)
         self._hook = L.GRAD_HOOK(self._on_grads_ready)          # keep the ctypes thunk alive
         L.check(L.lib().jat_trainer_set_grad_hook(self.ptr, C.cast(self._hook, C.c_void_p), None))
+
+    # the loss under the names it had as separate attributes; latent_loss: the latent term's seven values by name, in ABI order
+    loss = property(lambda self: self.loss_config.name)
+    charbonnier_eps = property(lambda self: self.loss_config.charbonnier_eps)
+    reconstruction_weight = property(lambda self: self.loss_config.reconstruction_weight)
+    recon_eps = property(lambda self: self.loss_config.recon_eps)
+    latent_loss = property(lambda self: dict(list(dataclasses.asdict(self.loss_config).items())[4:]))
 
     def _check_attached(self):
         if self._detached:
@@ -367,7 +394,7 @@ class Trainer:
         under its own name.  With grad_accum_steps > 1: the means over the step's
         micro-batches (the library keeps the sums; between two micro-batches, the mean over those run so far)."""
         n = self._micro if self._micro > 0 else self._last_micro
-        if self.latent_loss["latent_weight"] == 0.0:
+        if not self.loss_config.has_latent:
             return dict(total=float(self._scal[0]) / n)
         L.check(L.lib().jat_trainer_loss_terms(self.ptr, L.ptr(self._terms), L.stream_ptr()))
         terms = dict(zip(("total", "mse", "freq", "ms", "consistency", "latent"), (v / n for v in self._terms.tolist())))
@@ -578,7 +605,7 @@ class Trainer:
         from .sampler import channel_affine
         acc = torch.zeros(8, dtype=torch.float64, device=self.device)   # loss, steps, mse, freq, ms, cons, latent, -
         losses = []
-        ll = self.latent_loss
+        loss = self.loss_config
         out6 = torch.zeros(6, dtype=torch.float32, device=self.device)
         for i, (hr, lr) in enumerate(batches):
             if normalised:
@@ -594,24 +621,18 @@ class Trainer:
             pred = self.model(z_t.contiguous(), tt.contiguous(), lr_norm)
             rows = Bv * Cv
             scratch = torch.empty_like(pred)
-            if self.loss == "charbonnier":      # train_ddp_v3m2mod1.py:817-819: validation uses the training loss
-                work = torch.empty(4104, dtype=torch.uint8, device=self.device)
+            if loss.name == "charbonnier":      # train_ddp_v3m2mod1.py:817-819: validation uses the training loss
+                work = torch.empty(loss.recon_work_bytes(), dtype=torch.uint8, device=self.device)
                 L.check(L.lib().jat_k_recon_loss(L.ptr(pred), L.ptr(hr_norm), L.ptr(scratch), L.ptr(out6), pred.numel(),
-                                                 self.charbonnier_eps, 1.0, L.ptr(work), work.numel(), L.stream_ptr()))
-                val = out6[0].double() * self.reconstruction_weight
+                                                 loss.charbonnier_eps, 1.0, L.ptr(work), work.numel(), L.stream_ptr()))
+                val = out6[0].double() * loss.reconstruction_weight
                 acc[0] += val; acc[1] += 1
                 losses.append(float(val))
                 continue
-            work = torch.empty((Tv * 8 + 255) // 256 * 256 + rows * 32, dtype=torch.uint8, device=self.device)
-            weights = (ll["latent_weight"], ll["freq_weight"], ll["ms_weight"], ll["consistency_weight"],
-                       ll["low_freq_phase_ratio"], ll["strict_cutoff"], ll["soft_cutoff"])
-            if self.recon_eps == 0.0 and self.reconstruction_weight == 1.0:
-                L.check(L.lib().jat_k_latent_loss(L.ptr(pred), L.ptr(hr_norm), L.ptr(lr_norm), L.ptr(scratch), L.ptr(out6), rows, Tv,
-                                                  *weights, 1.0, L.ptr(work), work.numel(), L.stream_ptr()))
-            else:                               # train_ddp_v3mod3.py:1138-1159: the training loss, Charbonnier and weights included
-                L.check(L.lib().jat_k_latent_loss_ex(L.ptr(pred), L.ptr(hr_norm), L.ptr(lr_norm), L.ptr(scratch), L.ptr(out6), rows,
-                                                     Tv, self.recon_eps, self.reconstruction_weight, *weights, 1.0, L.ptr(work),
-                                                     work.numel(), L.stream_ptr()))
+            # train_ddp_v3mod3.py:1138-1159: the training loss, Charbonnier and weights included ((0, 1): the v3mod2 loss's kernels)
+            work = torch.empty(loss.latent_work_bytes(rows, Tv), dtype=torch.uint8, device=self.device)
+            L.check(L.lib().jat_k_latent_loss_ex(L.ptr(pred), L.ptr(hr_norm), L.ptr(lr_norm), L.ptr(scratch), L.ptr(out6), rows, Tv,
+                                                 *loss.abi(), 1.0, L.ptr(work), work.numel(), L.stream_ptr()))
             o = out6.double()
             acc[0] += o[0]; acc[1] += 1; acc[2:7] += o[1:6]
             losses.append(float(o[0]))
@@ -623,7 +644,7 @@ class Trainer:
             metrics = dict(zip(("mse_loss", "freq_loss", "ms_loss", "consistency_loss", "total_latent_loss"),
                                (acc[2:7] / steps).tolist()))
         std = float(torch.tensor(losses).std()) if len(losses) > 1 else 0.0
-        if ll["latent_weight"] == 0.0:
+        if not loss.has_latent:
             metrics = {}
         return avg, std, metrics
 

@@ -630,6 +630,57 @@ def test_adamw_skips_a_non_finite_step(bad):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# reconstruction loss (MSE / Charbonnier) and its gradient: recon_grad_kernel<CHARB> through jat_k_recon_loss
+# ---------------------------------------------------------------------------------------------------------------------
+RECON_SWEEP = 1024 * 256 * 4                     # elements one sweep of the grid covers: 1024 blocks x 256 threads x 4
+RECON_SIZES = (1, 7, 4099, RECON_SWEEP + 5)      # the scalar tail alone; one vector + tail; many vectors + a tail of 3; a second
+#                                                  sweep with one vector and a one-element tail
+
+
+@functools.lru_cache(maxsize=1)
+def recon_inputs():
+    """(pred, target) fp32 of the largest size, every size uses a prefix: every third target sits at pred + 2e-3 * noise
+    (|d| ~ sqrt(eps)), every ninth element from index 4 on has pred == target (index 0 keeps a non-zero difference)."""
+    import jatsr_amd.recipe as recipe
+    n = max(RECON_SIZES)
+    pred, target, near = (recipe.gaussian("recon_" + k, (n,), 900 + i) for i, k in enumerate(("pred", "target", "near")))
+    target[::3] = pred[::3] + np.float32(2e-3) * near[::3]
+    target[4::9] = pred[4::9]
+    return pred, target
+
+
+@pytest.mark.parametrize("eps", [0.0, 1e-6])
+@pytest.mark.parametrize("n", RECON_SIZES)
+def test_recon_loss_vector_body_tail_and_second_sweep(n, eps):
+    """jat_k_recon_loss against fp64 numpy where the merged kernel changes form, at loss_scale 1 and 1024 (it scales the gradient
+    only).  Gates of test_charbonnier_kernel_vs_reference_function: loss 2e-6 relative, dpred rel-L2 2e-6, exact 0 where
+    pred == target."""
+    pred, target = (x[:n] for x in recon_inputs())
+    d = pred.astype(np.float64) - target.astype(np.float64)
+    if eps > 0:
+        r = np.sqrt(d * d + eps)
+        loss_ref, g_ref = float(r.mean()), d / r / n
+    else:
+        loss_ref, g_ref = float((d * d).mean()), 2 * d / n
+    assert loss_ref > 0
+    p_d, t_d = torch.from_numpy(pred.copy()).to(dev()), torch.from_numpy(target.copy()).to(dev())
+    for scale in (1.0, 1024.0):
+        gb, g = guarded((n,))
+        ob, out = guarded((1,))
+        wk = work((1024 + 2) * 4)
+        call(L.lib().jat_k_recon_loss, L.ptr(p_d), L.ptr(t_d), L.ptr(g), L.ptr(out), n, eps, scale, L.ptr(wk), wk.numel() * 4,
+             L.stream_ptr())
+        got = g.cpu().numpy().astype(np.float64) / scale
+        loss_err = abs(float(out[0]) - loss_ref) / loss_ref
+        g_err = float(np.linalg.norm(got - g_ref) / np.linalg.norm(g_ref))
+        print(f"n {n} eps {eps} scale {scale}: loss rel err {loss_err:.3e}, dpred rel-L2 {g_err:.3e}")
+        assert loss_err <= 2e-6
+        assert g_err <= 2e-6
+        assert np.all(got[4::9] == 0.0) and np.isfinite(got).all()
+        assert guards_intact(gb) and guards_intact(ob)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # small-batch Linear backward (adaLN modulation and t_embedder)
 # ---------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("B,N,K,silu,ldy_pad,with_db", [

@@ -172,6 +172,31 @@ def test_trainer_argument_errors_come_before_any_gpu_need():
         Trainer(None, 1, 4, loss="charbonier")
 
 
+def test_loss_config_carries_the_nine_values_in_abi_order():
+    """The four loss selections `Trainer` accepts -> the argument list of jat_trainer_set_loss_ex / jat_k_latent_loss_ex (recon_eps,
+    recon_weight, latent_weight, freq, ms, consistency, phase ratio, strict, soft), and the names the loss had as attributes."""
+    from jatsr_amd.train import LossConfig, check_loss_arguments
+    sub, bands = (0.25, 0.75, 0.2), (0.4, 0.25, 0.5)
+    for loss, lw, rw, eps, recon_eps in (("mse", 0.0, 1.0, 1e-6, 0.0), ("mse", 0.3, 0.5, 1e-3, 0.0),
+                                         ("charbonnier", 0.0, 2.0, 1e-3, 1e-3), ("charbonnier_latent", 0.3, 0.5, 1e-4, 1e-4)):
+        c = check_loss_arguments(loss, lw, rw, eps, sub, bands)
+        assert isinstance(c, LossConfig) and c.abi() == (recon_eps, rw, lw) + sub + bands, loss
+        assert (c.name, c.charbonnier_eps, c.recon_eps, c.reconstruction_weight, c.has_latent) == (loss, eps, recon_eps, rw, lw != 0.0)
+        assert all(type(v) is float for v in c.abi())
+    # what is left out keeps the defaults of Trainer's signature and of the library's LossSpec
+    assert check_loss_arguments("mse", 0).abi() == (0.0, 1.0, 0.0, 0.5, 0.5, 0.1, 0.3, 0.30, 0.36)
+    assert len(L.SIGNATURES["jat_trainer_set_loss_ex"][1]) == 1 + len(check_loss_arguments("mse", 0).abi())
+    # the work buffers of the two validation calls, as the entry points size them
+    assert LossConfig.recon_work_bytes() == 4104
+    assert LossConfig.latent_work_bytes(6, 35) == 512 + 192 and LossConfig.latent_work_bytes(1, 32) == 256 + 32
+    # and the rejected selections raise what they raised
+    for args, match in ((("charbonier", 0.0), "loss must be"), (("charbonnier", 0.3), "latent"), (("charbonnier_latent", 0.0), "'charbonnier'"),
+                        (("charbonnier_latent", 0.3, 1.0, -1e-6), "charbonnier_eps"), (("mse", 0.0, float("nan")), "finite"),
+                        (("mse", 0.3, 1.0, 1e-6, (0.5, float("inf"), 0.1)), "finite")):
+        with pytest.raises(ValueError, match=match):
+            check_loss_arguments(*args)
+
+
 def test_new_symbols_are_declared_and_bound():
     header = open(os.path.join(ROOT, "include", "jat_hip.h")).read()
     for name, doubles in (("jat_trainer_set_loss_ex", 9), ("jat_k_latent_loss_ex", 9)):
