@@ -722,6 +722,30 @@ int jat_bank_search(jat_bank* bank, const float* x, const float* mean, const flo
 int jat_bank_blend(jat_bank* bank, const float* x, const int32_t* idx, const float* value_mean, const float* value_std,
                    float rate, float* y, int32_t B, int32_t T, void* stream);
 
+/* ---- top-k latent retrieval: the k nearest rows, inverse-square blend ------------------------------- */
+#define JAT_BANK_MAX_K 8
+/* Device bytes jat_bank_search_topk needs for n_queries queries and k in 1..JAT_BANK_MAX_K (k = 1: what
+ * jat_bank_search_workspace_bytes returns). */
+int jat_bank_topk_workspace_bytes(const jat_bank* bank, int64_t n_queries, int32_t k, size_t* bytes);
+/* The search above for the k nearest key rows.  With the rows i < size ordered by (d(q, i), i), d exactly as in
+ * jat_bank_search, query n = b T + t gets the first k of them in that order:
+ *   idx[n, j] the row, dist2[n, j] = max(d, 0) (dist2 may be NULL);  size < k: the places j >= size hold idx -1, dist2 +inf.
+ * The first j columns of a result for k are the result for j, bit for bit; k = 1 is jat_bank_search.  The same
+ * independence of B, of the query's neighbours, of the split of the key range and of the run.  work: 8-byte aligned, at
+ * least the bytes the query function above returns for B T queries and this k. */
+int jat_bank_search_topk(jat_bank* bank, const float* x, const float* mean, const float* std, int32_t B, int32_t T, int32_t k,
+                         int32_t* idx, float* dist2, void* work, size_t work_bytes, void* stream);
+/* idx int32 / dist2 fp32 [B T, k] as jat_bank_search_topk writes them (any caller-made lists of that form do).  Per frame,
+ * in fp32:  dt_j = max(dist2_j, dist2_floor),  u_j = (dt_0 / dt_j)^2 where idx_j >= 0 and 0 elsewhere,  w_j = u_j / sum_j u_j
+ * (sum over ascending j),  v = sum_j w_j float(values[idx_j, c]) (an fmaf chain over ascending j), then v de-normalised and
+ * mixed exactly as in jat_bank_blend:  y = (1 - rate) x + rate (v value_std + value_mean).  Where every dist2_j exceeds the
+ * floor, w is square(1 / dist2) normalised to sum 1.  An index >= size is clamped into the bank, a negative one carries
+ * weight 0 and is not read; a frame without any usable entry gets v = 0.  k = 1 computes jat_bank_blend bit for bit.
+ * dist2_floor > 0 and finite (1e-6 suits squared distances of normalised latents); rate in [0, 1]; y may be x. */
+int jat_bank_blend_topk(jat_bank* bank, const float* x, const int32_t* idx, const float* dist2, int32_t k,
+                        const float* value_mean, const float* value_std, float rate, float dist2_floor, float* y, int32_t B,
+                        int32_t T, void* stream);
+
 /* ---- pitch tracking (YIN) and F0-preservation counts ------------------------------------------------ */
 /* Steps 1-5 of de Cheveigne & Kawahara (2002) on mono fp32 audio x[B, L], framed as the STFT above frames it:
  * W = frame_length / 2, frames = 1 + L / hop_length, frame f = x_pad[f hop : f hop + frame_length] with frame_length / 2

@@ -181,6 +181,9 @@ SIGNATURES = {
     "jat_bank_search_workspace_bytes": (C.c_int, [_VP, _I64, C.POINTER(_SZ)]),
     "jat_bank_search": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _VP, _VP, _VP, _SZ, _VP]),
     "jat_bank_blend": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _F32, _VP, _I32, _I32, _VP]),
+    "jat_bank_topk_workspace_bytes": (C.c_int, [_VP, _I64, _I32, C.POINTER(_SZ)]),
+    "jat_bank_search_topk": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _VP, _VP, _VP, _SZ, _VP]),
+    "jat_bank_blend_topk": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _VP, _VP, _F32, _F32, _VP, _I32, _I32, _VP]),
     "jat_yin_periods": (C.c_int, [_I32, C.c_double, C.c_double, _I32, C.POINTER(_I32), C.POINTER(_I32)]),
     "jat_yin": (C.c_int, [C.POINTER(JatYinParams), _VP, _I32, _I64] + [_VP] * 7),
     "jat_f0_compare": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, C.c_double, _VP, _VP]),
@@ -199,6 +202,7 @@ MONITOR_WORK_BYTES = 49152   # JAT_MONITOR_WORK_BYTES
 LTAS_SLICES = 64             # JAT_LTAS_SLICES
 BANK_SLAB = 4096             # JAT_BANK_SLAB
 BANK_KEYS, BANK_VALUES = 0, 1
+BANK_MAX_K = 8               # JAT_BANK_MAX_K
 
 GRAD_HOOK = C.CFUNCTYPE(None, C.c_int64, C.c_int64, C.c_void_p)   # jat_trainer_set_grad_hook callback
 

@@ -13,7 +13,7 @@ struct jat_bank {
 namespace {
 
 constexpr int64_t kMax31 = 0x7fffffff;
-static_assert(JAT_BANK_SLAB == RT_SLAB, "header and kernel disagree");
+static_assert(JAT_BANK_SLAB == RT_SLAB && JAT_BANK_MAX_K == RT_MAX_K, "header and kernel disagree");
 
 int check_bank(const char* who, const jat_bank* b) {
   if (!b) return fail(JAT_E_INVALID, "%s: null bank", who);
@@ -31,6 +31,16 @@ int check_queries(const char* who, const jat_bank* b, int32_t B, int32_t T) {
 size_t search_bytes(const jat_bank* b, int64_t nq) {
   const size_t slabs = ((size_t)b->capacity + RT_SLAB - 1) / RT_SLAB;
   return align_up(slabs * (size_t)nq * sizeof(RtPartial), 256);
+}
+
+size_t topk_bytes(const jat_bank* b, int64_t nq, int k) {
+  const size_t slabs = ((size_t)b->capacity + RT_SLAB - 1) / RT_SLAB;
+  return align_up(slabs * (size_t)nq * rt_list_length(k) * sizeof(RtPartial), 256);
+}
+
+int check_k(const char* who, int32_t k) {
+  if (k < 1 || k > JAT_BANK_MAX_K) return fail(JAT_E_INVALID, "%s: k %d outside 1..%d", who, k, JAT_BANK_MAX_K);
+  return JAT_OK;
 }
 
 void release(jat_bank* b) {
@@ -169,6 +179,52 @@ int jat_bank_blend(jat_bank* bank, const float* x, const int32_t* idx, const flo
   if (bank->size < 1) return fail(JAT_E_STATE, "jat_bank_blend: the bank is empty");
   KCHK(bank_blend_launch(bank->values, bank->size, bank->channels, x, idx, value_mean, value_std, rate, y, B, T,
                          (hipStream_t)stream));
+  return JAT_OK;
+}
+
+int jat_bank_topk_workspace_bytes(const jat_bank* bank, int64_t n_queries, int32_t k, size_t* bytes) {
+  JCHK(check_bank("jat_bank_topk_workspace_bytes", bank));
+  if (!bytes) return fail(JAT_E_INVALID, "jat_bank_topk_workspace_bytes: null output pointer");
+  if (n_queries < 1 || n_queries > kMax31 / 2)
+    return fail(JAT_E_INVALID, "jat_bank_topk_workspace_bytes: %lld queries outside 1..2^30", (long long)n_queries);
+  JCHK(check_k("jat_bank_topk_workspace_bytes", k));
+  *bytes = topk_bytes(bank, n_queries, k);
+  return JAT_OK;
+}
+
+int jat_bank_search_topk(jat_bank* bank, const float* x, const float* mean, const float* std, int32_t B, int32_t T, int32_t k,
+                         int32_t* idx, float* dist2, void* work, size_t work_bytes, void* stream) {
+  JCHK(check_bank("jat_bank_search_topk", bank));
+  JCHK(check_queries("jat_bank_search_topk", bank, B, T));
+  JCHK(check_k("jat_bank_search_topk", k));
+  if (!x || !idx || !work) return fail(JAT_E_INVALID, "jat_bank_search_topk: null buffer");
+  if ((mean != nullptr) != (std != nullptr))
+    return fail(JAT_E_INVALID, "jat_bank_search_topk: mean and std are both given or both null");
+  if ((uintptr_t)work & 7) return fail(JAT_E_INVALID, "jat_bank_search_topk: the workspace must be 8-byte aligned");
+  const size_t need = topk_bytes(bank, (int64_t)B * T, k);
+  if (work_bytes < need) return fail(JAT_E_INVALID, "jat_bank_search_topk: workspace %zu < %zu bytes", work_bytes, need);
+  if (bank->size < 1) return fail(JAT_E_STATE, "jat_bank_search_topk: the bank is empty");
+  KCHK(bank_search_topk_launch(bank->keys, bank->norms, bank->size, bank->channels, x, mean, std, B, T, k, idx, dist2,
+                               (RtPartial*)work, (hipStream_t)stream));
+  return JAT_OK;
+}
+
+int jat_bank_blend_topk(jat_bank* bank, const float* x, const int32_t* idx, const float* dist2, int32_t k,
+                        const float* value_mean, const float* value_std, float rate, float dist2_floor, float* y, int32_t B,
+                        int32_t T, void* stream) {
+  JCHK(check_bank("jat_bank_blend_topk", bank));
+  JCHK(check_queries("jat_bank_blend_topk", bank, B, T));
+  JCHK(check_k("jat_bank_blend_topk", k));
+  if (!x || !idx || !dist2 || !y) return fail(JAT_E_INVALID, "jat_bank_blend_topk: null buffer");
+  if ((value_mean != nullptr) != (value_std != nullptr))
+    return fail(JAT_E_INVALID, "jat_bank_blend_topk: value_mean and value_std are both given or both null");
+  if (!(rate >= 0.f && rate <= 1.f))
+    return fail(JAT_E_INVALID, "jat_bank_blend_topk: index rate %g outside [0, 1]", (double)rate);
+  if (!(dist2_floor > 0.f) || dist2_floor == __builtin_inff())
+    return fail(JAT_E_INVALID, "jat_bank_blend_topk: dist2_floor %g must be positive and finite", (double)dist2_floor);
+  if (bank->size < 1) return fail(JAT_E_STATE, "jat_bank_blend_topk: the bank is empty");
+  KCHK(bank_blend_topk_launch(bank->values, bank->size, bank->channels, x, idx, dist2, k, dist2_floor, value_mean, value_std,
+                              rate, y, B, T, (hipStream_t)stream));
   return JAT_OK;
 }
 

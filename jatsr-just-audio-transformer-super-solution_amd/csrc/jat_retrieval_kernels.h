@@ -9,13 +9,16 @@ constexpr int RT_QTILE = 32;         // queries per search workgroup, resident i
 constexpr int RT_KTILE = 128;        // key rows per step of the scan: one 32-row MFMA tile per wave
 constexpr int RT_KCHUNK = 64;        // channels of the key tile staged in LDS at once
 constexpr int RT_MIN_C = 32, RT_MAX_C = 1024;
+constexpr int RT_MAX_K = 8;          // nearest rows per query at most (JAT_BANK_MAX_K)
 
-struct RtPartial {   // one per (slab, query)
+struct RtPartial {   // one per (slab, query), or the list length of them for a top-k search
   float d;
   int32_t idx;
 };
 
 inline bool rt_channels_ok(int C) { return C >= RT_MIN_C && C <= RT_MAX_C && C % 32 == 0; }
+// the list length a request for the k nearest rows runs with: the next of 1, 2, 4, 8
+inline int rt_list_length(int k) { return k <= 1 ? 1 : k <= 2 ? 2 : k <= 4 ? 4 : 8; }
 
 // rows[row0 + i, c] = fp16((float(src[c, first + i * stride]) - mean[c]) / std[c]) for i < count, and with src2 the same into
 // rows2 with (mean2, std2).  src / src2: [C, len], fp16 or fp32.  The caller has checked first + (count - 1) * stride < len.
@@ -28,6 +31,18 @@ hipError_t bank_norms_launch(const uint16_t* rows, float* norms, int64_t row0, i
 // used as it is.  part: ceil(size / RT_SLAB) * B * T entries.
 hipError_t bank_search_launch(const uint16_t* keys, const float* norms, int size, int C, const float* x, const float* mean,
                               const float* std, int B, int T, int32_t* idx, float* dist2, RtPartial* part, hipStream_t s);
+// The k nearest key rows of every query in ascending (d, index): idx int32 [B * T, k], dist2 fp32 [B * T, k] (may be null),
+// unused places (size < k) idx -1 and dist2 +inf.  1 <= k <= RT_MAX_K; k = 1 is bank_search_launch.  part:
+// ceil(size / RT_SLAB) * B * T * rt_list_length(k) entries.
+hipError_t bank_search_topk_launch(const uint16_t* keys, const float* norms, int size, int C, const float* x,
+                                   const float* mean, const float* std, int B, int T, int k, int32_t* idx, float* dist2,
+                                   RtPartial* part, hipStream_t s);
+// y = (1 - rate) x + rate v with v = sum_j w_j float(values[idx[b, t, j], c]) (* std[c] + mean[c] when given),
+// w_j = u_j / sum_j u_j, u_j = (max(dist2_0, floor) / max(dist2_j, floor))^2 where idx_j >= 0 and 0 elsewhere; an index
+// >= size is clamped, a negative one is not read
+hipError_t bank_blend_topk_launch(const uint16_t* values, int size, int C, const float* x, const int32_t* idx,
+                                  const float* dist2, int k, float floor, const float* mean, const float* std, float rate,
+                                  float* y, int B, int T, hipStream_t s);
 // y[b, c, t] = (1 - rate) x[b, c, t] + rate v,  v = float(values[idx[b, t], c]) (* std[c] + mean[c] when given); an index
 // outside [0, size) is clamped into it
 hipError_t bank_blend_launch(const uint16_t* values, int size, int C, const float* x, const int32_t* idx, const float* mean,

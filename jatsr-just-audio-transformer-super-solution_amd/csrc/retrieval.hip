@@ -15,6 +15,11 @@
 // depend on the slab split, on B or on the query's place in its tile.  One partial per (slab, query); bank_reduce_kernel
 // takes them in slab order.  No atomics.
 // Edges: key rows >= size are neither read nor compared; queries >= B * T are zeros and are not written.
+//
+// Top-k.  The same scan with a list length KP of 2, 4 or 8 in place of the single (d, idx): a lane keeps its KP best pairs
+// sorted in registers, the eight lists of a query are merged by (d, idx) in LDS at the end of the slab (KP partials per
+// (slab, query)), and bank_reduce_topk_kernel merges the slabs' lists in slab order.  A request for k runs the next KP >= k
+// and writes the first k entries.  bank_blend_topk_kernel mixes the k value rows with inverse-square-distance weights.
 #include "jat_retrieval_kernels.h"
 
 #include <type_traits>
@@ -84,7 +89,23 @@ __global__ __launch_bounds__(RT_THREADS) void bank_norms_kernel(const uint16_t* 
 // ---- search ---------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ bool better(float d, int i, float bd, int bi) { return d < bd || (d == bd && i < bi); }
 
-template <bool NORM>
+// The sorted list of one lane, of one query of a slab, of one query: KP (d, idx) pairs ascending, unused places (+inf, -1).
+// `before(d, i, entry)` says whether the candidate goes in front of an entry; the candidate lands behind every entry it is
+// not in front of.  Every index is a compile-time constant, so the list stays in registers.
+template <int KP, typename Before>
+__device__ __forceinline__ void list_insert(float (&ld)[KP], int (&li)[KP], float d, int i, Before before) {
+#pragma unroll
+  for (int j = KP - 1; j >= 1; --j) {
+    const bool here = before(d, i, ld[j], li[j]), above = before(d, i, ld[j - 1], li[j - 1]);
+    ld[j] = here ? (above ? ld[j - 1] : d) : ld[j];
+    li[j] = here ? (above ? li[j - 1] : i) : li[j];
+  }
+  if (before(d, i, ld[0], li[0])) ld[0] = d, li[0] = i;
+}
+
+// KP = 1 is the arg-min search (one RtPartial per (slab, query), bank_reduce_kernel); KP = 2, 4, 8 keep the KP best per lane
+// and write KP partials per (slab, query) for bank_reduce_topk_kernel.  The scan is the same text for all of them.
+template <bool NORM, int KP>
 __global__ __launch_bounds__(RT_THREADS) void bank_search_kernel(const uint16_t* __restrict__ keys,
                                                                  const float* __restrict__ norms, int size, int C,
                                                                  const float* __restrict__ x, const float* __restrict__ mean,
@@ -161,8 +182,12 @@ __global__ __launch_bounds__(RT_THREADS) void bank_search_kernel(const uint16_t*
     if (++f_ch == nch) f_ch = 0, ++f_tile;
   };
 
-  float best_d = __builtin_inff();
+  float best_d = __builtin_inff();                         // KP == 1
   int best_i = k_begin;
+  float ld[KP];                                            // KP > 1: rows ascend per lane, so a strict < keeps the lower
+  int li[KP];                                              // index in front on equal d
+#pragma unroll
+  for (int j = 0; j < KP; ++j) ld[j] = __builtin_inff(), li[j] = -1;
   int tile = 0, ch = 0;                                    // the chunk in LDS
   rt_f32x16 acc;
 #pragma unroll
@@ -208,9 +233,14 @@ __global__ __launch_bounds__(RT_THREADS) void bank_search_kernel(const uint16_t*
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const float d = (qv + kv[r]) - 2.f * acc[4 * g + r];
-            if (k0 + r < k_end && d < best_d) {
-              best_d = d;
-              best_i = k0 + r;
+            if constexpr (KP == 1) {
+              if (k0 + r < k_end && d < best_d) {
+                best_d = d;
+                best_i = k0 + r;
+              }
+            } else {
+              if (k0 + r < k_end && d < ld[KP - 1])
+                list_insert<KP>(ld, li, d, k0 + r, [](float d, int, float ed, int) { return d < ed; });
             }
           }
         }
@@ -222,18 +252,45 @@ __global__ __launch_bounds__(RT_THREADS) void bank_search_kernel(const uint16_t*
   }
 
   __syncthreads();
-  RtPartial* cand = (RtPartial*)sK;                        // [8][RT_QTILE]
-  cand[(wave * 2 + half) * RT_QTILE + col] = RtPartial{best_d, best_i};
-  __syncthreads();
-  if (tid < RT_QTILE) {
-    RtPartial b = cand[tid];
+  RtPartial* cand = (RtPartial*)sK;                        // [8][KP][RT_QTILE]
+  if constexpr (KP == 1) {
+    cand[(wave * 2 + half) * RT_QTILE + col] = RtPartial{best_d, best_i};
+    __syncthreads();
+    if (tid < RT_QTILE) {
+      RtPartial b = cand[tid];
 #pragma unroll
-    for (int k = 1; k < 8; ++k) {
-      const RtPartial c = cand[k * RT_QTILE + tid];
-      if (better(c.d, c.idx, b.d, b.idx)) b = c;
+      for (int k = 1; k < 8; ++k) {
+        const RtPartial c = cand[k * RT_QTILE + tid];
+        if (better(c.d, c.idx, b.d, b.idx)) b = c;
+      }
+      const int64_t g = (int64_t)blockIdx.x * RT_QTILE + tid;
+      if (g < nq) part[(int64_t)blockIdx.y * nq + g] = b;
     }
-    const int64_t g = (int64_t)blockIdx.x * RT_QTILE + tid;
-    if (g < nq) part[(int64_t)blockIdx.y * nq + g] = b;
+  } else {
+    // the eight lists of a query (4 waves x 2 halves), each ascending in (d, idx), merged by (d, idx) by one thread
+#pragma unroll
+    for (int j = 0; j < KP; ++j) cand[((wave * 2 + half) * KP + j) * RT_QTILE + col] = RtPartial{ld[j], li[j]};
+    __syncthreads();
+    if (tid < RT_QTILE) {
+#pragma unroll
+      for (int j = 0; j < KP; ++j) {
+        const RtPartial c = cand[j * RT_QTILE + tid];
+        ld[j] = c.d, li[j] = c.idx;
+      }
+      for (int l = 1; l < 8; ++l) {
+#pragma unroll
+        for (int j = 0; j < KP; ++j) {
+          const RtPartial c = cand[(l * KP + j) * RT_QTILE + tid];
+          if (!better(c.d, c.idx, ld[KP - 1], li[KP - 1])) break;   // the list ascends: nothing behind c enters either
+          list_insert<KP>(ld, li, c.d, c.idx, [](float d, int i, float ed, int ei) { return better(d, i, ed, ei); });
+        }
+      }
+      const int64_t g = (int64_t)blockIdx.x * RT_QTILE + tid;
+      if (g < nq) {
+#pragma unroll
+        for (int j = 0; j < KP; ++j) part[((int64_t)blockIdx.y * nq + g) * KP + j] = RtPartial{ld[j], li[j]};
+      }
+    }
   }
 }
 
@@ -248,6 +305,38 @@ __global__ __launch_bounds__(RT_THREADS) void bank_reduce_kernel(const RtPartial
   }
   idx[g] = b.idx;
   if (dist2) dist2[g] = b.d > 0.f ? b.d : 0.f;
+}
+
+// One thread per query: the slabs' lists in slab order.  Slabs ascend and a slab's list ascends in (d, idx), so a strict <
+// keeps the lower index in front on equal d.  The first k of the KP entries are written; an unused place is (-1, +inf).
+template <int KP>
+__global__ __launch_bounds__(RT_THREADS) void bank_reduce_topk_kernel(const RtPartial* __restrict__ part, int nslabs,
+                                                                      int64_t nq, int k, int32_t* __restrict__ idx,
+                                                                      float* __restrict__ dist2) {
+  const int64_t g = (int64_t)blockIdx.x * RT_THREADS + threadIdx.x;
+  if (g >= nq) return;
+  float ld[KP];
+  int li[KP];
+#pragma unroll
+  for (int j = 0; j < KP; ++j) {
+    const RtPartial c = part[g * KP + j];
+    ld[j] = c.d, li[j] = c.idx;
+  }
+  for (int s = 1; s < nslabs; ++s) {
+#pragma unroll
+    for (int j = 0; j < KP; ++j) {
+      const RtPartial c = part[((int64_t)s * nq + g) * KP + j];
+      if (!(c.d < ld[KP - 1])) break;
+      list_insert<KP>(ld, li, c.d, c.idx, [](float d, int, float ed, int) { return d < ed; });
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < KP; ++j) {
+    if (j < k) {
+      idx[g * k + j] = ld[j] == __builtin_inff() ? -1 : li[j];
+      if (dist2) dist2[g * k + j] = ld[j] > 0.f ? ld[j] : 0.f;
+    }
+  }
 }
 
 // ---- blend: gather fp16 value rows (lanes along c), transpose through LDS, mix (lanes along t) ----------------------------
@@ -278,6 +367,71 @@ __global__ __launch_bounds__(RT_THREADS) void bank_blend_kernel(const uint16_t* 
   for (int k = 0; k < 4; ++k) {
     const int64_t off = ((int64_t)b * C + c0 + hi + 8 * k) * T + t;
     y[off] = __fadd_rn(__fmul_rn(keep, x[off]), __fmul_rn(rate, tile[hi + 8 * k][lo]));   // (1 - r) x + r v, unfused
+  }
+}
+
+// ---- top-k blend: the weights of a frame once per (block, t), then the gather of bank_blend_kernel over k rows -----------------
+// dt_j = max(dist2_j, floor), u_j = (dt_0 / dt_j)^2 (0 where idx_j < 0), w_j = u_j / sum_j u_j, v = sum_j w_j value[idx_j]:
+// one division per j, the sum over ascending j, v an fmaf chain over ascending j.  The chain starts from -0, so a single
+// term of weight 1 keeps the stored value's bits, the sign of a zero included: k = 1 is bank_blend_kernel bit for bit.
+template <bool DENORM>
+__global__ __launch_bounds__(RT_THREADS) void bank_blend_topk_kernel(const uint16_t* __restrict__ values, int size, int C,
+                                                                     const float* x, const int32_t* __restrict__ idx,
+                                                                     const float* __restrict__ dist2, int k, float floor,
+                                                                     const float* __restrict__ mean,
+                                                                     const float* __restrict__ sd, float rate, float* y,
+                                                                     int T) {
+  __shared__ float tile[32][33];
+  __shared__ float sw[32][RT_MAX_K];
+  __shared__ int si[32][RT_MAX_K];
+  const int t0 = blockIdx.x * 32, c0 = blockIdx.y * 32, b = blockIdx.z;
+  const int lo = threadIdx.x & 31, hi = threadIdx.x >> 5;
+  if (threadIdx.x < 32 && t0 + (int)threadIdx.x < T) {
+    const int64_t f = ((int64_t)b * T + t0 + threadIdx.x) * k;
+    const float d0 = fmaxf(dist2[f], floor);
+    float u[RT_MAX_K], S = 0.f;
+    int ii[RT_MAX_K];
+#pragma unroll
+    for (int j = 0; j < RT_MAX_K; ++j) {
+      u[j] = 0.f, ii[j] = -1;
+      if (j < k) {
+        const int i = idx[f + j];
+        ii[j] = i >= size ? size - 1 : i;
+        if (i >= 0) {
+          const float q = __fdiv_rn(d0, fmaxf(dist2[f + j], floor));
+          u[j] = __fmul_rn(q, q);
+        }
+        S = __fadd_rn(S, u[j]);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < RT_MAX_K; ++j) {
+      sw[threadIdx.x][j] = S > 0.f ? __fdiv_rn(u[j], S) : 0.f;   // no usable entry at all: v = 0
+      si[threadIdx.x][j] = ii[j];
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int kk = 0; kk < 4; ++kk) {
+    const int tl = hi + 8 * kk;
+    if (t0 + tl < T) {
+      float v = -0.f;
+      for (int j = 0; j < k; ++j) {
+        const int i = si[tl][j];
+        if (i >= 0) v = fmaf(sw[tl][j], h2f(values[(int64_t)i * C + c0 + lo]), v);   // an unused place is not read
+      }
+      if (DENORM) v = __fadd_rn(__fmul_rn(v, sd[c0 + lo]), mean[c0 + lo]);   // the inverse of channel_affine_kernel
+      tile[lo][tl] = v;
+    }
+  }
+  __syncthreads();
+  const int t = t0 + lo;
+  if (t >= T) return;
+  const float keep = 1.f - rate;
+#pragma unroll
+  for (int kk = 0; kk < 4; ++kk) {
+    const int64_t off = ((int64_t)b * C + c0 + hi + 8 * kk) * T + t;
+    y[off] = __fadd_rn(__fmul_rn(keep, x[off]), __fmul_rn(rate, tile[hi + 8 * kk][lo]));   // (1 - r) x + r v, unfused
   }
 }
 
@@ -315,27 +469,52 @@ hipError_t bank_norms_launch(const uint16_t* rows, float* norms, int64_t row0, i
   return hipGetLastError();
 }
 
-hipError_t bank_search_launch(const uint16_t* keys, const float* norms, int size, int C, const float* x, const float* mean,
-                              const float* std, int B, int T, int32_t* idx, float* dist2, RtPartial* part, hipStream_t s) {
-  static_assert(KROW % 8 == 0 && sizeof(RtPartial) == 8 && 8 * RT_QTILE * sizeof(RtPartial) <= RT_KTILE * KROW * 2,
-                "LDS layout of bank_search_kernel");
+namespace {
+
+// one launcher for every list length: KP = 1 ends in bank_reduce_kernel, the longer lists in bank_reduce_topk_kernel
+template <int KP>
+hipError_t search_launch(const uint16_t* keys, const float* norms, int size, int C, const float* x, const float* mean,
+                         const float* std, int B, int T, int k, int32_t* idx, float* dist2, RtPartial* part, hipStream_t s) {
+  static_assert(KROW % 8 == 0 && sizeof(RtPartial) == 8 && 8 * RT_QTILE * KP * sizeof(RtPartial) <= RT_KTILE * KROW * 2,
+                "LDS layout of bank_search_kernel: the eight lists of every query fit the key tile");
   static_assert(RT_KTILE * (RT_KCHUNK / 8) == 4 * RT_THREADS && RT_KTILE == 32 * (RT_THREADS / 64) && RT_SLAB % RT_KTILE == 0,
                 "tile loader of bank_search_kernel");
   const int64_t nq = (int64_t)B * T;
   const int nslabs = (size + RT_SLAB - 1) / RT_SLAB;
   const size_t lds = search_lds_bytes(C);
-  static const hipError_t attr[2] = {allow_lds(bank_search_kernel<false>, search_lds_bytes(RT_MAX_C)),
-                                     allow_lds(bank_search_kernel<true>, search_lds_bytes(RT_MAX_C))};
+  static const hipError_t attr[2] = {allow_lds(bank_search_kernel<false, KP>, search_lds_bytes(RT_MAX_C)),
+                                     allow_lds(bank_search_kernel<true, KP>, search_lds_bytes(RT_MAX_C))};
   if (attr[0] != hipSuccess) return attr[0];
   if (attr[1] != hipSuccess) return attr[1];
   const dim3 grid((unsigned)((nq + RT_QTILE - 1) / RT_QTILE), (unsigned)nslabs), block(RT_THREADS);
   if (mean)
-    hipLaunchKernelGGL(bank_search_kernel<true>, grid, block, lds, s, keys, norms, size, C, x, mean, std, T, nq, part);
+    hipLaunchKernelGGL((bank_search_kernel<true, KP>), grid, block, lds, s, keys, norms, size, C, x, mean, std, T, nq, part);
   else
-    hipLaunchKernelGGL(bank_search_kernel<false>, grid, block, lds, s, keys, norms, size, C, x, mean, std, T, nq, part);
-  hipLaunchKernelGGL(bank_reduce_kernel, dim3((unsigned)((nq + RT_THREADS - 1) / RT_THREADS)), dim3(RT_THREADS), 0, s, part,
-                     nslabs, nq, idx, dist2);
+    hipLaunchKernelGGL((bank_search_kernel<false, KP>), grid, block, lds, s, keys, norms, size, C, x, mean, std, T, nq, part);
+  const dim3 rgrid((unsigned)((nq + RT_THREADS - 1) / RT_THREADS));
+  if constexpr (KP == 1)
+    hipLaunchKernelGGL(bank_reduce_kernel, rgrid, block, 0, s, part, nslabs, nq, idx, dist2);
+  else
+    hipLaunchKernelGGL(bank_reduce_topk_kernel<KP>, rgrid, block, 0, s, part, nslabs, nq, k, idx, dist2);
   return hipGetLastError();
+}
+
+}  // namespace
+
+hipError_t bank_search_launch(const uint16_t* keys, const float* norms, int size, int C, const float* x, const float* mean,
+                              const float* std, int B, int T, int32_t* idx, float* dist2, RtPartial* part, hipStream_t s) {
+  return search_launch<1>(keys, norms, size, C, x, mean, std, B, T, 1, idx, dist2, part, s);
+}
+
+hipError_t bank_search_topk_launch(const uint16_t* keys, const float* norms, int size, int C, const float* x,
+                                   const float* mean, const float* std, int B, int T, int k, int32_t* idx, float* dist2,
+                                   RtPartial* part, hipStream_t s) {
+  switch (rt_list_length(k)) {
+    case 1: return search_launch<1>(keys, norms, size, C, x, mean, std, B, T, k, idx, dist2, part, s);
+    case 2: return search_launch<2>(keys, norms, size, C, x, mean, std, B, T, k, idx, dist2, part, s);
+    case 4: return search_launch<4>(keys, norms, size, C, x, mean, std, B, T, k, idx, dist2, part, s);
+    default: return search_launch<8>(keys, norms, size, C, x, mean, std, B, T, k, idx, dist2, part, s);
+  }
 }
 
 hipError_t bank_blend_launch(const uint16_t* values, int size, int C, const float* x, const int32_t* idx, const float* mean,
@@ -345,5 +524,18 @@ hipError_t bank_blend_launch(const uint16_t* values, int size, int C, const floa
     hipLaunchKernelGGL(bank_blend_kernel<true>, grid, block, 0, s, values, size, C, x, idx, mean, std, rate, y, T);
   else
     hipLaunchKernelGGL(bank_blend_kernel<false>, grid, block, 0, s, values, size, C, x, idx, mean, std, rate, y, T);
+  return hipGetLastError();
+}
+
+hipError_t bank_blend_topk_launch(const uint16_t* values, int size, int C, const float* x, const int32_t* idx,
+                                  const float* dist2, int k, float floor, const float* mean, const float* std, float rate,
+                                  float* y, int B, int T, hipStream_t s) {
+  const dim3 grid((unsigned)((T + 31) / 32), (unsigned)(C / 32), (unsigned)B), block(RT_THREADS);
+  if (mean)
+    hipLaunchKernelGGL(bank_blend_topk_kernel<true>, grid, block, 0, s, values, size, C, x, idx, dist2, k, floor, mean, std,
+                       rate, y, T);
+  else
+    hipLaunchKernelGGL(bank_blend_topk_kernel<false>, grid, block, 0, s, values, size, C, x, idx, dist2, k, floor, mean, std,
+                       rate, y, T);
   return hipGetLastError();
 }

@@ -23,8 +23,9 @@ per-channel normalisation (:381-394).  Differences, all outside the hot path's s
     the LR simulation (`--simulate-lr`), or the decoded LR latent (latent-file input).  Every other file is unchanged.
   * `--index-bank PATH --index-rate R` also writes `{stem}_generated{suffix}_idx.pt` (and, with `--dac-weights`,
     `{stem}_generated{suffix}_idx.wav`): the generated latent with R of each frame's nearest neighbour in a latent bank
-    (`python -m jatsr_amd.retrieval build`) mixed in (jatsr_amd.retrieval, csrc/retrieval.hip).  Every other file is
-    unchanged.
+    (`python -m jatsr_amd.retrieval build`) mixed in (jatsr_amd.retrieval, csrc/retrieval.hip).  `--index-k K` (1..8,
+    default 1) mixes in the inverse-square-distance weighted mean of the K nearest frames instead; the file's metadata
+    records `index_k`, and for K > 1 the file also holds `idx` and `dist2` [frames, K].  Every other file is unchanged.
 
     python -m jatsr_amd.infer --checkpoint ckpt.pt --input-file clip.pt --stats-file stats.json --cfg-scale 3.0
 """
@@ -38,7 +39,7 @@ import torch
 
 from . import io as jio
 from .model import JaT_AudioSR_V2, JaT_AudioSR_V3, load_model
-from .retrieval import index_rate_arg
+from .retrieval import index_k_arg, index_rate_arg
 from .sampler import chunk_plan, sample_long
 
 
@@ -93,6 +94,9 @@ def build_parser():
                         "generated latent blended with each frame's nearest bank frame")
     p.add_argument("--index-rate", type=index_rate_arg, default=0.4, metavar="R",
                    help="with --index-bank: share of the retrieved frame in the blend, in [0, 1] (0.3 to 0.6 are usual)")
+    p.add_argument("--index-k", type=index_k_arg, default=1, metavar="K",
+                   help="with --index-bank: blend in the inverse-square-distance weighted mean of each frame's K nearest bank "
+                        "frames, 1..8 (1: the single nearest frame; RVC's index uses 8)")
     return p
 
 
@@ -116,6 +120,7 @@ def run(args):
         raise SystemExit("--f0-metrics needs --dac-weights and an HR ground truth (--simulate-lr, or a latent file with hr_latent)")
     index_bank = getattr(args, "index_bank", None)
     index_rate = index_rate_arg(getattr(args, "index_rate", 0.4)) if index_bank else 0.0
+    index_k = index_k_arg(getattr(args, "index_k", 1)) if index_bank else 1
     device = torch.device(args.device)
     os.makedirs(args.output_dir, exist_ok=True)
     model = load_model(args.checkpoint, device=device, cls=JaT_AudioSR_V2 if args.layernorm else JaT_AudioSR_V3,
@@ -170,12 +175,15 @@ def run(args):
         from .retrieval import LatentBank
         bank = LatentBank.load(index_bank, device=device)
         query = lr[None, :, :total].to(device).float() if bank.key == "lr" else None
-        enhanced = bank.retrieve(gen, index_rate, stats=stats, query=query)
+        enhanced, nn_idx, nn_dist2 = bank.retrieve(gen, index_rate, stats=stats, query=query, k=index_k, neighbours=True)
         idx_path = os.path.join(args.output_dir, f"{stem}_generated{suffix}_idx.pt")
+        lists = {"idx": nn_idx[0].cpu(), "dist2": nn_dist2[0].cpu()} if index_k > 1 else {}      # [frames, K]
         jio.save_latent_file(idx_path, generated_latent=enhanced[0].to("cpu", torch.float16),
                              metadata={"source": os.path.basename(path), "index_bank": os.path.basename(index_bank),
-                                       "index_rate": index_rate, "bank_rows": len(bank), "bank_key": bank.key})
-        print(f"retrieval: {len(bank)} bank rows (key={bank.key}), index rate {index_rate} -> {idx_path}")
+                                       "index_rate": index_rate, "index_k": index_k, "bank_rows": len(bank),
+                                       "bank_key": bank.key}, **lists)
+        print(f"retrieval: {len(bank)} bank rows (key={bank.key}), index rate {index_rate}" +
+              (f", {index_k} nearest frames" if index_k > 1 else "") + f" -> {idx_path}")
         if args.dac_weights:
             name = f"{stem}_generated{suffix}_idx.wav"
             jio.write_wav_float32(os.path.join(args.output_dir, name), codec.decode(enhanced[:1])[0, 0], codec.sample_rate)

@@ -8,6 +8,11 @@ include/jat_hip.h).  `key="hr"` looks a frame up by its own (generated) content,
 
     python -m jatsr_amd.retrieval build --data-dir data_processed --out bank.pt --max-frames 100000
     python -m jatsr_amd.infer ... --index-bank bank.pt --index-rate 0.4
+    python -m jatsr_amd.infer ... --index-bank bank.pt --index-rate 0.4 --index-k 8
+
+`--index-k K` (`search_topk`, `blend_topk`, `retrieve(k=K)`) mixes in the inverse-square-distance weighted mean of
+the K nearest frames, 1 <= K <= 8, as RVC's index does with K = 8, instead of the single nearest one: the retrieved track then
+varies continuously with the query instead of jumping where the arg-min changes.
 
 Whether retrieval improves audio quality is not established here: nothing in this repository was run with trained weights.
 """
@@ -61,6 +66,33 @@ def index_rate_arg(text):
         return check_index_rate(text)
     except ValueError as e:
         raise argparse.ArgumentTypeError(str(e))
+
+
+def check_index_k(index_k):
+    """The number of nearest frames as an int in 1..8 (JAT_BANK_MAX_K); ValueError otherwise."""
+    try:
+        k = int(index_k)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError(f"index_k {index_k!r} outside 1..{L.BANK_MAX_K}")
+    if k != index_k or isinstance(index_k, bool) or not 1 <= k <= L.BANK_MAX_K:
+        raise ValueError(f"index_k {index_k!r} outside 1..{L.BANK_MAX_K}")
+    return k
+
+
+def index_k_arg(text):
+    """argparse type of --index-k."""
+    try:
+        return check_index_k(int(text))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"index_k {text!r} outside 1..{L.BANK_MAX_K}")
+
+
+def check_dist2_floor(dist2_floor):
+    """The distance floor of the top-k blend as a positive finite float; ValueError otherwise (a NaN is not positive)."""
+    f = C.c_float(float(dist2_floor)).value          # as the fp32 the kernel gets
+    if not 0.0 < f < float("inf"):
+        raise ValueError(f"dist2_floor {dist2_floor!r} must be positive and finite")
+    return f
 
 
 def _stats_cpu(stats, channels):
@@ -274,11 +306,68 @@ class LatentBank:
                                            L.stream_ptr()))
         return out
 
-    def retrieve(self, x, index_rate, stats=None, query=None):
+    def topk_workspace_bytes(self, n_queries, k):
+        n = C.c_size_t()
+        L.check(L.lib().jat_bank_topk_workspace_bytes(self._h, int(n_queries), int(k), C.byref(n)))
+        return n.value
+
+    def search_topk(self, x, k, mean=None, std=None):
+        """The k nearest key rows of every frame, 1 <= k <= 8, ordered by (distance, index) -> (idx int32 [B, T, k], dist2
+        fp32 [B, T, k]).  A bank of fewer than k rows fills the tail with idx -1 and dist2 +inf.  The first j columns are
+        the result for k = j, and k = 1 is `search`."""
+        k = check_index_k(k)
+        x = self._x(x)
+        B, _, T = x.shape
+        if B < 1 or T < 1:
+            raise ValueError(f"x {tuple(x.shape)}: B and T must be positive")
+        need = self.topk_workspace_bytes(B * T, k)
+        if self._work is None or self._work.numel() < need:
+            self._work = torch.empty(need, dtype=torch.uint8, device=self.device)
+        idx = torch.empty(B, T, k, dtype=torch.int32, device=self.device)
+        dist2 = torch.empty(B, T, k, dtype=torch.float32, device=self.device)
+        mean, std = self._vec(mean), self._vec(std)
+        with torch.cuda.device(self.device):
+            L.check(L.lib().jat_bank_search_topk(self._h, L.ptr(x), L.ptr(mean), L.ptr(std), B, T, k, L.ptr(idx), L.ptr(dist2),
+                                                 L.ptr(self._work), self._work.numel(), L.stream_ptr()))
+        return idx, dist2
+
+    def blend_topk(self, x, idx, dist2, index_rate, mean=None, std=None, out=None, dist2_floor=1e-6):
+        """(1 - index_rate) * x + index_rate * v with v the inverse-square-distance weighted mean of the k value rows idx
+        [B, T, k] names: weights (max(dist2_0, floor) / max(dist2_j, floor))^2 normalised to sum 1 — RVC's square(1 / score)
+        wherever the distances exceed the floor; entries with idx < 0 carry no weight.  With the value statistics v is
+        de-normalised first.  out: where to write ([B, C, T] fp32 contiguous; may be x)."""
+        r = check_index_rate(index_rate)
+        floor = check_dist2_floor(dist2_floor)
+        if out is None:
+            x = self._x(x)
+            out = torch.empty_like(x)
+        else:
+            if not x.is_contiguous() or not out.is_contiguous() or out.shape != x.shape or out.dtype != torch.float32:
+                raise ValueError("blend_topk(out=...): x and out must be contiguous fp32 tensors of one shape")
+            x = self._x(x)
+        B, _, T = x.shape
+        if idx.dim() != 3 or idx.shape[:2] != (B, T) or idx.dtype != torch.int32 or not idx.is_cuda:
+            raise ValueError(f"idx: expected CUDA int32 [{B}, {T}, k], got {idx.dtype} {tuple(idx.shape)}")
+        k = check_index_k(int(idx.shape[2]))
+        if dist2.shape != idx.shape or dist2.dtype != torch.float32 or not dist2.is_cuda:
+            raise ValueError(f"dist2: expected CUDA fp32 {tuple(idx.shape)}, got {dist2.dtype} {tuple(dist2.shape)}")
+        idx, dist2 = idx.contiguous(), dist2.contiguous()
+        mean, std = self._vec(mean), self._vec(std)
+        with torch.cuda.device(self.device):
+            L.check(L.lib().jat_bank_blend_topk(self._h, L.ptr(x), L.ptr(idx), L.ptr(dist2), k, L.ptr(mean), L.ptr(std), r,
+                                                floor, L.ptr(out), B, T, L.stream_ptr()))
+        return out
+
+    def retrieve(self, x, index_rate, stats=None, query=None, k=1, dist2_floor=1e-6, neighbours=False):
         """Search + blend on a de-normalised HR latent x [B, C, T].  The query is x under the HR statistics (key == "hr") or
         `query`, the un-normalised LR latent of the same shape, under the LR statistics (key == "lr"); the retrieved HR
-        frame is de-normalised in the blend.  stats: must be the statistics the bank was built with (default: those)."""
+        frame is de-normalised in the blend.  stats: must be the statistics the bank was built with (default: those).
+        k > 1: the inverse-square-distance weighted mean of the k nearest frames (`search_topk`, `blend_topk`) takes the
+        place of the single nearest one; k = 1 makes exactly the calls it always made.  neighbours: return (y, idx, dist2)
+        with the lists the blend used."""
         check_index_rate(index_rate)
+        k = check_index_k(k)
+        check_dist2_floor(dist2_floor)
         if stats is not None:
             self.check_stats(stats)
         elif self.stats is None:
@@ -289,10 +378,16 @@ class LatentBank:
                 raise ValueError("a bank keyed by LR frames needs the LR latent as `query`")
             if query.shape != x.shape:
                 raise ValueError(f"query {tuple(query.shape)} does not match x {tuple(x.shape)}")
-            idx, _ = self.search(query.to(self.device, torch.float32), s["lr_mean"], s["lr_std"])
+            q, mean, std = query.to(self.device, torch.float32), s["lr_mean"], s["lr_std"]
         else:
-            idx, _ = self.search(x, s["hr_mean"], s["hr_std"])
-        return self.blend(x, idx, index_rate, s["hr_mean"], s["hr_std"])
+            q, mean, std = x, s["hr_mean"], s["hr_std"]
+        if k == 1:
+            idx, dist2 = self.search(q, mean, std)
+            y = self.blend(x, idx, index_rate, s["hr_mean"], s["hr_std"])
+        else:
+            idx, dist2 = self.search_topk(q, k, mean, std)
+            y = self.blend_topk(x, idx, dist2, index_rate, s["hr_mean"], s["hr_std"], dist2_floor=dist2_floor)
+        return (y, idx, dist2) if neighbours else y
 
     # ---- files ----------------------------------------------------------------------------------------------------------
     def state(self):

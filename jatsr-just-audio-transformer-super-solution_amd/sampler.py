@@ -222,7 +222,7 @@ def chunk_groups(lens, pad_short_chunks=True):
 @torch.no_grad()
 def sample_long(model, lr_latent, hr_mean, hr_std, lr_mean, lr_std, num_steps=50, cfg_scale=1.0,
                 chunk_frames=1378, overlap_frames=172, noise=None, pad_short_chunks=True, solver="euler", timesteps=None,
-                bank=None, index_rate=0.0):
+                bank=None, index_rate=0.0, index_k=1):
     """Chunked long-sequence inference == the chunk loop of infer_test_v3m2.py:340-404, with the chunks of a file
     BATCHED into one sampler launch instead of the reference's serial B=1 loop (pad_short_chunks=False: one launch
     per distinct chunk length, the round-1 behaviour).
@@ -233,11 +233,14 @@ def sample_long(model, lr_latent, hr_mean, hr_std, lr_mean, lr_std, num_steps=50
     bank (a `jatsr_amd.retrieval.LatentBank`) with index_rate > 0: latent retrieval on the whole cross-faded output, once —
     every frame is looked up in the bank (by its own content under the HR statistics, or by the LR input under the LR
     statistics when the bank is keyed by LR frames) and index_rate of the retrieved HR frame is mixed in.  Without a bank, or
-    at index_rate 0, nothing more is launched.
+    at index_rate 0, nothing more is launched.  index_k in 1..8: that many nearest frames, mixed with inverse-square-distance
+    weights, stand in for the single nearest one (index_k = 1: `search` and `blend`, unchanged).
     """
     index_rate = float(index_rate)
     if not 0.0 <= index_rate <= 1.0:
         raise ValueError(f"index_rate {index_rate!r} outside [0, 1]")
+    from .retrieval import check_index_k
+    index_k = check_index_k(index_k)
     Cc, total = lr_latent.shape
     plan = chunk_plan(total, chunk_frames, overlap_frames)
     lr = lr_latent.unsqueeze(0)
@@ -277,4 +280,4 @@ def sample_long(model, lr_latent, hr_mean, hr_std, lr_mean, lr_std, num_steps=50
     if bank is None or index_rate == 0.0:
         return out
     stats = {"hr_mean": hr_mean, "hr_std": hr_std, "lr_mean": lr_mean, "lr_std": lr_std}
-    return bank.retrieve(out, index_rate, stats=stats, query=lr.float() if bank.key == "lr" else None)
+    return bank.retrieve(out, index_rate, stats=stats, query=lr.float() if bank.key == "lr" else None, k=index_k)
