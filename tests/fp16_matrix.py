@@ -46,6 +46,10 @@ MATRIX = {
     "test_gpu_ema.py": ("child", [
         ["-k", "(fused_adamw and not 1000004) or non_finite_gradient or swap_exchanges or follows_the_fp64 or weights_context or "
                "across_real"]]),
+    # every side-stream case: the whole file takes 18 s on the MI355X, less than the other children
+    "test_gpu_streams.py": ("child", [[]]),
+    # the four model entries: the only workspaces here whose kernels follow the operand dtype
+    "test_gpu_workspaces.py": ("child", [["-k", "model"]]),
     "test_gpu_mod3_train.py": ("own_child", "test_fp16_library_runs_the_mod3_step"),
     # latent_loss_kernel / latent_loss_fft_kernel: fp32 kernels of train.hip, a translation unit compiled with -DJAT_FP16
     "test_gpu_loss_paths.py": ("same_bits", "test_fp16_library_gives_the_same_bits"),

@@ -115,7 +115,7 @@ def test_end_to_end_against_the_fp64_statement(name):
         assert np.isfinite(g["f0"][b]).all() and (g["f0"][b] > 0).all()
 
 
-def _raw_yin(x, par, B, n, frames, lags, guard=96, stream=None):
+def _raw_yin(x, par, B, n, frames, lags, guard=96):
     """jat_yin straight through the ABI into buffers with guard bands on both sides -> (rc, payloads, guards_intact)"""
     spec = {"f0": (torch.float32, B * frames), "aperiodicity": (torch.float32, B * frames), "voiced": (torch.uint8, B * frames),
             "index": (torch.int32, B * frames), "d": (torch.float32, B * frames * lags), "cmndf": (torch.float32, B * frames * lags)}

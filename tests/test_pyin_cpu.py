@@ -190,7 +190,8 @@ def test_symbols_declared_bound_and_exported_from_both_libraries(built_lib):
 
 
 def test_no_existing_test_calls_the_new_symbols():
-    mine = {"test_pyin_cpu.py", "test_pyin_gpu.py", "pyin_ref.py"}
+    # test_gpu_streams.py came later and runs every stream-taking entry of the header on a side stream, these two included
+    mine = {"test_pyin_cpu.py", "test_pyin_gpu.py", "pyin_ref.py", "test_gpu_streams.py"}
     for name in sorted(os.listdir(os.path.join(ROOT, "tests"))):
         if name.endswith(".py") and name not in mine:
             assert "pyin" not in open(os.path.join(ROOT, "tests", name)).read(), name
