@@ -25,7 +25,7 @@ _LAZY = {
     "train_monitor": "train", "monitor_figures": "train",
     "LatentStore": "data", "epoch_batches": "data", "val_crop_start": "data", "train_crop_start": "data",
     "train_batch_plan": "data", "val_batch_plan": "data",
-    "LatentBank": "retrieval", "frame_plan": "retrieval",
+    "LatentBank": "retrieval", "frame_plan": "retrieval", "MultiScaleBank": "retrieval", "load_bank": "retrieval",
     "find_latest_checkpoint_dir": "fit", "resolve_run_dir": "fit",
 }
 __all__ = ["recipe"] + sorted(_LAZY)

@@ -198,6 +198,15 @@ SIGNATURES = {
     "jat_pyin_set_profile": (C.c_int, [_VP, _I32]),
     "jat_pyin_profile": (C.c_int, [_VP, _VP]),
 }
+# name -> (restype, argtypes); every symbol include/jat_hip_ms.h declares (multi-scale retrieval), bound after SIGNATURES
+MS_SIGNATURES = {
+    "jat_bank_add_pooled": (C.c_int, [_VP, _VP, _VP, _I32, _I64, _I64, _I64, _I32, _I32, _VP, _VP, _VP, _VP, _VP]),
+    "jat_bank_pool_frames": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I32, C.POINTER(_I32), C.POINTER(_VP), _VP]),
+    "jat_bank_mix_scales": (C.c_int, [_VP, _I32, C.POINTER(_I32), C.POINTER(_VP), C.POINTER(_F32), _F32, _VP, _I32, _I32, _I32,
+                                      _VP]),
+}
+BANK_MAX_SCALES = 4          # JAT_BANK_MAX_SCALES
+BANK_SCALES = (1, 2, 4, 8)   # what a scale may be
 MONITOR_WORK_BYTES = 49152   # JAT_MONITOR_WORK_BYTES
 LTAS_SLICES = 64             # JAT_LTAS_SLICES
 BANK_SLAB = 4096             # JAT_BANK_SLAB
@@ -224,7 +233,7 @@ def lib():
         # before it finds no device at the first kernel launch ("no ROCm-capable device is detected")
         import torch  # noqa: F401
         h = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(MS_SIGNATURES.items()):
             if not hasattr(h, name) and os.environ.get("JAT_LIB_ALLOW_MISSING"):
                 continue      # A/B against an OLDER build through JAT_LIB_PATH (tools/sampler_ab.py): it lacks the newest entry points
             fn = getattr(h, name)

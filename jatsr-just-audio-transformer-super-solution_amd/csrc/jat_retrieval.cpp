@@ -2,6 +2,7 @@
 // Every device buffer is allocated in jat_bank_create; add / search / blend only enqueue on the caller's stream.
 #include "jat_internal.h"
 #include "jat_retrieval_kernels.h"
+#include "../../include/jat_hip_ms.h"
 
 struct jat_bank {
   int channels = 0, capacity = 0, size = 0;
@@ -13,7 +14,8 @@ struct jat_bank {
 namespace {
 
 constexpr int64_t kMax31 = 0x7fffffff;
-static_assert(JAT_BANK_SLAB == RT_SLAB && JAT_BANK_MAX_K == RT_MAX_K, "header and kernel disagree");
+static_assert(JAT_BANK_SLAB == RT_SLAB && JAT_BANK_MAX_K == RT_MAX_K && JAT_BANK_MAX_SCALES == RT_MAX_SCALES,
+              "header and kernel disagree");
 
 int check_bank(const char* who, const jat_bank* b) {
   if (!b) return fail(JAT_E_INVALID, "%s: null bank", who);
@@ -40,6 +42,45 @@ size_t topk_bytes(const jat_bank* b, int64_t nq, int k) {
 
 int check_k(const char* who, int32_t k) {
   if (k < 1 || k > JAT_BANK_MAX_K) return fail(JAT_E_INVALID, "%s: k %d outside 1..%d", who, k, JAT_BANK_MAX_K);
+  return JAT_OK;
+}
+
+// what jat_bank_add and jat_bank_add_pooled refuse: `count` frames (window starts) first + i stride of a source of `len`
+int check_add(const char* who, const jat_bank* bank, const void* key_src, const void* value_src, int64_t len, int64_t first,
+              int64_t stride, int32_t count, const float* key_mean, const float* key_std, const float* value_mean,
+              const float* value_std) {
+  JCHK(check_bank(who, bank));
+  if (!key_src || !key_mean || !key_std) return fail(JAT_E_INVALID, "%s: null key source or statistics", who);
+  if (bank->paired ? (!value_src || !value_mean || !value_std) : (value_src != nullptr))
+    return fail(JAT_E_INVALID, bank->paired ? "%s: a paired bank needs the value source and its statistics"
+                                            : "%s: value source given to a bank that is not paired", who);
+  if (len < 1 || len > kMax31 || first < 0 || stride < 1 || count < 1)
+    return fail(JAT_E_INVALID, "%s: len %lld, first %lld, stride %lld, count %d", who, (long long)len, (long long)first,
+                (long long)stride, count);
+  if (first >= len || (int64_t)(count - 1) > (len - 1 - first) / stride)
+    return fail(JAT_E_INVALID, "%s: frames %lld + %lld i, i < %d, leave the %lld frames of the source", who, (long long)first,
+                (long long)stride, count, (long long)len);
+  if ((int64_t)bank->size + count > bank->capacity)
+    return fail(JAT_E_STATE, "%s: %d + %d rows exceed the capacity %d", who, bank->size, count, bank->capacity);
+  return JAT_OK;
+}
+
+// [p, p + n floats) and [q, q + m floats) share a byte
+bool overlap(const float* p, int64_t n, const float* q, int64_t m) {
+  const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
+  return a < b + (uintptr_t)m * sizeof(float) && b < a + (uintptr_t)n * sizeof(float);
+}
+
+// n scales, strictly ascending, each one of 1, 2, 4, 8 and at least `least`
+int check_scale_list(const char* who, int32_t n, const int32_t* scales, int most, int least) {
+  if (n < 1 || n > most) return fail(JAT_E_INVALID, "%s: %d scales outside 1..%d", who, n, most);
+  if (!scales) return fail(JAT_E_INVALID, "%s: null scales", who);
+  for (int i = 0; i < n; ++i) {
+    if (!rt_scale_ok(scales[i]) || scales[i] < least)
+      return fail(JAT_E_INVALID, "%s: scale %d is not one of%s 2, 4, 8", who, scales[i], least > 1 ? "" : " 1,");
+    if (i && scales[i] <= scales[i - 1])
+      return fail(JAT_E_INVALID, "%s: scales must ascend strictly (%d after %d)", who, scales[i], scales[i - 1]);
+  }
   return JAT_OK;
 }
 
@@ -98,19 +139,7 @@ int jat_bank_clear(jat_bank* bank) {
 int jat_bank_add(jat_bank* bank, const void* key_src, const void* value_src, int32_t src_is_fp16, int64_t len, int64_t first,
                  int64_t stride, int32_t count, const float* key_mean, const float* key_std, const float* value_mean,
                  const float* value_std, void* stream) {
-  JCHK(check_bank("jat_bank_add", bank));
-  if (!key_src || !key_mean || !key_std) return fail(JAT_E_INVALID, "jat_bank_add: null key source or statistics");
-  if (bank->paired ? (!value_src || !value_mean || !value_std) : (value_src != nullptr))
-    return fail(JAT_E_INVALID, bank->paired ? "jat_bank_add: a paired bank needs the value source and its statistics"
-                                            : "jat_bank_add: value source given to a bank that is not paired");
-  if (len < 1 || len > kMax31 || first < 0 || stride < 1 || count < 1)
-    return fail(JAT_E_INVALID, "jat_bank_add: len %lld, first %lld, stride %lld, count %d", (long long)len, (long long)first,
-                (long long)stride, count);
-  if (first >= len || (int64_t)(count - 1) > (len - 1 - first) / stride)
-    return fail(JAT_E_INVALID, "jat_bank_add: frames %lld + %lld i, i < %d, leave the %lld frames of the source",
-                (long long)first, (long long)stride, count, (long long)len);
-  if ((int64_t)bank->size + count > bank->capacity)
-    return fail(JAT_E_STATE, "jat_bank_add: %d + %d rows exceed the capacity %d", bank->size, count, bank->capacity);
+  JCHK(check_add("jat_bank_add", bank, key_src, value_src, len, first, stride, count, key_mean, key_std, value_mean, value_std));
   hipStream_t s = (hipStream_t)stream;
   KCHK(bank_pack_launch(key_src, bank->paired ? value_src : nullptr, src_is_fp16 != 0, len, first, stride, count, key_mean,
                         key_std, value_mean, value_std, bank->keys, bank->values, bank->size, bank->channels, s));
@@ -225,6 +254,68 @@ int jat_bank_blend_topk(jat_bank* bank, const float* x, const int32_t* idx, cons
   if (bank->size < 1) return fail(JAT_E_STATE, "jat_bank_blend_topk: the bank is empty");
   KCHK(bank_blend_topk_launch(bank->values, bank->size, bank->channels, x, idx, dist2, k, dist2_floor, value_mean, value_std,
                               rate, y, B, T, (hipStream_t)stream));
+  return JAT_OK;
+}
+
+// ---- multi-scale retrieval (include/jat_hip_ms.h) ----------------------------------------------------------------------------
+int jat_bank_add_pooled(jat_bank* bank, const void* key_src, const void* value_src, int32_t src_is_fp16, int64_t len,
+                        int64_t first, int64_t stride, int32_t count, int32_t window, const float* key_mean,
+                        const float* key_std, const float* value_mean, const float* value_std, void* stream) {
+  JCHK(check_add("jat_bank_add_pooled", bank, key_src, value_src, len, first, stride, count, key_mean, key_std, value_mean,
+                 value_std));
+  if (!rt_scale_ok(window)) return fail(JAT_E_INVALID, "jat_bank_add_pooled: window %d is not one of 1, 2, 4, 8", window);
+  hipStream_t s = (hipStream_t)stream;
+  KCHK(bank_pack_pool_launch(key_src, bank->paired ? value_src : nullptr, src_is_fp16 != 0, len, first, stride, count, window,
+                             key_mean, key_std, value_mean, value_std, bank->keys, bank->values, bank->size, bank->channels,
+                             s));
+  KCHK(bank_norms_launch(bank->keys, bank->norms, bank->size, count, bank->channels, s));
+  bank->size += count;
+  return JAT_OK;
+}
+
+int jat_bank_pool_frames(const float* x, const float* mean, const float* std, int32_t B, int32_t C, int32_t T, int32_t n,
+                         const int32_t* scales, float* const* outs, void* stream) {
+  JCHK(check_queries("jat_bank_pool_frames", nullptr, B, T));
+  if (!rt_channels_ok(C))
+    return fail(JAT_E_INVALID, "jat_bank_pool_frames: channels %d must be a multiple of 32 in %d..%d", C, RT_MIN_C, RT_MAX_C);
+  if (!x || !outs) return fail(JAT_E_INVALID, "jat_bank_pool_frames: null buffer");
+  if ((mean != nullptr) != (std != nullptr))
+    return fail(JAT_E_INVALID, "jat_bank_pool_frames: mean and std are both given or both null");
+  JCHK(check_scale_list("jat_bank_pool_frames", n, scales, RT_MAX_SCALES - 1, 2));
+  RtPoolArgs a = {};
+  a.n = n;
+  for (int i = 0; i < n; ++i) {
+    const int64_t Ts = ((int64_t)T + scales[i] - 1) / scales[i];
+    if (!outs[i]) return fail(JAT_E_INVALID, "jat_bank_pool_frames: null output for scale %d", scales[i]);
+    if (overlap(x, (int64_t)B * C * T, outs[i], (int64_t)B * C * Ts))
+      return fail(JAT_E_INVALID, "jat_bank_pool_frames: the output of scale %d overlaps x", scales[i]);
+    a.out[i] = outs[i], a.scale[i] = scales[i];
+  }
+  KCHK(bank_pool_queries_launch(x, mean, std, B, C, T, a, (hipStream_t)stream));
+  return JAT_OK;
+}
+
+int jat_bank_mix_scales(const float* x, int32_t n, const int32_t* scales, const float* const* tracks, const float* weights,
+                        float rate, float* y, int32_t B, int32_t C, int32_t T, void* stream) {
+  JCHK(check_queries("jat_bank_mix_scales", nullptr, B, T));
+  if (C < 1 || C > RT_MAX_C) return fail(JAT_E_INVALID, "jat_bank_mix_scales: channels %d outside 1..%d", C, RT_MAX_C);
+  if (!x || !y || !tracks || !weights) return fail(JAT_E_INVALID, "jat_bank_mix_scales: null buffer");
+  if (!(rate >= 0.f && rate <= 1.f))
+    return fail(JAT_E_INVALID, "jat_bank_mix_scales: index rate %g outside [0, 1]", (double)rate);
+  JCHK(check_scale_list("jat_bank_mix_scales", n, scales, RT_MAX_SCALES, 1));
+  RtMixArgs a = {};
+  a.n = n;
+  for (int i = 0; i < n; ++i) {
+    const int64_t Ts = ((int64_t)T + scales[i] - 1) / scales[i];
+    if (!tracks[i]) return fail(JAT_E_INVALID, "jat_bank_mix_scales: null track for scale %d", scales[i]);
+    if (!(weights[i] > 0.f) || weights[i] == __builtin_inff())
+      return fail(JAT_E_INVALID, "jat_bank_mix_scales: weight %g of scale %d must be positive and finite", (double)weights[i],
+                  scales[i]);
+    if (overlap(y, (int64_t)B * C * T, tracks[i], (int64_t)B * C * Ts))
+      return fail(JAT_E_INVALID, "jat_bank_mix_scales: the track of scale %d overlaps y", scales[i]);
+    a.v[i] = tracks[i], a.scale[i] = scales[i], a.a[i] = weights[i];
+  }
+  KCHK(bank_mix_scales_launch(x, a, rate, y, B, C, T, (hipStream_t)stream));
   return JAT_OK;
 }
 

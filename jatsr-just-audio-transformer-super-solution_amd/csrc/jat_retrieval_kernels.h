@@ -47,3 +47,32 @@ hipError_t bank_blend_topk_launch(const uint16_t* values, int size, int C, const
 // outside [0, size) is clamped into it
 hipError_t bank_blend_launch(const uint16_t* values, int size, int C, const float* x, const int32_t* idx, const float* mean,
                              const float* std, float rate, float* y, int B, int T, hipStream_t s);
+
+// ---- multi-scale retrieval (retrieval_ms.hip) -----------------------------------------------------------------
+constexpr int RT_MAX_SCALES = 4;       // scales per multi-scale bank at most, each one of 1, 2, 4, 8
+constexpr int RT_POOL_FRAMES = 256;    // frames of x one pooling workgroup reads: 32 windows of the widest scale
+
+inline bool rt_scale_ok(int s) { return s == 1 || s == 2 || s == 4 || s == 8; }
+struct RtPoolArgs {   // by value in the kernel's arguments: the scales > 1 of one launch and where each goes
+  float* out[RT_MAX_SCALES - 1];       // [B, C, ceil(T / scale)]
+  int scale[RT_MAX_SCALES - 1];
+  int n;
+};
+struct RtMixArgs {    // by value: the tracks of one mix
+  const float* v[RT_MAX_SCALES];       // [B, C, ceil(T / scale)]
+  int scale[RT_MAX_SCALES];
+  float a[RT_MAX_SCALES];              // the weights, normalised by the caller
+  int n;
+};
+// bank_pack_launch with a window: row i pools the frames first + i * stride + j, j < min(window, len - frame), of each
+// channel: normalised, summed in ascending order, divided by their number.  window = 1 writes what bank_pack_launch writes.
+hipError_t bank_pack_pool_launch(const void* src, const void* src2, bool src_fp16, int64_t len, int64_t first, int64_t stride,
+                                 int count, int window, const float* mean, const float* std, const float* mean2,
+                                 const float* std2, uint16_t* rows, uint16_t* rows2, int64_t row0, int C, hipStream_t s);
+// out_i[b, c, ts] = the pooled window of scale_i that starts at frame ts * scale_i of x[b, c, :] (normalised with mean / std
+// when given), for every i < a.n in one launch; C a multiple of 32
+hipError_t bank_pool_queries_launch(const float* x, const float* mean, const float* std, int B, int C, int T,
+                                    const RtPoolArgs& a, hipStream_t s);
+// y = (1 - rate) x + rate sum_i a_i u_i, u_i the track v_i interpolated linearly (half-pixel centres) to T frames; y may be x
+hipError_t bank_mix_scales_launch(const float* x, const RtMixArgs& a, float rate, float* y, int B, int C, int T,
+                                  hipStream_t s);

@@ -26,6 +26,9 @@ per-channel normalisation (:381-394).  Differences, all outside the hot path's s
     (`python -m jatsr_amd.retrieval build`) mixed in (jatsr_amd.retrieval, csrc/retrieval.hip).  `--index-k K` (1..8,
     default 1) mixes in the inverse-square-distance weighted mean of the K nearest frames instead; the file's metadata
     records `index_k`, and for K > 1 the file also holds `idx` and `dist2` [frames, K].  Every other file is unchanged.
+    A multi-scale bank file (`retrieval build --scales 1,2,4`) needs no switch: `--index-bank` loads either
+    format, `--index-scale-weights W1,W2,...` replaces the stored scale weights, and the metadata gains `index_scales` and
+    `index_scale_weights` (for K > 1 the lists are `idx_s{scale}` / `dist2_s{scale}`, one pair per scale).
 
     python -m jatsr_amd.infer --checkpoint ckpt.pt --input-file clip.pt --stats-file stats.json --cfg-scale 3.0
 """
@@ -39,7 +42,7 @@ import torch
 
 from . import io as jio
 from .model import JaT_AudioSR_V2, JaT_AudioSR_V3, load_model
-from .retrieval import index_k_arg, index_rate_arg
+from .retrieval import index_k_arg, index_rate_arg, scale_weights_arg
 from .sampler import chunk_plan, sample_long
 
 
@@ -97,6 +100,9 @@ def build_parser():
     p.add_argument("--index-k", type=index_k_arg, default=1, metavar="K",
                    help="with --index-bank: blend in the inverse-square-distance weighted mean of each frame's K nearest bank "
                         "frames, 1..8 (1: the single nearest frame; RVC's index uses 8)")
+    p.add_argument("--index-scale-weights", type=scale_weights_arg, default=None, metavar="W1,W2,...",
+                   help="with a multi-scale --index-bank (retrieval build --scales): the share of each scale's track, one "
+                        "positive number per scale, normalised to sum 1 (default: the weights stored in the bank file)")
     return p
 
 
@@ -172,18 +178,35 @@ def run(args):
     if args.dac_weights:
         codec = decode_to_wav(args, gen, hr, lr, total, stem, suffix, device, codec, source)
     if index_bank:
-        from .retrieval import LatentBank
-        bank = LatentBank.load(index_bank, device=device)
+        from .retrieval import MultiScaleBank, load_bank
+        bank = load_bank(index_bank, device=device)            # either format: a LatentBank or a MultiScaleBank
+        multi = isinstance(bank, MultiScaleBank)
+        scale_weights = getattr(args, "index_scale_weights", None)
+        if scale_weights is not None:
+            if not multi:
+                raise SystemExit("--index-scale-weights needs a multi-scale bank (retrieval build --scales)")
+            try:
+                bank.set_weights(scale_weights)
+            except ValueError as e:
+                raise SystemExit(f"--index-scale-weights: {e}")
         query = lr[None, :, :total].to(device).float() if bank.key == "lr" else None
         enhanced, nn_idx, nn_dist2 = bank.retrieve(gen, index_rate, stats=stats, query=query, k=index_k, neighbours=True)
         idx_path = os.path.join(args.output_dir, f"{stem}_generated{suffix}_idx.pt")
-        lists = {"idx": nn_idx[0].cpu(), "dist2": nn_dist2[0].cpu()} if index_k > 1 else {}      # [frames, K]
+        lists, extra = {}, {}
+        if multi:                                              # per scale s: idx_s{s}, dist2_s{s} [ceil(frames / s), K]
+            extra = {"index_scales": list(bank.scales), "index_scale_weights": list(bank.weights)}
+            if index_k > 1:
+                for sc, i, d in zip(bank.scales, nn_idx, nn_dist2):
+                    lists.update({f"idx_s{sc}": i[0].cpu(), f"dist2_s{sc}": d[0].cpu()})
+        elif index_k > 1:
+            lists = {"idx": nn_idx[0].cpu(), "dist2": nn_dist2[0].cpu()}                         # [frames, K]
         jio.save_latent_file(idx_path, generated_latent=enhanced[0].to("cpu", torch.float16),
                              metadata={"source": os.path.basename(path), "index_bank": os.path.basename(index_bank),
                                        "index_rate": index_rate, "index_k": index_k, "bank_rows": len(bank),
-                                       "bank_key": bank.key}, **lists)
+                                       "bank_key": bank.key, **extra}, **lists)
         print(f"retrieval: {len(bank)} bank rows (key={bank.key}), index rate {index_rate}" +
-              (f", {index_k} nearest frames" if index_k > 1 else "") + f" -> {idx_path}")
+              (f", {index_k} nearest frames" if index_k > 1 else "") +
+              (f", scales {list(bank.scales)}" if multi else "") + f" -> {idx_path}")
         if args.dac_weights:
             name = f"{stem}_generated{suffix}_idx.wav"
             jio.write_wav_float32(os.path.join(args.output_dir, name), codec.decode(enhanced[:1])[0, 0], codec.sample_rate)

@@ -14,6 +14,14 @@ include/jat_hip.h).  `key="hr"` looks a frame up by its own (generated) content,
 the K nearest frames, 1 <= K <= 8, as RVC's index does with K = 8, instead of the single nearest one: the retrieved track then
 varies continuously with the query instead of jumping where the arg-min changes.
 
+Multi-scale retrieval (`MultiScaleBank`; the roadmap's `MultiScaleFeatureBank`): one bank per time scale s in
+{1, 2, 4, 8} whose rows are the mean of s consecutive normalised frames.  The prediction is pooled to each scale, looked up with
+the same search and blend, brought back to the frame rate by linear interpolation and the scales' tracks are mixed in with
+weights that sum to 1, at the one index rate: a coarse lookup sees 23, 46 or 93 ms of context instead of 11.6 ms.
+
+    python -m jatsr_amd.retrieval build --data-dir data_processed --out bank_ms.pt --max-frames 100000 --scales 1,2,4
+    python -m jatsr_amd.infer ... --index-bank bank_ms.pt --index-rate 0.4 [--index-scale-weights 2,1,1]
+
 Whether retrieval improves audio quality is not established here: nothing in this repository was run with trained weights.
 """
 from __future__ import annotations
@@ -28,7 +36,8 @@ import torch
 from . import _lib as L
 
 STAT_KEYS = ("hr_mean", "hr_std", "lr_mean", "lr_std")
-FORMAT = 1
+FORMAT = 1            # a single bank
+FORMAT_MS = 2         # a multi-scale bank: one single-bank dictionary per scale
 
 
 def frame_plan(lengths, max_frames):
@@ -95,6 +104,67 @@ def check_dist2_floor(dist2_floor):
     return f
 
 
+def check_scales(scales):
+    """The time scales of a multi-scale bank as a tuple: 1 to 4 of 1, 2, 4, 8, strictly ascending.  Takes a sequence of ints or
+    text such as "1,2,4"; ValueError otherwise."""
+    try:
+        if isinstance(scales, str):
+            scales = [int(v) for v in scales.split(",")]
+        out = tuple(scales)
+    except (TypeError, ValueError):
+        raise ValueError(f"scales {scales!r}: expected 1 to {L.BANK_MAX_SCALES} of {L.BANK_SCALES}, ascending")
+    if not 1 <= len(out) <= L.BANK_MAX_SCALES:
+        raise ValueError(f"scales {scales!r}: expected 1 to {L.BANK_MAX_SCALES} of them")
+    for v in out:
+        if isinstance(v, bool) or not isinstance(v, int) or v not in L.BANK_SCALES:
+            raise ValueError(f"scales {scales!r}: {v!r} is not one of {L.BANK_SCALES}")
+    if any(b <= a for a, b in zip(out, out[1:])):
+        raise ValueError(f"scales {scales!r} must ascend strictly")
+    return out
+
+
+def scales_arg(text):
+    """argparse type of --scales."""
+    try:
+        return check_scales(str(text))
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
+def check_scale_weights(weights, n):
+    """The n scale weights the mix runs with: positive finite numbers, normalised in fp64 to sum 1, each then rounded to fp32
+    (returned as Python floats holding those fp32 values).  None: all equal.  n = 1 gives exactly 1.0.  Takes a sequence or
+    text such as "2,1,1"; ValueError otherwise."""
+    n = int(n)
+    if weights is None:
+        weights = [1.0] * n
+    try:
+        if isinstance(weights, str):
+            weights = weights.split(",")
+        w = [float(v) for v in weights]
+    except (TypeError, ValueError):
+        raise ValueError(f"scale weights {weights!r}: expected {n} positive numbers")
+    if len(w) != n:
+        raise ValueError(f"scale weights {weights!r}: {len(w)} of them for {n} scales")
+    if not all(0.0 < v < float("inf") for v in w):
+        raise ValueError(f"scale weights {weights!r} must be positive and finite")
+    total = sum(w)
+    out = tuple(C.c_float(v / total).value for v in w)
+    if not all(0.0 < v < float("inf") for v in out) or not 0.0 < total < float("inf"):
+        raise ValueError(f"scale weights {weights!r} must be positive and finite after normalisation in fp32")
+    return out
+
+
+def scale_weights_arg(text):
+    """argparse type of --index-scale-weights and --scale-weights: the raw numbers; they are normalised against the bank."""
+    try:
+        w = [float(v) for v in str(text).split(",")]
+        check_scale_weights(w, len(w))
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+    return w
+
+
 def _stats_cpu(stats, channels):
     out = {}
     for k in STAT_KEYS:
@@ -126,6 +196,8 @@ def pack_state(keys, values, key, stats):
 
 def unpack_state(d):
     """Validate a bank dictionary -> (keys, values, key, channels, stats)."""
+    if isinstance(d, dict) and d.get("format") == FORMAT_MS:
+        raise ValueError("this is a multi-scale bank (format 2), not a single bank: load it with retrieval.load_bank")
     for k in ("keys", "values", "key", "channels", "stats"):
         if k not in d:
             raise KeyError(f"bank file lacks {k!r} (keys: {sorted(d.keys())})")
@@ -202,9 +274,13 @@ class LatentBank:
         return v
 
     # ---- building -------------------------------------------------------------------------------------------------------
-    def add(self, hr_latent, stats, lr_latent=None, first=0, stride=1, count=None):
+    def add(self, hr_latent, stats, lr_latent=None, first=0, stride=1, count=None, window=1):
         """Append frames first, first + stride, ... (`count` of them; default: to the end) of a [C, len] latent array,
-        fp16 or fp32, normalised with `stats`.  key == "lr" needs the LR array of the same shape: its frames are the keys."""
+        fp16 or fp32, normalised with `stats`.  key == "lr" needs the LR array of the same shape: its frames are the keys.
+        window in (2, 4, 8): each row is the mean of the `window` normalised frames that start there, fewer at the end of the
+        array (`jat_bank_add_pooled`, what a `MultiScaleBank` holds at that scale); window = 1 makes the call it always made."""
+        if window not in L.BANK_SCALES or isinstance(window, bool):
+            raise ValueError(f"window {window!r} is not one of {L.BANK_SCALES}")
         self._set_stats(stats)
         if (lr_latent is not None) != (self.key == "lr"):
             raise ValueError("lr_latent is given exactly when the bank's key is 'lr'")
@@ -222,12 +298,15 @@ class LatentBank:
         s = self._dev_stats
         with torch.cuda.device(self.device):
             if self.key == "lr":
-                rc = L.lib().jat_bank_add(self._h, L.ptr(lr), L.ptr(hr), int(dt == torch.float16), n, first, stride, int(count),
-                                          L.ptr(s["lr_mean"]), L.ptr(s["lr_std"]), L.ptr(s["hr_mean"]), L.ptr(s["hr_std"]),
-                                          L.stream_ptr())
+                src = (L.ptr(lr), L.ptr(hr), int(dt == torch.float16), n, first, stride, int(count))
+                st = (L.ptr(s["lr_mean"]), L.ptr(s["lr_std"]), L.ptr(s["hr_mean"]), L.ptr(s["hr_std"]), L.stream_ptr())
             else:
-                rc = L.lib().jat_bank_add(self._h, L.ptr(hr), None, int(dt == torch.float16), n, first, stride, int(count),
-                                          L.ptr(s["hr_mean"]), L.ptr(s["hr_std"]), None, None, L.stream_ptr())
+                src = (L.ptr(hr), None, int(dt == torch.float16), n, first, stride, int(count))
+                st = (L.ptr(s["hr_mean"]), L.ptr(s["hr_std"]), None, None, L.stream_ptr())
+            if window == 1:
+                rc = L.lib().jat_bank_add(self._h, *src, *st)
+            else:
+                rc = L.lib().jat_bank_add_pooled(self._h, *src, int(window), *st)
         L.check(rc)
         hr.record_stream(torch.cuda.current_stream(self.device))
         if lr is not None:
@@ -416,27 +495,276 @@ class LatentBank:
     def from_data_dir(cls, data_dir, stats, split="train", max_frames=100_000, key="hr", device="cuda"):
         """A bank over the `split` of a prepared data set (`python -m jatsr_amd.prepare`): the frames `frame_plan` names,
         files in sorted order, one file uploaded at a time."""
-        from .data import _load_fp16
-        folder = os.path.join(str(data_dir), split)
-        files = sorted(glob.glob(os.path.join(folder, "*.pt")))
-        if not files:
-            raise ValueError(f"No .pt files found in {folder}")
-        lengths, channels = [], None
-        for path in files:
-            hr, _ = _load_fp16(path)
-            if channels is None:
-                channels = int(hr.shape[0])
-            if hr.shape[0] != channels:
-                raise ValueError(f"{path}: {hr.shape[0]} channels, the files before it have {channels}")
-            lengths.append(int(hr.shape[1]))
-        plan = frame_plan(lengths, max_frames)
-        bank = cls(channels, sum(c for _, _, c in plan), key=key, device=device)
-        for path, (first, stride, count) in zip(files, plan):
-            if count == 0:
-                continue
-            hr, lr = _load_fp16(path)
-            bank.add(hr, stats, lr_latent=lr if key == "lr" else None, first=first, stride=stride, count=count)
-        return bank
+        files, channels, plan = _plan_data_dir(data_dir, split, max_frames)
+        return _fill_from_files(cls(channels, sum(c for _, _, c in plan), key=key, device=device), files, plan, stats)
+
+
+def _plan_data_dir(data_dir, split, max_frames):
+    """The sorted latent files of a split, their channel count and the `frame_plan` over their lengths."""
+    from .data import _load_fp16
+    folder = os.path.join(str(data_dir), split)
+    files = sorted(glob.glob(os.path.join(folder, "*.pt")))
+    if not files:
+        raise ValueError(f"No .pt files found in {folder}")
+    lengths, channels = [], None
+    for path in files:
+        hr, _ = _load_fp16(path)
+        if channels is None:
+            channels = int(hr.shape[0])
+        if hr.shape[0] != channels:
+            raise ValueError(f"{path}: {hr.shape[0]} channels, the files before it have {channels}")
+        lengths.append(int(hr.shape[1]))
+    return files, channels, frame_plan(lengths, max_frames)
+
+
+def _fill_from_files(bank, files, plan, stats):
+    """`bank.add` of every file's planned frames (a LatentBank, or a MultiScaleBank: the same window starts at every scale)."""
+    from .data import _load_fp16
+    for path, (first, stride, count) in zip(files, plan):
+        if count == 0:
+            continue
+        hr, lr = _load_fp16(path)
+        bank.add(hr, stats, lr_latent=lr if bank.key == "lr" else None, first=first, stride=stride, count=count)
+    return bank
+
+
+# ---- multi-scale retrieval (DESIGN §24; C ABI: include/jat_hip_ms.h) ------------------------------------------------------------
+def _frames(x, name="x"):
+    if x.dim() != 3 or x.dtype != torch.float32 or not x.is_cuda or min(x.shape) < 1:
+        raise ValueError(f"{name}: expected a CUDA fp32 [B, C, T] tensor, got {x.dtype} {tuple(x.shape)}")
+    return x.contiguous()
+
+
+def _stat_vec(v, channels, device):
+    if v is None:
+        return None
+    v = torch.as_tensor(v).to(device, torch.float32).contiguous().view(-1)
+    if v.numel() != channels:
+        raise ValueError(f"statistics vector of {v.numel()} entries, expected {channels}")
+    return v
+
+
+def pooled_length(T, scale):
+    """Frames of a [.., T] track pooled at `scale`: ceil(T / scale)."""
+    return -(-int(T) // int(scale))
+
+
+def pool_frames(x, scales, mean=None, std=None, outs=None):
+    """x fp32 [B, C, T] -> one [B, C, ceil(T / s)] tensor per scale s of `scales` (each of 2, 4, 8, ascending), in ONE launch
+    that reads x once: the mean of the s frames that start at t = 0, s, 2 s, ... (normalised first when mean / std are given;
+    ascending sequential adds, one division; the last window of a row may hold fewer frames and divides by their number).
+    outs: where to write (contiguous fp32 tensors of those shapes)."""
+    x = _frames(x)
+    scales = check_scales(scales)
+    if scales[0] == 1:
+        raise ValueError(f"scales {scales!r}: scale 1 is x itself and takes no buffer")
+    B, Cc, T = x.shape
+    if (mean is None) != (std is None):
+        raise ValueError("mean and std are given together or not at all")
+    mean, std = _stat_vec(mean, Cc, x.device), _stat_vec(std, Cc, x.device)
+    if outs is None:
+        outs = [torch.empty(B, Cc, pooled_length(T, s), dtype=torch.float32, device=x.device) for s in scales]
+    outs = list(outs)
+    for s, o in zip(scales, outs):
+        if tuple(o.shape) != (B, Cc, pooled_length(T, s)) or o.dtype != torch.float32 or not o.is_contiguous() or o.device != x.device:
+            raise ValueError(f"outs: scale {s} needs a contiguous fp32 [{B}, {Cc}, {pooled_length(T, s)}] tensor on {x.device}")
+    if len(outs) != len(scales):
+        raise ValueError(f"outs: {len(outs)} tensors for {len(scales)} scales")
+    n = len(scales)
+    with torch.cuda.device(x.device):
+        L.check(L.lib().jat_bank_pool_frames(L.ptr(x), L.ptr(mean), L.ptr(std), B, Cc, T, n, (C.c_int32 * n)(*scales),
+                                             (C.c_void_p * n)(*[o.data_ptr() for o in outs]), L.stream_ptr()))
+    return outs
+
+
+def mix_scales(x, scales, tracks, weights, index_rate, out=None):
+    """(1 - index_rate) x + index_rate sum_i weights[i] u_i with u_i the track of scale scales[i] ([B, C, ceil(T / s)] fp32)
+    brought to T frames by linear interpolation with half-pixel centres (F.interpolate(mode="linear", align_corners=False); a
+    track of scale 1 is taken as it is).  weights are used as given (`check_scale_weights` makes them sum to 1).  out: where
+    to write; may be x, may not be a track."""
+    x = _frames(x)
+    scales = check_scales(scales)
+    r = check_index_rate(index_rate)
+    B, Cc, T = x.shape
+    tracks, w = [t for t in tracks], [float(v) for v in weights]
+    n = len(scales)
+    if len(tracks) != n or len(w) != n:
+        raise ValueError(f"{len(tracks)} tracks and {len(w)} weights for {n} scales")
+    if not all(0.0 < C.c_float(v).value < float("inf") for v in w):
+        raise ValueError(f"scale weights {weights!r} must be positive and finite")
+    for s, t in zip(scales, tracks):
+        if tuple(t.shape) != (B, Cc, pooled_length(T, s)) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != x.device:
+            raise ValueError(f"tracks: scale {s} needs a contiguous fp32 [{B}, {Cc}, {pooled_length(T, s)}] tensor on {x.device}")
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
+        raise ValueError("mix_scales(out=...): out must be a contiguous fp32 tensor of x's shape")
+    with torch.cuda.device(x.device):
+        L.check(L.lib().jat_bank_mix_scales(L.ptr(x), n, (C.c_int32 * n)(*scales), (C.c_void_p * n)(*[t.data_ptr() for t in tracks]),
+                                            (C.c_float * n)(*w), r, L.ptr(out), B, Cc, T, L.stream_ptr()))
+    return out
+
+
+def pack_ms_state(scales, weights, banks):
+    """The dictionary a multi-scale bank file holds: format 2, the scales, the normalised fp32 weights and one single-bank
+    dictionary (`pack_state`) per scale, all of one key kind, channel count, row count and set of statistics."""
+    scales = check_scales(scales)
+    weights = tuple(float(v) for v in weights)       # as `check_scale_weights` returned them: not normalised a second time
+    if len(weights) != len(scales) or not all(0.0 < v < float("inf") and v == C.c_float(v).value for v in weights) or \
+            abs(sum(weights) - 1.0) > 1e-6:
+        raise ValueError(f"scale weights {weights!r}: expected {len(scales)} positive fp32 values that sum to 1")
+    banks = [dict(b) for b in banks]
+    if len(banks) != len(scales):
+        raise ValueError(f"{len(banks)} banks for {len(scales)} scales")
+    first = unpack_state(banks[0])
+    for b in banks:
+        keys, _, key, channels, stats = unpack_state(b)
+        if (key, channels, int(keys.shape[0])) != (first[2], first[3], int(first[0].shape[0])) or not same_stats(stats, first[4]):
+            raise ValueError("the banks of a multi-scale bank share key kind, channels, row count and statistics")
+    return {"format": FORMAT_MS, "scales": list(scales), "weights": list(weights), "banks": banks}
+
+
+def unpack_ms_state(d):
+    """Validate a multi-scale bank dictionary -> (scales, weights, [single-bank dictionaries])."""
+    if not isinstance(d, dict) or d.get("format") != FORMAT_MS:
+        raise ValueError("not a multi-scale bank (format 2); a single bank loads with LatentBank.load or retrieval.load_bank")
+    for k in ("scales", "weights", "banks"):
+        if k not in d:
+            raise KeyError(f"multi-scale bank file lacks {k!r} (keys: {sorted(d.keys())})")
+    st = pack_ms_state(d["scales"], d["weights"], d["banks"])
+    return tuple(st["scales"]), tuple(st["weights"]), st["banks"]
+
+
+class MultiScaleBank:
+    """One `LatentBank` per time scale (the roadmap's MultiScaleFeatureBank): the bank of scale s holds, for the same window
+    starts, the mean of s consecutive normalised frames.  `retrieve` pools the prediction to each scale, looks it up with the
+    single bank's search and blend, interpolates each retrieved track back to the frame rate and mixes
+        y = (1 - index_rate) x + index_rate sum_i weights[i] u_i,        weights summing to 1.
+    scales = (1,) is a `LatentBank`, bit for bit."""
+
+    def __init__(self, channels, capacity, scales=(1, 2, 4), key="hr", weights=None, device="cuda"):
+        self.scales = check_scales(scales)
+        self.weights = check_scale_weights(weights, len(self.scales))
+        self._adopt([LatentBank(channels, capacity, key=key, device=device) for _ in self.scales])
+
+    def _adopt(self, banks):
+        self.banks = list(banks)
+        b = self.banks[0]
+        self.channels, self.capacity, self.key, self.device = b.channels, b.capacity, b.key, b.device
+
+    @staticmethod
+    def roadmap_rate(r, n):
+        """The index rate at which this family, with equal weights, is the roadmap's (x + r sum_s up_s) / (1 + n r)."""
+        return n * r / (1.0 + n * r)
+
+    @property
+    def stats(self):
+        return self.banks[0].stats
+
+    def check_stats(self, stats):
+        self.banks[0].check_stats(stats)
+
+    def set_weights(self, weights):
+        """Other scale weights (positive numbers, normalised to sum 1) than the ones the bank was built or loaded with."""
+        self.weights = check_scale_weights(weights, len(self.scales))
+
+    def __len__(self):
+        """Rows per scale."""
+        return len(self.banks[0])
+
+    def clear(self):
+        for b in self.banks:
+            b.clear()
+
+    def add(self, hr_latent, stats, lr_latent=None, first=0, stride=1, count=None):
+        """`LatentBank.add` at every scale: the windows of scale s start at the same frames first, first + stride, ... and
+        hold s frames (fewer at the end of the array).  The arrays are uploaded once."""
+        dt = torch.float16 if hr_latent.dtype == torch.float16 else torch.float32
+        hr = hr_latent.to(self.device, dt)
+        lr = None if lr_latent is None else lr_latent.to(self.device, dt)
+        n = 0
+        for s, b in zip(self.scales, self.banks):
+            n = b.add(hr, stats, lr_latent=lr, first=first, stride=stride, count=count, window=s)
+        return n
+
+    def retrieve(self, x, index_rate, stats=None, query=None, k=1, dist2_floor=1e-6, neighbours=False):
+        """`LatentBank.retrieve` over every scale, on a de-normalised HR latent x [B, C, T]: one `pool_frames` launch pools the
+        query (x under the HR statistics, or the LR latent `query` under the LR statistics for key == "lr") to the scales
+        above 1; each scale's bank is searched (`search`, or `search_topk` for k > 1, the same k at every scale) and its
+        de-normalised HR rows are written over that scale's pooled buffer by `blend` / `blend_topk` at rate 1; one `mix_scales`
+        launch interpolates and mixes.  Nothing waits for the device.  neighbours: (y, [idx per scale], [dist2 per scale])."""
+        r = check_index_rate(index_rate)
+        k = check_index_k(k)
+        check_dist2_floor(dist2_floor)
+        if self.scales == (1,):                      # the single bank itself: the calls and the bits of LatentBank.retrieve
+            out = self.banks[0].retrieve(x, r, stats=stats, query=query, k=k, dist2_floor=dist2_floor, neighbours=neighbours)
+            return (out[0], [out[1]], [out[2]]) if neighbours else out
+        if stats is not None:
+            self.check_stats(stats)
+        elif self.stats is None:
+            raise ValueError("the bank holds no statistics yet (nothing was added)")
+        s = self.banks[0]._dev_stats
+        x = self.banks[0]._x(x)
+        if self.key == "lr":
+            if query is None:
+                raise ValueError("a bank keyed by LR frames needs the LR latent as `query`")
+            if query.shape != x.shape:
+                raise ValueError(f"query {tuple(query.shape)} does not match x {tuple(x.shape)}")
+            q, mean, std = self.banks[0]._x(query.to(self.device, torch.float32), "query"), s["lr_mean"], s["lr_std"]
+        else:
+            q, mean, std = x, s["hr_mean"], s["hr_std"]
+        coarse = [v for v in self.scales if v > 1]
+        pooled = dict(zip(coarse, pool_frames(q, coarse, mean, std)))
+        tracks, idxs, dists = [], [], []
+        for scale, bank in zip(self.scales, self.banks):
+            # scale 1: the query with its statistics, as the single bank does, and a fresh track; above: the pooled, already
+            # normalised query, and the track written over it (0 * pooled + 1 * v, the blend at rate 1)
+            qs, m, sd, base, out = (q, mean, std, x, None) if scale == 1 else (pooled[scale], None, None, pooled[scale], pooled[scale])
+            if k == 1:
+                idx, dist2 = bank.search(qs, m, sd)
+                tracks.append(bank.blend(base, idx, 1.0, s["hr_mean"], s["hr_std"], out=out))
+            else:
+                idx, dist2 = bank.search_topk(qs, k, m, sd)
+                tracks.append(bank.blend_topk(base, idx, dist2, 1.0, s["hr_mean"], s["hr_std"], out=out, dist2_floor=dist2_floor))
+            idxs.append(idx)
+            dists.append(dist2)
+        y = mix_scales(x, self.scales, tracks, self.weights, r)
+        return (y, idxs, dists) if neighbours else y
+
+    # ---- files ----------------------------------------------------------------------------------------------------------
+    def state(self):
+        return pack_ms_state(self.scales, self.weights, [b.state() for b in self.banks])
+
+    def save(self, path):
+        torch.save(self.state(), path)
+
+    @classmethod
+    def from_state(cls, d, device="cuda", capacity=None):
+        scales, weights, banks = unpack_ms_state(d)
+        self = cls.__new__(cls)
+        self.scales, self.weights = scales, weights
+        self._adopt([LatentBank.from_state(b, device=device, capacity=capacity) for b in banks])
+        return self
+
+    @classmethod
+    def load(cls, path, device="cuda"):
+        return cls.from_state(torch.load(path, map_location="cpu", weights_only=False), device=device)
+
+    @classmethod
+    def from_data_dir(cls, data_dir, stats, split="train", max_frames=100_000, key="hr", device="cuda", scales=(1, 2, 4),
+                      weights=None):
+        """`LatentBank.from_data_dir` at every scale: ONE `frame_plan` names the window starts of all scales."""
+        files, channels, plan = _plan_data_dir(data_dir, split, max_frames)
+        bank = cls(channels, sum(c for _, _, c in plan), scales=scales, key=key, weights=weights, device=device)
+        return _fill_from_files(bank, files, plan, stats)
+
+
+def load_bank(path, device="cuda"):
+    """A bank file of either format -> `LatentBank` (format 1) or `MultiScaleBank` (format 2)."""
+    d = torch.load(path, map_location="cpu", weights_only=False)
+    if isinstance(d, dict) and d.get("format") == FORMAT_MS:
+        return MultiScaleBank.from_state(d, device=device)
+    return LatentBank.from_state(d, device=device)
 
 
 def _device_view(address, shape, dtype, device, owner):
@@ -466,6 +794,11 @@ def build_parser():
     b.add_argument("--max-frames", type=int, default=100_000, help="upper bound on the rows of the bank")
     b.add_argument("--key", default="hr", choices=["hr", "lr"], help="what a frame is looked up by")
     b.add_argument("--device", default="cuda")
+    b.add_argument("--scales", type=scales_arg, default=None, metavar="S1,S2,...",
+                   help="write a multi-scale bank (format 2): one bank per time scale, each of 1, 2, 4, 8, ascending, e.g. 1,2,4 "
+                        "(default: a single bank, the file as it always was)")
+    b.add_argument("--scale-weights", type=scale_weights_arg, default=None, metavar="W1,W2,...",
+                   help="with --scales: the share of each scale's track in the mix, normalised to sum 1 (default: equal)")
     return p
 
 
@@ -478,10 +811,21 @@ def main(argv=None):
         raise SystemExit(f"No .pt files found in {folder}")
     channels = int(torch.load(files[0], map_location="cpu", mmap=True, weights_only=False)["hr_latent"].shape[0])
     stats = jio.load_stats(args.stats_file or os.path.join(args.data_dir, "global_stats_separated.json"), channels=channels)
-    bank = LatentBank.from_data_dir(args.data_dir, stats, split=args.split, max_frames=args.max_frames, key=args.key,
-                                    device=args.device)
+    if args.scale_weights is not None and args.scales is None:
+        raise SystemExit("--scale-weights needs --scales")
+    if args.scales is None:
+        bank = LatentBank.from_data_dir(args.data_dir, stats, split=args.split, max_frames=args.max_frames, key=args.key,
+                                        device=args.device)
+    else:
+        try:
+            weights = check_scale_weights(args.scale_weights, len(args.scales))
+        except ValueError as e:
+            raise SystemExit(f"--scale-weights: {e}")
+        bank = MultiScaleBank.from_data_dir(args.data_dir, stats, split=args.split, max_frames=args.max_frames, key=args.key,
+                                            device=args.device, scales=args.scales, weights=args.scale_weights)
     bank.save(args.out)
-    print(f"bank of {len(bank)} x {bank.channels} fp16 rows (key={bank.key}) from {len(files)} files -> {args.out}")
+    print(f"bank of {len(bank)} x {bank.channels} fp16 rows (key={bank.key}) from {len(files)} files" +
+          (f", scales {list(args.scales)} with weights {[round(w, 6) for w in weights]}" if args.scales else "") + f" -> {args.out}")
     return args.out
 
 
