@@ -205,6 +205,14 @@ MS_SIGNATURES = {
     "jat_bank_mix_scales": (C.c_int, [_VP, _I32, C.POINTER(_I32), C.POINTER(_VP), C.POINTER(_F32), _F32, _VP, _I32, _I32, _I32,
                                       _VP]),
 }
+# name -> (restype, argtypes); every symbol include/jat_hip_harm.h declares (harmonic analysis, template, comparison)
+HARM_SIGNATURES = {
+    "jat_harmonic_analyze": (C.c_int, [_VP, _I32, _I64, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP, _VP, _VP]),
+    "jat_harmonic_synth_workspace_bytes": (C.c_int, [_I32, _I64, _I32, C.POINTER(_SZ)]),
+    "jat_harmonic_synth": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I64, _I32, _I32, _VP, _VP, _VP, _SZ, _VP]),
+    "jat_harmonic_compare": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, C.c_double, C.c_double, _VP, _VP]),
+}
+HARM_MAX = 128               # JAT_HARM_MAX
 BANK_MAX_SCALES = 4          # JAT_BANK_MAX_SCALES
 BANK_SCALES = (1, 2, 4, 8)   # what a scale may be
 MONITOR_WORK_BYTES = 49152   # JAT_MONITOR_WORK_BYTES
@@ -233,7 +241,7 @@ def lib():
         # before it finds no device at the first kernel launch ("no ROCm-capable device is detected")
         import torch  # noqa: F401
         h = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(MS_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(MS_SIGNATURES.items()) + list(HARM_SIGNATURES.items()):
             if not hasattr(h, name) and os.environ.get("JAT_LIB_ALLOW_MISSING"):
                 continue      # A/B against an OLDER build through JAT_LIB_PATH (tools/sampler_ab.py): it lacks the newest entry points
             fn = getattr(h, name)

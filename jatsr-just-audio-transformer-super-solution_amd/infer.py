@@ -17,6 +17,9 @@ per-channel normalisation (:381-394).  Differences, all outside the hot path's s
   * `--f0-metrics` (valid where `--metrics` is) adds an `"f0"` entry to that JSON: how far the YIN pitch tracks of the decoded
     generated and LR audio agree with the HR audio's (jatsr_amd.pitch); without `--metrics` the JSON holds that entry alone;
     `--f0-method pyin` takes the tracks with pYIN instead and records `"method": "pyin"` inside that entry;
+  * `--harmonic-metrics` (valid where `--metrics` is) adds a `"harmonic"` entry to that JSON: the amplitudes of the harmonics of
+    the HR audio's pitch track in the decoded generated and LR audio against the HR audio's, split at the LR audio's detected
+    band limit into kept and regenerated harmonics (jatsr_amd.harmonic); the track is taken with `--f0-method`;
   * `--lf-replace [HZ]` (with `--dac-weights`) also writes `{stem}_generated{suffix}_lf.wav`: the decoded audio with its
     band below HZ (bare flag: the detected band limit of the source) replaced by the source's own (jatsr_amd.splice,
     csrc/splice.hip).  The source is the 44.1 kHz waveform that was encoded (`--input-audio`), the whole file taken through
@@ -85,6 +88,10 @@ def build_parser():
                         "{stem}_metrics.json (valid where --metrics is; jatsr_amd.pitch)")
     p.add_argument("--f0-method", choices=("yin", "pyin"), default="yin",
                    help="with --f0-metrics: the tracker; pyin adds \"method\": \"pyin\" to the \"f0\" entry")
+    p.add_argument("--harmonic-metrics", action="store_true",
+                   help="harmonic amplitudes of the decoded generated and LR audio at the HR ground truth's pitch track, below and "
+                        "above the LR audio's band limit: a \"harmonic\" entry in {stem}_metrics.json (valid where --metrics is; "
+                        "jatsr_amd.harmonic)")
     p.add_argument("--lf-replace", type=str, nargs="?", const="auto", default=None, metavar="HZ",
                    help="also write {stem}_generated_lf.wav: the decoded audio with the band below HZ (bare flag: the "
                         "detected band limit of the source) taken from the source waveform (needs --dac-weights).  With a "
@@ -124,6 +131,9 @@ def run(args):
     f0_metrics = getattr(args, "f0_metrics", False)
     if f0_metrics and (not args.dac_weights or (args.input_audio and args.simulate_lr is None)):
         raise SystemExit("--f0-metrics needs --dac-weights and an HR ground truth (--simulate-lr, or a latent file with hr_latent)")
+    harmonic_metrics = getattr(args, "harmonic_metrics", False)
+    if harmonic_metrics and (not args.dac_weights or (args.input_audio and args.simulate_lr is None)):
+        raise SystemExit("--harmonic-metrics needs --dac-weights and an HR ground truth (--simulate-lr, or a latent file with hr_latent)")
     index_bank = getattr(args, "index_bank", None)
     index_rate = index_rate_arg(getattr(args, "index_rate", 0.4)) if index_bank else 0.0
     index_k = index_k_arg(getattr(args, "index_k", 1)) if index_bank else 1
@@ -147,6 +157,8 @@ def run(args):
         raise SystemExit(f"--metrics: {path} holds no hr_latent, so there is no ground truth to compare with")
     if f0_metrics and hr is None:
         raise SystemExit(f"--f0-metrics: {path} holds no hr_latent, so there is no ground truth to compare with")
+    if harmonic_metrics and hr is None:
+        raise SystemExit(f"--harmonic-metrics: {path} holds no hr_latent, so there is no ground truth to compare with")
     C = model.input_channels
     stats = jio.load_stats(args.stats_file, channels=C, device=device)
 
@@ -274,7 +286,8 @@ def decode_to_wav(args, gen, hr, lr, total, stem, suffix, device, codec=None, so
     outs.append((f"{stem}_lr_input.wav", lr[None, :, :total].to(device)))
     decoded = []
     f0_metrics = getattr(args, "f0_metrics", False)
-    keep = args.metrics or f0_metrics or args.lf_replace is not None
+    harmonic_metrics = getattr(args, "harmonic_metrics", False)
+    keep = args.metrics or f0_metrics or harmonic_metrics or args.lf_replace is not None
     for name, z in outs:
         audio = codec.decode(z)                      # [1, 1, frames * 512]
         jio.write_wav_float32(os.path.join(args.output_dir, name), audio[0, 0], codec.sample_rate)
@@ -291,7 +304,7 @@ def decode_to_wav(args, gen, hr, lr, total, stem, suffix, device, codec=None, so
         jio.write_wav_float32(os.path.join(args.output_dir, name), spliced, codec.sample_rate)
         print(f"low band below {hz:.1f} Hz ({'detected' if args.lf_replace == 'auto' else 'given'}) taken from the "
               f"{'decoded LR latent' if source is None else 'input waveform'} -> {name}")
-    if args.metrics or f0_metrics:
+    if args.metrics or f0_metrics or harmonic_metrics:
         import json
 
         generated, hr_gt, lr_input = decoded
@@ -313,6 +326,11 @@ def decode_to_wav(args, gen, hr, lr, total, stem, suffix, device, codec=None, so
             if spliced is not None:
                 rep["f0"]["generated_lf"] = pitch.f0_metrics(spliced, hr_gt, sr=codec.sample_rate, **f0_kw)["generated"]
             rep["f0"].update(f0_kw)
+        if harmonic_metrics:
+            from . import harmonic
+            rep["harmonic"] = harmonic.harmonic_metrics(generated, hr_gt, lr_input, sr=codec.sample_rate,
+                                                        method=getattr(args, "f0_method", "yin"))
+            print(harmonic.format_report(rep["harmonic"]))
         out = os.path.join(args.output_dir, f"{stem}_metrics{suffix}.json")
         with open(out, "w") as f:
             json.dump(rep, f, indent=2)

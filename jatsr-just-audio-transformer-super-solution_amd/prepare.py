@@ -17,6 +17,10 @@ the GPU (csrc/resample.hip, csrc/dac_enc.hip).  Differences:
     44.1 kHz with hop 512 over the whole file, so frame t is centred on the first sample of latent frame t): `hr_f0` fp32 [T]
     and `hr_voiced` uint8 [T] beside the latents.  Without the flag the files are what they were.  `--f0-method pyin` takes
     the track with pYIN (f0 quantised to 10-cent bins, 0 where unvoiced) and also stores `hr_voiced_prob` fp32 [T].
+  * `--f0 --harmonics H` also stores `hr_harmonics` fp16 [T, H]: the amplitudes of the first H harmonics of that track in the
+    HR recording (jatsr_amd.harmonic.analyze at the stored `hr_f0` / `hr_voiced`), 0 where the track does not reach.  With
+    `--f0-method pyin` the table is taken at the refined track (YIN's f0 within 50 cents of pYIN's bin), not at the quantised
+    `hr_f0`.
 
     python -m jatsr_amd.prepare --source-dir wavs --output-dir data --dac-weights dac.pth
 """
@@ -77,20 +81,26 @@ def to_codec_rate(x, codec):
     return resample(x, HIGH_SR, codec.sample_rate, CODEC_LOWPASS_WIDTH, CODEC_ROLLOFF)
 
 
-def hr_pitch_track(x, sr: int, codec, frames: int, method: str = "yin"):
+def hr_codec_signal(x, sr: int, codec):
+    """The peak-normalised mono recording x [L] at `sr` -> the whole recording at the codec's rate [L'], as the tracks and the
+    harmonic table read it"""
+    from .resample import resample
+    hr48 = resample(x[None], sr, HIGH_SR) if sr != HIGH_SR else x[None]
+    return to_codec_rate(hr48, codec)[0].contiguous()
+
+
+def hr_pitch_track(x, sr: int, codec, frames: int, method: str = "yin", signal=None):
     """The peak-normalised mono recording x [L] at `sr` -> (hr_f0 fp32 [frames], hr_voiced uint8 [frames]) on the GPU: YIN
     (jatsr_amd.pitch defaults, hop 512) on the whole recording at the codec's rate, cut to the latent frame count; frames the
     track does not reach are f0 = 0 and unvoiced.  method "pyin": the pYIN track instead, and a third value, hr_voiced_prob
-    fp32 [frames] (0 where the track does not reach)."""
+    fp32 [frames] (0 where the track does not reach).  `signal`: hr_codec_signal(x, sr, codec) where the caller has it."""
     import torch
 
     from .pitch import pyin, yin
-    from .resample import resample
     if method not in ("yin", "pyin"):
         raise ValueError(f"prepare: f0 method must be 'yin' or 'pyin', got {method!r}")
-    hr48 = resample(x[None], sr, HIGH_SR) if sr != HIGH_SR else x[None]
-    f0, voiced, third = (yin if method == "yin" else pyin)(to_codec_rate(hr48, codec)[0].contiguous(), sr=codec.sample_rate,
-                                                           hop_length=512)
+    y = hr_codec_signal(x, sr, codec) if signal is None else signal
+    f0, voiced, third = (yin if method == "yin" else pyin)(y, sr=codec.sample_rate, hop_length=512)
     n = min(frames, f0.shape[0])
     hr_f0 = torch.zeros(frames, dtype=torch.float32, device=f0.device)
     hr_voiced = torch.zeros(frames, dtype=torch.uint8, device=f0.device)
@@ -102,12 +112,37 @@ def hr_pitch_track(x, sr: int, codec, frames: int, method: str = "yin"):
     return hr_f0, hr_voiced, hr_prob
 
 
+def hr_harmonic_table(signal, codec, hr_f0, hr_voiced, n_harmonics: int, method: str = "yin"):
+    """hr_codec_signal's recording and the track of hr_pitch_track [frames] -> hr_harmonics fp16 [frames, n_harmonics] on the
+    GPU: the harmonic amplitudes (jatsr_amd.harmonic.analyze, hop 512 at the codec's rate) at that track; rows the recording
+    does not reach are 0.  method "pyin": the stored hr_f0 is quantised to 10-cent bins, which misplaces high harmonics by more
+    than a bin, so the table is taken at the refined track of jatsr_amd.harmonic (refine_f0: YIN's f0 of the same frame where it
+    lies within 50 cents of the bin); hr_f0 itself stays pYIN's."""
+    import torch
+
+    from .harmonic import analyze, refine_f0
+    y = signal
+    frames, have = hr_f0.shape[0], 1 + y.shape[0] // 512
+    f0 = torch.zeros(have, dtype=torch.float32, device=y.device)
+    voiced = torch.zeros(have, dtype=torch.uint8, device=y.device)
+    n = min(frames, have)
+    f0[:n], voiced[:n] = hr_f0[:n], hr_voiced[:n]
+    if method == "pyin":
+        from .pitch import yin
+        f0 = refine_f0(f0, voiced, yin(y, sr=codec.sample_rate, hop_length=512)[0])
+    amp, _ = analyze(y, f0, voiced, n_harmonics=n_harmonics, sr=codec.sample_rate, hop_length=512)
+    out = torch.zeros(frames, amp.shape[1], dtype=torch.float16, device=y.device)
+    out[:n] = amp[:n].to(torch.float16)
+    return out
+
+
 def prepare_audio(audio, sr: int, codec, low_sr: int = 16000, batch: int = 8, device="cuda", timings: dict | None = None,
-                  f0: bool = False, f0_method: str = "yin"):
+                  f0: bool = False, f0_method: str = "yin", harmonics: int = 0):
     """One recording -> dict(hr_latent fp32 [1024, T], lr_latent, sum fp64 [2048], sq_sum, count, metadata), tensors on the
     GPU; None for a recording shorter than 1 s.  `audio`: [L] or [channels, L], array or tensor; `codec`: a DacCodec with an
     encoder.  sum / sq_sum: HR channels first, then LR, over the values rounded to fp16; count: T (frames of each).
-    With `f0` also hr_f0 fp32 [T] and hr_voiced uint8 [T] (hr_pitch_track), and with f0_method "pyin" hr_voiced_prob fp32 [T]."""
+    With `f0` also hr_f0 fp32 [T] and hr_voiced uint8 [T] (hr_pitch_track), and with f0_method "pyin" hr_voiced_prob fp32 [T];
+    with `f0` and `harmonics` = H > 0 also hr_harmonics fp16 [T, H] (hr_harmonic_table)."""
     import torch
 
     from . import _lib as L
@@ -117,6 +152,8 @@ def prepare_audio(audio, sr: int, codec, low_sr: int = 16000, batch: int = 8, de
         raise ValueError(f"prepare_audio: sample rates must be positive integers, got {sr!r}, {low_sr!r}")
     if batch < 1:
         raise ValueError(f"prepare_audio: batch {batch} must be >= 1")
+    if harmonics and not f0:
+        raise ValueError("prepare_audio: harmonics needs f0 (the table is taken at the stored track)")
     sr, low_sr = int(sr), int(low_sr)
     x = torch.as_tensor(audio)
     if not x.is_cuda:
@@ -172,11 +209,15 @@ def prepare_audio(audio, sr: int, codec, low_sr: int = 16000, batch: int = 8, de
     out = {"hr_latent": hr, "lr_latent": lr, "sum": s, "sq_sum": q, "count": hr.shape[-1],
            "metadata": {"duration": duration, "sr": sr, "chunks": len(chunks), "frames": hr.shape[-1],
                         "hop_48k": hop48, "trim_frames": trim, "valid_frames": valid}}
+    sig_kw = {"signal": hr_codec_signal(x, sr, codec)} if f0 and harmonics else {}     # resampled once for the track and the table
     if f0 and f0_method == "yin":
-        out["hr_f0"], out["hr_voiced"] = clock.run("f0", lambda: hr_pitch_track(x, sr, codec, hr.shape[-1]))
+        out["hr_f0"], out["hr_voiced"] = clock.run("f0", lambda: hr_pitch_track(x, sr, codec, hr.shape[-1], **sig_kw))
     elif f0:
         out["hr_f0"], out["hr_voiced"], out["hr_voiced_prob"] = clock.run(
-            "f0", lambda: hr_pitch_track(x, sr, codec, hr.shape[-1], f0_method))
+            "f0", lambda: hr_pitch_track(x, sr, codec, hr.shape[-1], f0_method, **sig_kw))
+    if f0 and harmonics:
+        out["hr_harmonics"] = clock.run("harmonics", lambda: hr_harmonic_table(sig_kw["signal"], codec, out["hr_f0"],
+                                                                               out["hr_voiced"], harmonics, f0_method))
     return out
 
 
@@ -207,6 +248,8 @@ def build_parser():
                    help="also store hr_f0 / hr_voiced: a YIN pitch track of the HR recording, one value per latent frame")
     p.add_argument("--f0-method", choices=("yin", "pyin"), default="yin",
                    help="with --f0: the tracker; pyin also stores hr_voiced_prob fp32 [T]")
+    p.add_argument("--harmonics", type=int, default=0, metavar="H",
+                   help="with --f0: also store hr_harmonics fp16 [T, H], the amplitudes of the track's first H harmonics (1..128)")
     p.add_argument("--device", default="cuda", help="an AMD GPU; there is no CPU path")
     return p
 
@@ -251,15 +294,19 @@ def run(args):
         x, sr = jio.read_wav(path)
         want_f0 = getattr(args, "f0", False)
         f0_method = getattr(args, "f0_method", "yin")
+        harmonics = getattr(args, "harmonics", 0)
+        if harmonics and not want_f0:
+            raise SystemExit("--harmonics needs --f0")
         res = prepare_audio(x, sr, codec, low_sr=args.low_sr, batch=args.batch, device=args.device, f0=want_f0,
-                            **({"f0_method": f0_method} if f0_method != "yin" else {}))
+                            **({"f0_method": f0_method} if f0_method != "yin" else {}),
+                            **({"harmonics": harmonics} if harmonics else {}))
         if res is None:
             print(f"skipped {path}: shorter than {MIN_SECONDS:g} s")
             report["skipped"].append(path)
             continue
         jio.save_latent_file(out_path, hr_latent=res["hr_latent"], lr_latent=res["lr_latent"],
                              metadata={"name": stem, "path": path, "duration": res["metadata"]["duration"], "sr": sr},
-                             **({k: res[k].cpu() for k in ("hr_f0", "hr_voiced", "hr_voiced_prob") if k in res} if want_f0 else {}))
+                             **({k: res[k].cpu() for k in ("hr_f0", "hr_voiced", "hr_voiced_prob", "hr_harmonics") if k in res} if want_f0 else {}))
         s, q = res["sum"].cpu(), res["sq_sum"].cpu()
         total_sum = s if total_sum is None else total_sum + s
         total_sq = q if total_sq is None else total_sq + q
