@@ -357,6 +357,13 @@ int jat_k_weight_grad_plan(int32_t out, int32_t in, int32_t tokens, int32_t* til
 /* GQA attention on bf16 q[M,Hq*64], k[M,Hkv*64], vt[B,Hkv,64,Npad] -> o[M,Hq*64]; softmax(q k^T / 8) v. */
 int jat_k_attention(const uint16_t* q, const uint16_t* k, const uint16_t* vt, uint16_t* o, int32_t B,
                     int32_t N, int32_t Hq, int32_t Hkv, int32_t Npad, void* stream);
+/* jat_k_attention with per-sample key counts, as Sampler.run(lengths=...) runs a short chunk in a bucket of longer ones: lens
+ * [B] int32 on the device; every query row of sample b (the rows past lens[b] included: the next layer reads them) attends to
+ * the keys < lens[b] alone, whatever k and vt hold beyond them.  Same launch as jat_k_attention (jat_k_attention_route).
+ * Precondition: lens[b] >= 1 (a sample without a key has no softmax; the sampler refuses such a length); values above N act
+ * as N.  JAT_E_INVALID for a NULL lens. */
+int jat_k_attention_lens(const uint16_t* q, const uint16_t* k, const uint16_t* vt, uint16_t* o, const int32_t* lens, int32_t B,
+                         int32_t N, int32_t Hq, int32_t Hkv, int32_t Npad, void* stream);
 /* The kernel jat_k_attention / jat_k_attention_train, the forward, the sampler and the trainer launch for N tokens per sample with
  * V padded to Npad keys, for a call with (training forward) or without an lse output and with or without dropout: group = 1: the
  * group kernel (K / V staged once per KV head, N <= 128); group = 0: the streaming kernel with qt * 16 queries per wave (qt 1

@@ -99,6 +99,7 @@ SIGNATURES = {
     "jat_k_weight_grad_ex": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _VP, _SZ, _I32, _VP]),
     "jat_k_weight_grad_plan": (C.c_int, [_I32, _I32, _I32, _VP, _VP]),
     "jat_k_attention": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP]),
+    "jat_k_attention_lens": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _I32, _VP]),
     "jat_k_attention_route": (C.c_int, [_I32, _I32, _I32, _I32, _VP, _VP, _VP]),
     "jat_k_recon_loss": (C.c_int, [_VP, _VP, _VP, _VP, _I64, C.c_double, _F32, _VP, _SZ, _VP]),
     "jat_k_cast_bf16": (C.c_int, [_VP, _VP, _I64, _VP]),

@@ -1170,6 +1170,17 @@ extern "C" int jat_k_attention(const uint16_t* q, const uint16_t* k, const uint1
   KCHK(launch_attention(a, (hipStream_t)stream));
   return JAT_OK;
 }
+// jat_k_attention with per-sample key counts (AttnArgs::lens, as Sampler.run(lengths=...) sets it): same launch_attention
+extern "C" int jat_k_attention_lens(const uint16_t* q, const uint16_t* k, const uint16_t* vt, uint16_t* o, const int32_t* lens,
+                                    int32_t B, int32_t N, int32_t Hq, int32_t Hkv, int32_t Npad, void* stream) {
+  if (!lens) return fail(JAT_E_INVALID, "null lens");
+  AttnArgs a{};
+  a.q = q; a.k = k; a.vt = vt; a.o = o; a.ldq = (int64_t)Hq * 64; a.ldk = (int64_t)Hkv * 64; a.ldo = (int64_t)Hq * 64;
+  a.B = B; a.N = N; a.Hq = Hq; a.Hkv = Hkv; a.npad = Npad;
+  a.scale_log2e = kAttnScaleLog2e; a.lens = lens;
+  KCHK(launch_attention(a, (hipStream_t)stream));
+  return JAT_OK;
+}
 // which kernel launch_attention starts for this shape (attention.hip); host only, launches nothing
 extern "C" int jat_k_attention_route(int32_t N, int32_t Npad, int32_t has_lse, int32_t has_dropout, int32_t* group, int32_t* qt,
                                      int32_t* kvb) {

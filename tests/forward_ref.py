@@ -106,6 +106,24 @@ def linspace_f32(a, b, n):
                      for i in range(n)], np.float32)
 
 
+# ---- the attention kernels' operation on its own ---------------------------------------------------------------------------
+def attention_heads(q, k, v, B, N, Hq, Hkv, lens=None):
+    """softmax(q k^T / 8) v with GQA head sharing in fp64, on operands as the kernels get them: q [B*N, Hq*64], k, v [B*N, Hkv*64]
+    -> [B*N, Hq*64].  lens [B] (optional): the scores of the keys >= lens[b] are -inf for EVERY query row of sample b, the rows
+    past lens[b] included (the next layer reads them); lens[b] >= 1."""
+    g = Hq // Hkv
+    Q = q.to(F64).view(B, N, Hq, HEAD_DIM).transpose(1, 2)
+    K = k.to(F64).view(B, N, Hkv, HEAD_DIM).transpose(1, 2).repeat_interleave(g, dim=1)
+    V = v.to(F64).view(B, N, Hkv, HEAD_DIM).transpose(1, 2).repeat_interleave(g, dim=1)
+    S = Q @ K.transpose(-1, -2) / math.sqrt(HEAD_DIM)
+    if lens is not None:
+        lens = torch.as_tensor(lens, device=S.device).view(B, 1, 1, 1)
+        assert bool((lens >= 1).all())
+        S = S.masked_fill(torch.arange(N, device=S.device).view(1, 1, 1, N) >= lens, float("-inf"))
+    O = torch.softmax(S, -1) @ V
+    return O.transpose(1, 2).reshape(B * N, Hq * HEAD_DIM)
+
+
 # ---- the fused attention of one KV group ----------------------------------------------------------------------------------
 def attention_group(q, k, v, rnd, inv_freq=None):
     """RoPE + softmax(q k^T / 8) v of ONE KV group from the projections as they leave the accumulator: q [B, N, G*64] (the G

@@ -111,6 +111,45 @@ def test_fused_attention_of_one_kv_group_is_the_oracles_attention(name):
     assert R.rel_l2(a, b) < EXACT
 
 
+def test_attention_reference_with_key_lengths_is_the_plain_reference_on_the_valid_tokens():
+    """`attention_heads(lens=...)`, the reference of tests/test_gpu_kernels.py::test_attention_lens_*: for every sample the rows
+    < lens[b] equal the plain reference evaluated on that sample's first lens[b] tokens alone, whatever the keys beyond hold
+    (here: K scaled by 8 and V = 100, as the GPU tests poison them); all-full lens and lens above N equal the plain reference;
+    the rows past lens[b] are finite and are the softmax over the valid keys of their own queries; lens[b] = 1 gives V's row 0 in
+    every query row.  The plain reference itself is pinned against a direct evaluation of single heads."""
+    B, N, Hq, Hkv = 4, 23, 6, 2
+    lens = [23, 13, 1, 22]
+    q, k, v = (R.t64(recipe.gaussian("lens_" + n, (B * N, h * 64), 9)) * s for n, h, s in (("q", Hq, 1.5), ("k", Hkv, 1.5), ("v", Hkv, 1.0)))
+    plain = R.attention_heads(q, k, v, B, N, Hq, Hkv)
+    # the plain reference itself, head by head
+    for b, h in ((0, 0), (3, 5), (1, 2)):
+        rows = slice(b * N, (b + 1) * N)
+        kv = h // (Hq // Hkv)
+        s = q[rows, h * 64:(h + 1) * 64] @ k[rows, kv * 64:(kv + 1) * 64].T / 8.0
+        assert R.rel_l2(plain[rows, h * 64:(h + 1) * 64], torch.softmax(s, -1) @ v[rows, kv * 64:(kv + 1) * 64]) < EXACT
+    kp, vp = k.clone().view(B, N, -1), v.clone().view(B, N, -1)
+    for b, n in enumerate(lens):
+        kp[b, n:] *= 8
+        vp[b, n:] = 100.0
+    kp, vp = kp.view(B * N, -1), vp.view(B * N, -1)
+    got = R.attention_heads(q, kp, vp, B, N, Hq, Hkv, lens=lens)
+    assert bool(torch.isfinite(got).all())
+    for b, n in enumerate(lens):
+        rows = slice(b * N, b * N + n)
+        alone = R.attention_heads(q[rows], k[rows], v[rows], 1, n, Hq, Hkv)
+        assert R.rel_l2(got[rows], alone) < EXACT, b
+        # a row past lens[b]: its own query over the valid keys
+        if n < N:
+            h, kv, r = 4, 4 // (Hq // Hkv), b * N + N - 1
+            s = q[r, h * 64:(h + 1) * 64] @ k[rows, kv * 64:(kv + 1) * 64].T / 8.0
+            assert R.rel_l2(got[r, h * 64:(h + 1) * 64], torch.softmax(s, -1) @ v[rows, kv * 64:(kv + 1) * 64]) < EXACT
+    assert torch.equal(got[2 * N:3 * N], v.view(B, N, Hkv, 64)[2, 0].repeat_interleave(Hq // Hkv, 0).reshape(1, -1).expand(N, -1))
+    # the poison is seen without the mask
+    assert R.rel_l2(R.attention_heads(q, kp, vp, B, N, Hq, Hkv), plain) > 1.0
+    for full in ([N] * B, [N + 7] * B, torch.tensor([N, N + 1, N, 2 * N])):
+        assert torch.equal(R.attention_heads(q, k, v, B, N, Hq, Hkv, lens=full), plain)
+
+
 def test_cfg_euler_step_and_sampler_are_the_oracles():
     cfg, sd, orc = setup("micro")
     C = cfg["input_channels"]

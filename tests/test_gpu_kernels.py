@@ -394,14 +394,9 @@ def test_retired_gemm_variants_are_rejected():
         assert rc != 0, v
 
 
-def _attention_ref(q, k, v, B, N, Hq, Hkv):
-    g = Hq // Hkv
-    Q = q.double().view(B, N, Hq, 64).transpose(1, 2)
-    K = k.double().view(B, N, Hkv, 64).transpose(1, 2).repeat_interleave(g, dim=1)
-    V = v.double().view(B, N, Hkv, 64).transpose(1, 2).repeat_interleave(g, dim=1)
-    S = Q @ K.transpose(-1, -2) / 8.0
-    O = torch.softmax(S, -1) @ V
-    return O.transpose(1, 2).reshape(B * N, Hq * 64)
+def _attention_ref(q, k, v, B, N, Hq, Hkv, lens=None):
+    """tests/forward_ref.py `attention_heads` (fp64; with lens: the keys >= lens[b] at -inf for every query row of sample b)"""
+    return R.attention_heads(q, k, v, B, N, Hq, Hkv, lens)
 
 
 @pytest.mark.parametrize("B,N,Hq,Hkv", [(2, 128, 20, 4), (1, 345, 20, 4), (3, 6, 4, 2), (1, 1024, 8, 4), (2, 70, 4, 4)])
@@ -438,6 +433,162 @@ def test_attention_spiky_rows():
     ref = _attention_ref(qf, kf, vf, B, N, Hq, Hkv)
     assert rel(o, ref) < 6e-3
     assert (o.double() - ref).abs().max() < 2e-2 * float(ref.abs().max())
+
+
+# ---- per-sample key counts (AttnArgs::lens through jat_k_attention_lens) -----------------------------------------------------
+# How Sampler.run(lengths=...) and sample_long run a short chunk in a bucket of longer ones.  attn_fwd_kernel: Nb = min(lens[b], N),
+# the key-block count from Nb, the mask only where key0 + KVB > Nb; attn_group_kernel: Nk = min(lens[b], N), the mask only where
+# Nk < 128.  name -> (N, Npad, Hq, Hkv, lens, (group, qt, kvb) under the default switches, the lens < N whose stand-alone run takes
+# the same route under the default switches).  Heads as few as the head loops allow: the streaming kernel has none (one block per
+# q head; (4, 2) keeps the GQA sharing), the group kernel walks the G = Hq / Hkv heads of a KV head in pairs: G = 3 (odd), 1, 2.
+# In "stream345" 344 / 321 / 320 / 192 / 65 / 64 / 63 sit on either side of a 64-key block edge; "block23" is the one shape the
+# sampler-level lengths tests reach.
+_GROUP_LENS = [100, 99, 65, 64, 33, 17, 1]
+LENS_BUCKETS = {
+    "stream345": (345, 384, 4, 2, [345, 344, 321, 320, 192, 130, 65, 64, 63, 1], (0, 1, 64), [344, 321, 320, 192, 130]),
+    "group100_g3": (100, 128, 6, 2, _GROUP_LENS, (1, 1, 64), _GROUP_LENS[1:]),
+    "group100_g1": (100, 128, 2, 2, _GROUP_LENS, (1, 1, 64), _GROUP_LENS[1:]),
+    "group100_g2": (100, 128, 4, 2, _GROUP_LENS, (1, 1, 64), _GROUP_LENS[1:]),
+    "group128": (128, 128, 4, 2, [128, 127, 96], (1, 1, 64), [127, 96]),
+    "block23": (23, 64, 4, 2, [23, 13, 1], (0, 1, 64), [13, 1]),
+}
+DEFAULT_SWITCHES = not any(os.environ.get(k) for k in ("JAT_ATTN_GROUP", "JAT_ATTN_QT", "JAT_ATTN_KVB"))
+_lens_cache = {}
+
+
+def _attn_route(N, npad):
+    g, qt, kvb = C.c_int32(-1), C.c_int32(-1), C.c_int32(-1)
+    L.check(L.lib().jat_k_attention_route(N, npad, 0, 0, C.byref(g), C.byref(qt), C.byref(kvb)))
+    return (g.value, qt.value, kvb.value)
+
+
+def _to_vt(v, B, N, Hkv, npad):
+    """v [B*N, Hkv*64] -> V^T [B, Hkv, 64, npad], zero from N to npad"""
+    vt = torch.zeros(B, Hkv, 64, npad, dtype=OP, device=v.device)
+    vt[:, :, :, :N] = v.view(B, N, Hkv, 64).permute(0, 2, 3, 1)
+    return vt
+
+
+def _run_attention(q, k, vt, B, N, Hq, Hkv, npad, lens=None):
+    """jat_k_attention (lens None) or jat_k_attention_lens into a NaN-filled output"""
+    o = torch.full((B * N, Hq * 64), float("nan"), device=q.device).to(OP)
+    if lens is None:
+        L.check(L.lib().jat_k_attention(L.ptr(q), L.ptr(k), L.ptr(vt), L.ptr(o), B, N, Hq, Hkv, npad, L.stream_ptr()))
+    else:
+        assert lens.dtype == torch.int32 and lens.numel() == B and int(lens.min()) >= 1
+        L.check(L.lib().jat_k_attention_lens(L.ptr(q), L.ptr(k), L.ptr(vt), L.ptr(o), L.ptr(lens), B, N, Hq, Hkv, npad,
+                                             L.stream_ptr()))
+    torch.cuda.synchronize()
+    return o
+
+
+def _past_lens(k, v, B, N, lens, fill):
+    """copies of k and v [B*N, Hkv*64] with the rows at keys >= lens[b] replaced: fill None -> K times 8 (exact in OP) and V = 100,
+    so that ONE leaked key takes most of the softmax weight of about half of the query rows (its logit has eight times the
+    spread of a real one) and moves them by tens of units; fill = a seed -> other finite values"""
+    kp, vp = k.clone().view(B, N, -1), v.clone().view(B, N, -1)
+    for b, n in enumerate(lens):
+        if n < N:
+            if fill is None:
+                kp[b, n:] = kp[b, n:] * 8
+                vp[b, n:] = 100.0
+            else:
+                kp[b, n:] = gen(tuple(kp[b, n:].shape), fill + b, 6.0).to(OP)
+                vp[b, n:] = (gen(tuple(vp[b, n:].shape), fill + 50 + b, 20.0) - 37.0).to(OP)
+    return kp.view(B * N, -1), vp.view(B * N, -1)
+
+
+def _lens_case(name):
+    """Inputs as test_attention draws them (q, k at scale 1.5, v at 1), poisoned past lens[b]; the kernel's output; the fp64 reference.
+    Built once per bucket and left unchanged."""
+    if name not in _lens_cache:
+        N, npad, Hq, Hkv, lens, _, _ = LENS_BUCKETS[name]
+        B = len(lens)
+        q, k, v = (gen((B * N, h * 64), s, sc).to(OP) for h, s, sc in ((Hq, 40, 1.5), (Hkv, 41, 1.5), (Hkv, 42, 1.0)))
+        kp, vp = _past_lens(k, v, B, N, lens, None)
+        vt = _to_vt(vp, B, N, Hkv, npad)
+        lens_t = torch.tensor(lens, dtype=torch.int32, device=q.device)
+        o = _run_attention(q, kp, vt, B, N, Hq, Hkv, npad, lens_t)
+        ref = _attention_ref(q, kp, vp, B, N, Hq, Hkv, lens_t)
+        assert bool(torch.isfinite(kp).all()) and bool(torch.isfinite(vt).all()) and float(vt[..., N:].abs().max() if npad > N else 0) == 0
+        _lens_cache[name] = dict(q=q, k=k, v=v, kp=kp, vp=vp, vt=vt, lens_t=lens_t, o=o, ref=ref)
+    return _lens_cache[name]
+
+
+@pytest.mark.parametrize("name", list(LENS_BUCKETS))
+def test_attention_lens_vs_fp64(name):
+    """jat_k_attention_lens against the masked fp64 reference, with test_attention's gates (P and the output are rounded to OP:
+    rel < 6e-3, max-abs < 2e-2 max|ref|) applied to every sample on its own, over all N query rows (the rows past lens[b] too: the
+    next layer reads them), every element finite; a sample with lens[b] = 1 is V's row 0 in every query row, bit for bit (P = 1,
+    l = 1).  The leak the poison makes: with the mask of one sample off by a key, that sample's rel is of order 1."""
+    N, npad, Hq, Hkv, lens, route, _ = LENS_BUCKETS[name]
+    if DEFAULT_SWITCHES:
+        assert _attn_route(N, npad) == route
+    c = _lens_case(name)
+    o, ref = c["o"], c["ref"]
+    assert bool(torch.isfinite(o).all())
+    for b, n in enumerate(lens):
+        ob, rb = o[b * N:(b + 1) * N], ref[b * N:(b + 1) * N]
+        r, ma, top = rel(ob, rb), float((ob.double() - rb).abs().max()), float(rb.abs().max())
+        print(f"{name} route {_attn_route(N, npad)} lens {n}: rel {r:.3e}, max-abs {ma:.3e} of max|ref| {top:.3e}")
+        assert r < 6e-3 and ma < 2e-2 * top, (name, n)
+        if n == 1:
+            row0 = c["v"].view(len(lens), N, Hkv, 64)[b, 0].repeat_interleave(Hq // Hkv, 0).reshape(1, Hq * 64)
+            assert torch.equal(ob, row0.expand(N, -1)), (name, b)
+
+
+@pytest.mark.parametrize("name", list(LENS_BUCKETS))
+def test_attention_lens_full_lengths_are_the_plain_call(name):
+    """lens[b] = N everywhere, and lens[b] = N + 7 (values above N act as N): the bits of jat_k_attention on the same buffers."""
+    N, npad, Hq, Hkv, lens, _, _ = LENS_BUCKETS[name]
+    B = len(lens)
+    c = _lens_case(name)
+    vt = _to_vt(c["v"], B, N, Hkv, npad)
+    plain = _run_attention(c["q"], c["k"], vt, B, N, Hq, Hkv, npad)
+    assert bool(torch.isfinite(plain).all())
+    for full in (N, N + 7):
+        lens_t = torch.full((B,), full, dtype=torch.int32, device=plain.device)
+        assert torch.equal(_run_attention(c["q"], c["k"], vt, B, N, Hq, Hkv, npad, lens_t), plain), (name, full)
+
+
+@pytest.mark.parametrize("name", list(LENS_BUCKETS))
+def test_attention_lens_rows_equal_the_stand_alone_run(name):
+    """"Same key blocks as a stand-alone run of Nb tokens" (attn_fwd_kernel): the rows < lens[b] of sample b are the bits of
+    jat_k_attention on that sample's first lens[b] tokens alone (same Npad, V^T zero beyond lens[b]) — wherever
+    jat_k_attention_route gives (N, Npad) and (lens[b], Npad) the same kernel; elsewhere only the fp64 gate applies.  Under the
+    default switches the lengths of LENS_BUCKETS' last column must take this branch, so that the condition cannot skip them."""
+    N, npad, Hq, Hkv, lens, _, must = LENS_BUCKETS[name]
+    c = _lens_case(name)
+    here, taken = _attn_route(N, npad), []
+    for b, n in enumerate(lens):
+        if n >= N or _attn_route(n, npad) != here:
+            continue
+        rows = slice(b * N, b * N + n)
+        vt = _to_vt(c["v"][rows], 1, n, Hkv, npad)
+        alone = _run_attention(c["q"][rows], c["k"][rows], vt, 1, n, Hq, Hkv, npad)
+        assert torch.equal(c["o"][rows], alone), (name, n)
+        taken.append(n)
+    print(f"{name} route {here}: bitwise against the stand-alone run at lens {taken}")
+    if DEFAULT_SWITCHES:
+        assert taken == must, (taken, must)
+    assert taken, name           # under every switch setting of tests/test_gpu_widths.py some length keeps the route
+
+
+@pytest.mark.parametrize("name", ["stream345", "group100_g3"])
+def test_attention_lens_ignores_what_lies_past_lens(name):
+    """The K rows and V columns at keys >= lens[b] refilled with other finite values: every row of every sample keeps its bits."""
+    N, npad, Hq, Hkv, lens, _, _ = LENS_BUCKETS[name]
+    B = len(lens)
+    c = _lens_case(name)
+    kp, vp = _past_lens(c["k"], c["v"], B, N, lens, 900)
+    assert not torch.equal(kp, c["kp"]) and not torch.equal(vp, c["vp"])
+    again = _run_attention(c["q"], kp, _to_vt(vp, B, N, Hkv, npad), B, N, Hq, Hkv, npad, c["lens_t"])
+    assert torch.equal(again, c["o"])
+
+
+def test_attention_lens_refuses_a_null_lens():
+    z = torch.zeros(64, 128, dtype=OP, device=dev())
+    assert L.lib().jat_k_attention_lens(L.ptr(z), L.ptr(z), L.ptr(z), L.ptr(z), None, 1, 64, 2, 2, 64, L.stream_ptr()) == L.JAT_E_INVALID
 
 
 def _rope_pair_rows(w):

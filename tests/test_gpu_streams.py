@@ -525,6 +525,20 @@ def _k_attention():
     return Case(inputs, call, outputs={"o": inputs["q"]})
 
 
+@case("k_attention_lens", ["jat_k_attention_lens"])
+def _k_attention_lens():
+    """a short second sample; the decoy lengths are in range (1 ... N) and differ from the true ones in both samples"""
+    B, N, Hq, Hkv = 2, 130, 4, 2          # three key blocks, the short sample ends in the second
+    inputs, npad = _attn_inputs(B, N, Hq, Hkv, 45)
+    inputs["lens"] = torch.tensor([N, 70], dtype=torch.int32, device="cuda")
+    decoys = {"lens": torch.tensor([3, N - 1], dtype=torch.int32, device="cuda")}
+
+    def call(_, i, o):
+        ck(L.lib().jat_k_attention_lens(vp(i["q"]), vp(i["k"]), vp(i["vt"]), vp(o["o"]), vp(i["lens"]), B, N, Hq, Hkv, npad,
+                                        L.stream_ptr()))
+    return Case(inputs, call, outputs={"o": inputs["q"]}, decoys=decoys)
+
+
 def _k_attention_train(split):
     B, N, Hq, Hkv, p, seed, site = 2, 130, 4, 2, 0.1, 0x1234567, 3
     inputs, npad = _attn_inputs(B, N, Hq, Hkv, 50)

@@ -25,11 +25,12 @@ Measured on MI355X ("Other widths"), error / E0 whole tensor; wor
     time_embed                1.3e-7 ... 1.4e-7 (gate 1e-5)
     training step             worst gradient at 0.31 ... 0.40 of its tolerance, always a q or k projection
 F stayed 1.5 and the training gates the constants of tests/test_gpu_train.py.  Wall time: 26 s without the children, the children
-7.4 / 6.5 / 6.9 s (160 per-kernel tests each); tests/test_gpu_forward_paths.py takes 17 s for scale.
+7.4 / 8.4 / 9.2 s (181 per-kernel tests each, 21 of them test_attention_lens_*); tests/test_gpu_forward_paths.py takes 17 s for scale.
 """
 import ctypes as C
 import math
 import os
+import re
 import subprocess
 import sys
 
@@ -321,6 +322,9 @@ CHILDREN = {
 }
 # the attention and norm tests of test_gpu_kernels.py, the attention training forward / backward of test_gpu_train_kernels.py
 # without the two 64-bit-index tests, the AdamW kernels (test_gpu_train_kernels.py, test_gpu_ema.py)
+# what CHILD_TESTS selects: 160 tests, and the 21 test_attention_lens_* of tests/test_gpu_kernels.py (per-sample key counts on the
+# switched instantiations); pinned so that a renamed test cannot leave the children unseen
+CHILD_COUNT = 181
 CHILD_TESTS = ("(test_attention or test_norm_modulate or test_norm_no_modulation or test_adamw or test_fused_adamw_ema_kernel) "
                "and not 64bit")
 CHILD_CODE = """
@@ -355,3 +359,4 @@ def test_switched_kernels_in_a_child_process(child):
     print(tail)
     assert out.returncode == 0 and "routes as intended" in out.stdout and " passed" in out.stdout, tail
     assert "skipped" not in out.stdout.splitlines()[-1] and "no tests ran" not in out.stdout, tail
+    assert re.search(r"\b%d passed\b" % CHILD_COUNT, out.stdout.splitlines()[-1]), tail

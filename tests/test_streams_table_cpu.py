@@ -31,7 +31,7 @@ def missing(entries, covered, exempt):
 
 def test_the_parser_finds_the_stream_taking_entries():
     e = stream_entries(header())
-    assert len(e) == len(set(e)) and len(e) == 74, len(e)
+    assert len(e) == len(set(e)) and len(e) == 75, len(e)
     for name in ("jat_forward", "jat_k_dac_rvq", "jat_yin", "jat_bank_blend_topk", "jat_trainer_create", "jat_f0_compare"):
         assert name in e, name
     for name in ("jat_bank_create", "jat_bank_clear", "jat_solver_plan", "jat_k_gemm_plan", "jat_model_workspace_bytes"):
