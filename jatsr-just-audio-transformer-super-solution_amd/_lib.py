@@ -213,6 +213,15 @@ HARM_SIGNATURES = {
     "jat_harmonic_synth": (C.c_int, [_VP, _VP, _VP, _I32, _I32, _I32, _I64, _I32, _I32, _VP, _VP, _VP, _SZ, _VP]),
     "jat_harmonic_compare": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, C.c_double, C.c_double, _VP, _VP]),
 }
+# name -> (restype, argtypes); every symbol include/jat_hip_km.h declares (k-means compaction of a retrieval bank)
+KM_SIGNATURES = {
+    "jat_bank_assign_workspace_bytes": (C.c_int, [_VP, _VP, _I64, C.POINTER(_SZ)]),
+    "jat_bank_assign": (C.c_int, [_VP, _I64, _I64, _VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "jat_bank_cluster_update_workspace_bytes": (C.c_int, [_VP, _I32, C.POINTER(_SZ)]),
+    "jat_bank_cluster_update": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "jat_bank_sum_dist2": (C.c_int, [_VP, _I64, _VP, _VP]),
+}
+KM_MAX_POOL = 1 << 22        # JAT_KM_MAX_POOL
 HARM_MAX = 128               # JAT_HARM_MAX
 BANK_MAX_SCALES = 4          # JAT_BANK_MAX_SCALES
 BANK_SCALES = (1, 2, 4, 8)   # what a scale may be
@@ -242,7 +251,8 @@ def lib():
         # before it finds no device at the first kernel launch ("no ROCm-capable device is detected")
         import torch  # noqa: F401
         h = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(MS_SIGNATURES.items()) + list(HARM_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(MS_SIGNATURES.items()) + list(HARM_SIGNATURES.items()) + \
+                list(KM_SIGNATURES.items()):
             if not hasattr(h, name) and os.environ.get("JAT_LIB_ALLOW_MISSING"):
                 continue      # A/B against an OLDER build through JAT_LIB_PATH (tools/sampler_ab.py): it lacks the newest entry points
             fn = getattr(h, name)

@@ -4,12 +4,7 @@
 #include "jat_retrieval_kernels.h"
 #include "../../include/jat_hip_ms.h"
 
-struct jat_bank {
-  int channels = 0, capacity = 0, size = 0;
-  bool paired = false;
-  uint16_t *keys = nullptr, *values = nullptr;   // [capacity, channels] fp16; values == keys unless paired
-  float* norms = nullptr;                        // |key row|^2, capacity rounded up to whole key tiles
-};
+#include "jat_bank.h"   // struct jat_bank, shared with jat_retrieval_km.cpp
 
 namespace {
 

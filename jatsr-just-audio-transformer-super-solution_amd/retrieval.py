@@ -22,6 +22,11 @@ weights that sum to 1, at the one index rate: a coarse lookup sees 23, 46 or 93 
     python -m jatsr_amd.retrieval build --data-dir data_processed --out bank_ms.pt --max-frames 100000 --scales 1,2,4
     python -m jatsr_amd.infer ... --index-bank bank_ms.pt --index-rate 0.4 [--index-scale-weights 2,1,1]
 
+k-means compaction (`kmeans`, `--clusters K`; what RVC's index training does with a large feature set): a pool of
+up to 2^22 frames is clustered on the GPU and the K centroids are stored as the bank, a bank file of the existing format:
+
+    python -m jatsr_amd.retrieval build --data-dir data_processed --out bank_km.pt --clusters 10000 [--pool-frames 1000000]
+
 Whether retrieval improves audio quality is not established here: nothing in this repository was run with trained weights.
 """
 from __future__ import annotations
@@ -468,6 +473,53 @@ class LatentBank:
             y = self.blend_topk(x, idx, dist2, index_rate, s["hr_mean"], s["hr_std"], dist2_floor=dist2_floor)
         return (y, idx, dist2) if neighbours else y
 
+    # ---- k-means compaction (C ABI: include/jat_hip_km.h) --------------------------------------------------------
+    def assign(self, pool, first=0, count=None, idx=None, changed=None):
+        """`self` holds the centroids: the nearest centroid of pool rows first .. first + count - 1 (default: to the end of
+        the pool) -> (idx int32 [count], dist2 fp32 [count]), the lowest index on equal distance.  idx: the buffer to
+        overwrite (default: a fresh one filled with -1); changed: an int32 tensor of one element that is incremented by the
+        number of entries of idx that differ from what the buffer held."""
+        if not isinstance(pool, LatentBank):
+            raise ValueError("assign: the pool is a LatentBank")
+        first = int(first)
+        count = len(pool) - first if count is None else int(count)
+        if count < 1 or first < 0:
+            raise ValueError(f"assign: rows {first} .. +{count} of a pool of {len(pool)}")
+        if idx is None:
+            idx = torch.full((count,), -1, dtype=torch.int32, device=self.device)
+        elif idx.shape != (count,) or idx.dtype != torch.int32 or idx.device != self.device or not idx.is_contiguous():
+            raise ValueError(f"idx: expected a contiguous int32 [{count}] tensor on {self.device}")
+        if changed is not None and (changed.numel() != 1 or changed.dtype != torch.int32 or changed.device != self.device):
+            raise ValueError(f"changed: expected an int32 tensor of one element on {self.device}")
+        dist2 = torch.empty(count, dtype=torch.float32, device=self.device)
+        need = C.c_size_t()
+        L.check(L.lib().jat_bank_assign_workspace_bytes(pool._h, self._h, count, C.byref(need)))
+        if self._work is None or self._work.numel() < need.value:
+            self._work = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            L.check(L.lib().jat_bank_assign(pool._h, first, count, self._h, L.ptr(idx), L.ptr(dist2), L.ptr(changed),
+                                            L.ptr(self._work), self._work.numel(), L.stream_ptr()))
+        return idx, dist2
+
+    def cluster_update(self, pool, idx, check=True):
+        """`self` holds the centroids: every centroid with members moves to the mean of the pool rows idx [N] assigns to it
+        (exact integer sums, one rounding per conversion; an empty cluster keeps its row) -> counts int32 [K].  An idx entry
+        outside [0, K) is skipped on the device; check: wait for the counts and raise ValueError unless they sum to N."""
+        N, K = len(pool), len(self)
+        if idx.shape != (N,) or idx.dtype != torch.int32 or idx.device != self.device or not idx.is_contiguous():
+            raise ValueError(f"idx: expected a contiguous int32 [{N}] tensor on {self.device}")
+        counts = torch.empty(max(K, 1), dtype=torch.int32, device=self.device)
+        need = C.c_size_t()
+        L.check(L.lib().jat_bank_cluster_update_workspace_bytes(pool._h, K, C.byref(need)))
+        work = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            L.check(L.lib().jat_bank_cluster_update(pool._h, L.ptr(idx), self._h, L.ptr(counts), L.ptr(work), work.numel(),
+                                                    L.stream_ptr()))
+        work.record_stream(torch.cuda.current_stream(self.device))
+        if check and int(counts.sum()) != N:
+            raise ValueError(f"cluster_update: {N - int(counts.sum())} entries of idx lie outside [0, {K}); they were skipped")
+        return counts
+
     # ---- files ----------------------------------------------------------------------------------------------------------
     def state(self):
         keys, _ = self.rows("keys")
@@ -492,11 +544,20 @@ class LatentBank:
         return cls.from_state(torch.load(path, map_location="cpu", weights_only=False), device=device)
 
     @classmethod
-    def from_data_dir(cls, data_dir, stats, split="train", max_frames=100_000, key="hr", device="cuda"):
+    def from_data_dir(cls, data_dir, stats, split="train", max_frames=100_000, key="hr", device="cuda", clusters=None,
+                      pool_frames=None, kmeans_iters=10):
         """A bank over the `split` of a prepared data set (`python -m jatsr_amd.prepare`): the frames `frame_plan` names,
-        files in sorted order, one file uploaded at a time."""
-        files, channels, plan = _plan_data_dir(data_dir, split, max_frames)
-        return _fill_from_files(cls(channels, sum(c for _, _, c in plan), key=key, device=device), files, plan, stats)
+        files in sorted order, one file uploaded at a time.  clusters=K: those frames (`pool_frames` of them at most, default
+        min(total, 2^22); `max_frames` is not used) are only the pool, and the bank holds the centroids `kmeans` leaves
+        (DESIGN §26); the report is kept as `bank.kmeans_report`."""
+        if clusters is None:
+            files, channels, plan = _plan_data_dir(data_dir, split, max_frames)
+            return _fill_from_files(cls(channels, sum(c for _, _, c in plan), key=key, device=device), files, plan, stats)
+        files, channels, plan = _plan_data_dir(data_dir, split, check_pool_frames(pool_frames))
+        pool = _fill_from_files(cls(channels, sum(c for _, _, c in plan), key=key, device=device), files, plan, stats)
+        bank, report = kmeans(pool, clusters, iters=kmeans_iters)
+        bank.kmeans_report = report
+        return bank
 
 
 def _plan_data_dir(data_dir, split, max_frames):
@@ -752,11 +813,107 @@ class MultiScaleBank:
 
     @classmethod
     def from_data_dir(cls, data_dir, stats, split="train", max_frames=100_000, key="hr", device="cuda", scales=(1, 2, 4),
-                      weights=None):
-        """`LatentBank.from_data_dir` at every scale: ONE `frame_plan` names the window starts of all scales."""
-        files, channels, plan = _plan_data_dir(data_dir, split, max_frames)
-        bank = cls(channels, sum(c for _, _, c in plan), scales=scales, key=key, weights=weights, device=device)
-        return _fill_from_files(bank, files, plan, stats)
+                      weights=None, clusters=None, pool_frames=None, kmeans_iters=10):
+        """`LatentBank.from_data_dir` at every scale: ONE `frame_plan` names the window starts of all scales.  clusters=K: the
+        pooled rows of each scale are clustered on their own with the same K (`kmeans`).  The banks of a
+        multi-scale file share their row count, so an empty cluster is NOT dropped here: it stays at the pool row it started
+        from.  The reports are kept as `bank.kmeans_report`, one per scale."""
+        if clusters is None:
+            files, channels, plan = _plan_data_dir(data_dir, split, max_frames)
+            bank = cls(channels, sum(c for _, _, c in plan), scales=scales, key=key, weights=weights, device=device)
+            return _fill_from_files(bank, files, plan, stats)
+        files, channels, plan = _plan_data_dir(data_dir, split, check_pool_frames(pool_frames))
+        pool = cls(channels, sum(c for _, _, c in plan), scales=scales, key=key, weights=weights, device=device)
+        _fill_from_files(pool, files, plan, stats)
+        done = [kmeans(b, clusters, iters=kmeans_iters, drop_empty=False) for b in pool.banks]
+        self = cls.__new__(cls)
+        self.scales, self.weights = pool.scales, pool.weights
+        self._adopt([b for b, _ in done])
+        self.kmeans_report = [r for _, r in done]
+        return self
+
+
+def check_clusters(n_clusters):
+    """The number of clusters as a positive int; ValueError otherwise."""
+    if isinstance(n_clusters, bool) or not isinstance(n_clusters, int) or n_clusters < 1:
+        raise ValueError(f"clusters {n_clusters!r} must be a positive integer")
+    return n_clusters
+
+
+def check_pool_frames(pool_frames):
+    """The upper bound on the rows of a k-means pool: None is 2^22 (JAT_KM_MAX_POOL), else an int in 1..2^22."""
+    if pool_frames is None:
+        return L.KM_MAX_POOL
+    if isinstance(pool_frames, bool) or not isinstance(pool_frames, int) or not 1 <= pool_frames <= L.KM_MAX_POOL:
+        raise ValueError(f"pool_frames {pool_frames!r} outside 1..{L.KM_MAX_POOL}")
+    return pool_frames
+
+
+def seed_positions(n_rows, n_clusters):
+    """The pool rows the centroids start from: i N // K for i < K, K distinct positions for K <= N."""
+    return [i * int(n_rows) // int(n_clusters) for i in range(int(n_clusters))]
+
+
+def sum_dist2(dist2):
+    """The sum of an fp32 device tensor in fp64 in one fixed order (`jat_bank_sum_dist2`) -> a device tensor of one double."""
+    if dist2.dtype != torch.float32 or not dist2.is_cuda or dist2.numel() < 1:
+        raise ValueError(f"dist2: expected a non-empty CUDA fp32 tensor, got {dist2.dtype} {tuple(dist2.shape)}")
+    dist2 = dist2.contiguous()
+    out = torch.empty(1, dtype=torch.float64, device=dist2.device)
+    with torch.cuda.device(dist2.device):
+        L.check(L.lib().jat_bank_sum_dist2(L.ptr(dist2), dist2.numel(), L.ptr(out), L.stream_ptr()))
+    return out
+
+
+def _bank_of_rows(like, keys, values, capacity=None):
+    bank = LatentBank(like.channels, capacity or int(keys.shape[0]), key=like.key, device=like.device)
+    if like.stats is not None:
+        bank._set_stats(like.stats)
+    bank.load_rows(keys, values)
+    return bank
+
+
+def kmeans(pool, n_clusters, iters=10, drop_empty=True):
+    """Lloyd's k-means over the rows of `pool` (a LatentBank of 1..2^22 rows) on the GPU -> (LatentBank of the centroids, report).
+
+    The centroids start from pool rows i N // K; an iteration is `assign` (nearest centroid, the lowest index on equal
+    distance) then `cluster_update` (every centroid to the exactly summed mean of its members; an empty cluster stays where it
+    is).  It stops after `iters` iterations, or before the update of an iteration whose assignment changed nothing.  With
+    drop_empty the clusters without members (duplicated seed rows end so) are left out, the rest in ascending order.  The
+    result is an ordinary bank of the pool's key kind and statistics.  report: requested and kept K, N, iterations, the inertia
+    (sum of squared distances, fp64) and the number of changed assignments per iteration, min / median / max cluster size."""
+    if not isinstance(pool, LatentBank):
+        raise ValueError("kmeans: the pool is a LatentBank")
+    K, N = check_clusters(n_clusters), len(pool)
+    if isinstance(iters, bool) or not isinstance(iters, int) or iters < 1:
+        raise ValueError(f"iters {iters!r} must be a positive integer")
+    if N > L.KM_MAX_POOL:
+        raise ValueError(f"kmeans: a pool of {N} rows exceeds {L.KM_MAX_POOL}")
+    if K > N:
+        raise ValueError(f"kmeans: {K} clusters for a pool of {N} rows")
+    paired = pool.key == "lr"
+    seeds = torch.tensor(seed_positions(N, K), dtype=torch.int64, device=pool.device)
+    cent = _bank_of_rows(pool, pool.rows("keys")[0][seeds], pool.rows("values")[0][seeds] if paired else None)
+    idx = torch.full((N,), -1, dtype=torch.int32, device=pool.device)
+    changed = torch.zeros(1, dtype=torch.int32, device=pool.device)
+    inertia, moved, counts = [], [], None
+    for _ in range(iters):
+        changed.zero_()
+        _, dist2 = cent.assign(pool, idx=idx, changed=changed)
+        inertia.append(float(sum_dist2(dist2)))
+        moved.append(int(changed))
+        if moved[-1] == 0:
+            break                       # the update of the same assignment is the one already made
+        counts = cent.cluster_update(pool, idx)
+    n = counts.cpu().tolist()
+    keep = [i for i in range(K) if n[i] > 0] if drop_empty else list(range(K))
+    if len(keep) < K:
+        pick = torch.tensor(keep, dtype=torch.int64, device=pool.device)
+        cent = _bank_of_rows(pool, cent.rows("keys")[0][pick], cent.rows("values")[0][pick] if paired else None)
+    kept = sorted(n[i] for i in keep)
+    report = {"clusters": K, "kept": len(keep), "rows": N, "iterations": len(moved), "inertia": inertia, "changed": moved,
+              "size_min": kept[0], "size_median": kept[len(kept) // 2], "size_max": kept[-1]}
+    return cent, report
 
 
 def load_bank(path, device="cuda"):
@@ -799,6 +956,12 @@ def build_parser():
                         "(default: a single bank, the file as it always was)")
     b.add_argument("--scale-weights", type=scale_weights_arg, default=None, metavar="W1,W2,...",
                    help="with --scales: the share of each scale's track in the mix, normalised to sum 1 (default: equal)")
+    b.add_argument("--clusters", type=int, default=None, metavar="K",
+                   help="cluster a pool of frames with k-means on the GPU and store the K centroids (empty clusters dropped) "
+                        "as the bank: the same file format (default: the strided frames themselves, --max-frames of them)")
+    b.add_argument("--pool-frames", type=int, default=None, metavar="N",
+                   help="with --clusters: upper bound on the frames that are clustered (default: all, 2^22 at most)")
+    b.add_argument("--kmeans-iters", type=int, default=10, metavar="I", help="with --clusters: iterations at most")
     return p
 
 
@@ -813,17 +976,34 @@ def main(argv=None):
     stats = jio.load_stats(args.stats_file or os.path.join(args.data_dir, "global_stats_separated.json"), channels=channels)
     if args.scale_weights is not None and args.scales is None:
         raise SystemExit("--scale-weights needs --scales")
+    km = {}
+    if args.clusters is None:
+        if args.pool_frames is not None:
+            raise SystemExit("--pool-frames needs --clusters")
+    else:
+        try:
+            km = dict(clusters=check_clusters(args.clusters), pool_frames=check_pool_frames(args.pool_frames),
+                      kmeans_iters=args.kmeans_iters)
+            if args.kmeans_iters < 1:
+                raise ValueError(f"kmeans_iters {args.kmeans_iters} must be at least 1")
+        except ValueError as e:
+            raise SystemExit(f"--clusters: {e}")
     if args.scales is None:
         bank = LatentBank.from_data_dir(args.data_dir, stats, split=args.split, max_frames=args.max_frames, key=args.key,
-                                        device=args.device)
+                                        device=args.device, **km)
     else:
         try:
             weights = check_scale_weights(args.scale_weights, len(args.scales))
         except ValueError as e:
             raise SystemExit(f"--scale-weights: {e}")
         bank = MultiScaleBank.from_data_dir(args.data_dir, stats, split=args.split, max_frames=args.max_frames, key=args.key,
-                                            device=args.device, scales=args.scales, weights=args.scale_weights)
+                                            device=args.device, scales=args.scales, weights=args.scale_weights, **km)
     bank.save(args.out)
+    if km:
+        import json
+        with open(args.out + ".kmeans.json", "w") as f:
+            json.dump(bank.kmeans_report, f, indent=1)
+        print(f"k-means report -> {args.out}.kmeans.json")
     print(f"bank of {len(bank)} x {bank.channels} fp16 rows (key={bank.key}) from {len(files)} files" +
           (f", scales {list(args.scales)} with weights {[round(w, 6) for w in weights]}" if args.scales else "") + f" -> {args.out}")
     return args.out
