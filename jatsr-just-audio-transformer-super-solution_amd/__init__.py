@@ -26,7 +26,7 @@ _LAZY = {
     "LatentStore": "data", "epoch_batches": "data", "val_crop_start": "data", "train_crop_start": "data",
     "train_batch_plan": "data", "val_batch_plan": "data",
     "LatentBank": "retrieval", "frame_plan": "retrieval", "MultiScaleBank": "retrieval", "load_bank": "retrieval",
-    "kmeans": "retrieval",
+    "kmeans": "retrieval", "IVFBank": "retrieval",
     "harmonic_metrics": "harmonic", "generate_harmonics": "harmonic",
     "find_latest_checkpoint_dir": "fit", "resolve_run_dir": "fit",
 }

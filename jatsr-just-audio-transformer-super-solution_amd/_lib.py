@@ -221,6 +221,15 @@ KM_SIGNATURES = {
     "jat_bank_cluster_update": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _SZ, _VP]),
     "jat_bank_sum_dist2": (C.c_int, [_VP, _I64, _VP, _VP]),
 }
+# name -> (restype, argtypes); every symbol include/jat_hip_ivf.h declares (IVF index over a retrieval bank)
+IVF_SIGNATURES = {
+    "jat_bank_group_workspace_bytes": (C.c_int, [_VP, _I32, C.POINTER(_SZ)]),
+    "jat_bank_group": (C.c_int, [_VP, _VP, _I32, _VP, _VP, _VP, _VP, _SZ, _VP]),
+    "jat_ivf_search_workspace_bytes": (C.c_int, [_VP, _VP, _I64, _I32, _I32, C.POINTER(_SZ)]),
+    "jat_ivf_search": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _SZ, _VP]),
+}
+IVF_MAX_NPROBE = 8           # JAT_IVF_MAX_NPROBE
+IVF_MAX_ROWS = 1 << 22       # JAT_IVF_MAX_ROWS
 KM_MAX_POOL = 1 << 22        # JAT_KM_MAX_POOL
 HARM_MAX = 128               # JAT_HARM_MAX
 BANK_MAX_SCALES = 4          # JAT_BANK_MAX_SCALES
@@ -252,7 +261,7 @@ def lib():
         import torch  # noqa: F401
         h = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(MS_SIGNATURES.items()) + list(HARM_SIGNATURES.items()) + \
-                list(KM_SIGNATURES.items()):
+                list(KM_SIGNATURES.items()) + list(IVF_SIGNATURES.items()):
             if not hasattr(h, name) and os.environ.get("JAT_LIB_ALLOW_MISSING"):
                 continue      # A/B against an OLDER build through JAT_LIB_PATH (tools/sampler_ab.py): it lacks the newest entry points
             fn = getattr(h, name)

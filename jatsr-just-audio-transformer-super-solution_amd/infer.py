@@ -45,7 +45,7 @@ import torch
 
 from . import io as jio
 from .model import JaT_AudioSR_V2, JaT_AudioSR_V3, load_model
-from .retrieval import index_k_arg, index_rate_arg, scale_weights_arg
+from .retrieval import index_k_arg, index_rate_arg, nprobe_arg, scale_weights_arg
 from .sampler import chunk_plan, sample_long
 
 
@@ -110,6 +110,9 @@ def build_parser():
     p.add_argument("--index-scale-weights", type=scale_weights_arg, default=None, metavar="W1,W2,...",
                    help="with a multi-scale --index-bank (retrieval build --scales): the share of each scale's track, one "
                         "positive number per scale, normalised to sum 1 (default: the weights stored in the bank file)")
+    p.add_argument("--index-nprobe", type=nprobe_arg, default=None, metavar="P",
+                   help="with an IVF --index-bank (retrieval build --ivf): the lists a search scans, 1..8 (default: the "
+                        "number stored in the bank file)")
     return p
 
 
@@ -190,9 +193,14 @@ def run(args):
     if args.dac_weights:
         codec = decode_to_wav(args, gen, hr, lr, total, stem, suffix, device, codec, source)
     if index_bank:
-        from .retrieval import MultiScaleBank, load_bank
-        bank = load_bank(index_bank, device=device)            # either format: a LatentBank or a MultiScaleBank
+        from .retrieval import IVFBank, MultiScaleBank, load_bank
+        bank = load_bank(index_bank, device=device)            # any format: a LatentBank, a MultiScaleBank or an IVFBank
         multi = isinstance(bank, MultiScaleBank)
+        index_nprobe = getattr(args, "index_nprobe", None)
+        if index_nprobe is not None:
+            if not isinstance(bank, IVFBank):
+                raise SystemExit("--index-nprobe needs an IVF bank (retrieval build --ivf)")
+            bank.nprobe = nprobe_arg(index_nprobe)
         scale_weights = getattr(args, "index_scale_weights", None)
         if scale_weights is not None:
             if not multi:
@@ -212,13 +220,16 @@ def run(args):
                     lists.update({f"idx_s{sc}": i[0].cpu(), f"dist2_s{sc}": d[0].cpu()})
         elif index_k > 1:
             lists = {"idx": nn_idx[0].cpu(), "dist2": nn_dist2[0].cpu()}                         # [frames, K]
+        if isinstance(bank, IVFBank):                          # idx are positions in the grouped bank
+            extra = {"index_lists": bank.nlist, "index_nprobe": bank.nprobe}
         jio.save_latent_file(idx_path, generated_latent=enhanced[0].to("cpu", torch.float16),
                              metadata={"source": os.path.basename(path), "index_bank": os.path.basename(index_bank),
                                        "index_rate": index_rate, "index_k": index_k, "bank_rows": len(bank),
                                        "bank_key": bank.key, **extra}, **lists)
         print(f"retrieval: {len(bank)} bank rows (key={bank.key}), index rate {index_rate}" +
               (f", {index_k} nearest frames" if index_k > 1 else "") +
-              (f", scales {list(bank.scales)}" if multi else "") + f" -> {idx_path}")
+              (f", scales {list(bank.scales)}" if multi else "") +
+              (f", {bank.nlist} lists, nprobe {bank.nprobe}" if isinstance(bank, IVFBank) else "") + f" -> {idx_path}")
         if args.dac_weights:
             name = f"{stem}_generated{suffix}_idx.wav"
             jio.write_wav_float32(os.path.join(args.output_dir, name), codec.decode(enhanced[:1])[0, 0], codec.sample_rate)

@@ -27,6 +27,14 @@ up to 2^22 frames is clustered on the GPU and the K centroids are stored as the 
 
     python -m jatsr_amd.retrieval build --data-dir data_processed --out bank_km.pt --clusters 10000 [--pool-frames 1000000]
 
+IVF index (`IVFBank`, `--ivf`; the `IVF{n},Flat` index RVC trains and searches with nprobe = 1): the rows are grouped
+by their nearest of n k-means centroids and a search scans only the lists of the `nprobe` centroids nearest to the query, so its
+cost no longer grows with the bank.  Within the probed lists the result is the exact search's, bit for bit; outside them a
+nearer row can be missed.  The bank file gets format 3; a multi-scale IVF is out of scope.
+
+    python -m jatsr_amd.retrieval build --data-dir data_processed --out bank_ivf.pt --max-frames 1000000 --ivf [--ivf-lists N] [--ivf-nprobe P]
+    python -m jatsr_amd.infer ... --index-bank bank_ivf.pt --index-rate 0.4 [--index-nprobe 8]
+
 Whether retrieval improves audio quality is not established here: nothing in this repository was run with trained weights.
 """
 from __future__ import annotations
@@ -43,6 +51,7 @@ from . import _lib as L
 STAT_KEYS = ("hr_mean", "hr_std", "lr_mean", "lr_std")
 FORMAT = 1            # a single bank
 FORMAT_MS = 2         # a multi-scale bank: one single-bank dictionary per scale
+FORMAT_IVF = 3        # an IVF index: a single-bank dictionary (rows grouped by list), the centroid keys, offsets, order, nprobe
 
 
 def frame_plan(lengths, max_frames):
@@ -203,6 +212,8 @@ def unpack_state(d):
     """Validate a bank dictionary -> (keys, values, key, channels, stats)."""
     if isinstance(d, dict) and d.get("format") == FORMAT_MS:
         raise ValueError("this is a multi-scale bank (format 2), not a single bank: load it with retrieval.load_bank")
+    if isinstance(d, dict) and d.get("format") == FORMAT_IVF:
+        raise ValueError("this is an IVF index (format 3), not a single bank: load it with retrieval.load_bank")
     for k in ("keys", "values", "key", "channels", "stats"):
         if k not in d:
             raise KeyError(f"bank file lacks {k!r} (keys: {sorted(d.keys())})")
@@ -916,9 +927,267 @@ def kmeans(pool, n_clusters, iters=10, drop_empty=True):
     return cent, report
 
 
+# ---- IVF index (C ABI: include/jat_hip_ivf.h) ---------------------------------------------------------------------
+def default_nlist(n_rows):
+    """The number of lists RVC's index training uses for N rows, min(int(16 sqrt(N)), N // 39), floored at 1."""
+    import math
+    n = int(n_rows)
+    if n < 1:
+        raise ValueError(f"default_nlist: {n_rows!r} rows")
+    return max(1, min(int(16 * math.sqrt(n)), n // 39))
+
+
+def check_nprobe(nprobe):
+    """The number of probed lists as an int in 1..8 (JAT_IVF_MAX_NPROBE); ValueError otherwise."""
+    if isinstance(nprobe, bool) or not isinstance(nprobe, int) or not 1 <= nprobe <= L.IVF_MAX_NPROBE:
+        raise ValueError(f"nprobe {nprobe!r} outside 1..{L.IVF_MAX_NPROBE}")
+    return nprobe
+
+
+def nprobe_arg(text):
+    """argparse type of --ivf-nprobe and --index-nprobe."""
+    try:
+        return check_nprobe(int(text))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"nprobe {text!r} outside 1..{L.IVF_MAX_NPROBE}")
+
+
+def check_offsets(offsets, n_lists, n_rows):
+    """The list offsets of an IVF index as a CPU int32 tensor [n_lists + 1]: they start at 0, never descend and end at the
+    number of rows (every row belongs to a list); ValueError otherwise."""
+    o = torch.as_tensor(offsets).detach().to("cpu")
+    if o.dim() != 1 or o.numel() != int(n_lists) + 1 or o.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"offsets: expected {int(n_lists) + 1} integers, got {o.dtype} {tuple(o.shape)}")
+    o = o.to(torch.int64)
+    if int(o[0]) != 0 or bool((o[1:] < o[:-1]).any()) or int(o[-1]) != int(n_rows):
+        raise ValueError(f"offsets must start at 0, never descend and end at {int(n_rows)} rows")
+    return o.to(torch.int32)
+
+
+def pack_ivf_state(bank, centroids, offsets, order, nprobe):
+    """The dictionary an IVF bank file holds: format 3, the single-bank dictionary of the grouped rows (`pack_state`), the
+    fp16 centroid keys [nlist, C], offsets int32 [nlist + 1], order int32 [N] (a permutation) and nprobe."""
+    bank = dict(bank)
+    keys, _, _, channels, _ = unpack_state(bank)
+    n = int(keys.shape[0])
+    centroids = torch.as_tensor(centroids).detach().cpu().contiguous()
+    if centroids.dim() != 2 or centroids.dtype != torch.float16 or centroids.shape[1] != channels or not 1 <= centroids.shape[0] <= n:
+        raise ValueError(f"centroids must be fp16 [1..{n}, {channels}], got {centroids.dtype} {tuple(centroids.shape)}")
+    offsets = check_offsets(offsets, centroids.shape[0], n)
+    order = torch.as_tensor(order).detach().cpu()
+    if order.dim() != 1 or order.numel() != n or order.dtype not in (torch.int32, torch.int64) or \
+            not torch.equal(torch.sort(order.to(torch.int64)).values, torch.arange(n)):
+        raise ValueError(f"order must be a permutation of 0..{n - 1}")
+    return {"format": FORMAT_IVF, "bank": bank, "centroids": centroids, "offsets": offsets, "order": order.to(torch.int32),
+            "nprobe": check_nprobe(nprobe)}
+
+
+def unpack_ivf_state(d):
+    """Validate an IVF bank dictionary -> (single-bank dictionary, centroids, offsets, order, nprobe)."""
+    if not isinstance(d, dict) or d.get("format") != FORMAT_IVF:
+        raise ValueError("not an IVF index (format 3); other bank files load with retrieval.load_bank")
+    for k in ("bank", "centroids", "offsets", "order", "nprobe"):
+        if k not in d:
+            raise KeyError(f"IVF bank file lacks {k!r} (keys: {sorted(d.keys())})")
+    st = pack_ivf_state(d["bank"], d["centroids"], d["offsets"], d["order"], d["nprobe"])
+    return st["bank"], st["centroids"], st["offsets"], st["order"], st["nprobe"]
+
+
+def group_rows(bank, idx, nlist, check=True):
+    """The rows of `bank` grouped by list (`jat_bank_group`): idx int32 [N] as `assign` writes it -> (grouped LatentBank,
+    offsets int32 [nlist + 1], order int32 [N]).  Inside a list the rows ascend by their original number; order[p] is the
+    original row of position p.  An idx entry outside [0, nlist) is placed behind all lists on the device; check: wait for the
+    offsets and raise ValueError when there is one."""
+    if not isinstance(bank, LatentBank):
+        raise ValueError("group_rows: the bank is a LatentBank")
+    N = len(bank)
+    if isinstance(nlist, bool) or not isinstance(nlist, int):
+        raise ValueError(f"nlist {nlist!r} must be an integer")
+    if idx.shape != (N,) or idx.dtype != torch.int32 or idx.device != bank.device or not idx.is_contiguous():
+        raise ValueError(f"idx: expected a contiguous int32 [{N}] tensor on {bank.device}")
+    need = C.c_size_t()
+    L.check(L.lib().jat_bank_group_workspace_bytes(bank._h, nlist, C.byref(need)))
+    dst = LatentBank(bank.channels, N, key=bank.key, device=bank.device)
+    if bank.stats is not None:
+        dst._set_stats(bank.stats)
+    offsets = torch.empty(nlist + 1, dtype=torch.int32, device=bank.device)
+    order = torch.empty(N, dtype=torch.int32, device=bank.device)
+    work = torch.empty(need.value, dtype=torch.uint8, device=bank.device)
+    with torch.cuda.device(bank.device):
+        L.check(L.lib().jat_bank_group(bank._h, L.ptr(idx), nlist, dst._h, L.ptr(offsets), L.ptr(order), L.ptr(work),
+                                       work.numel(), L.stream_ptr()))
+    work.record_stream(torch.cuda.current_stream(bank.device))
+    if check and int(offsets[-1]) != N:
+        raise ValueError(f"group_rows: {N - int(offsets[-1])} entries of idx lie outside [0, {nlist}); they belong to no list")
+    return dst, offsets, order
+
+
+class IVFBank:
+    """An inverted-file index over a `LatentBank` (RVC's `IVF{n},Flat`): `.bank` holds the rows grouped by list, `.centroids`
+    the coarse quantiser (a LatentBank of nlist rows), `.offsets` int32 [nlist + 1] the lists' positions, `.order` int32 [N] the
+    original row of every position, `.nprobe` how many lists a search scans.  Every index a search returns is a position in
+    `.bank`, so `blend`, `blend_topk` and `rows` are the bank's own.  Within the probed lists the result is the exact search's,
+    bit for bit; `nprobe >= nlist` is `bank.search_topk`."""
+
+    def __init__(self, bank, centroids, offsets, order, nprobe=1):
+        if not isinstance(bank, LatentBank) or not isinstance(centroids, LatentBank):
+            raise ValueError("IVFBank: the bank and the centroids are LatentBanks")
+        if bank.channels != centroids.channels:
+            raise ValueError(f"IVFBank: bank of {bank.channels} channels, centroids of {centroids.channels}")
+        if bank.device != centroids.device:
+            raise ValueError(f"IVFBank: bank on {bank.device}, centroids on {centroids.device}")
+        self.bank, self.centroids, self.nprobe = bank, centroids, check_nprobe(nprobe)
+        self.offsets = offsets.to(bank.device, torch.int32).contiguous()
+        self.order = order.to(bank.device, torch.int32).contiguous()
+        if self.offsets.shape != (len(centroids) + 1,) or self.order.shape != (len(bank),):
+            raise ValueError(f"IVFBank: offsets {tuple(self.offsets.shape)} / order {tuple(self.order.shape)} for "
+                             f"{len(centroids)} lists over {len(bank)} rows")
+        self._work = None
+
+    # ---- what the bank answers itself --------------------------------------------------------------------------------------
+    key = property(lambda self: self.bank.key)
+    stats = property(lambda self: self.bank.stats)
+    channels = property(lambda self: self.bank.channels)
+    device = property(lambda self: self.bank.device)
+    nlist = property(lambda self: len(self.centroids))
+
+    def check_stats(self, stats):
+        self.bank.check_stats(stats)
+
+    def __len__(self):
+        return len(self.bank)
+
+    def rows(self, which="keys", full=False):
+        return self.bank.rows(which, full)
+
+    def blend(self, *args, **kwargs):
+        return self.bank.blend(*args, **kwargs)
+
+    def blend_topk(self, *args, **kwargs):
+        return self.bank.blend_topk(*args, **kwargs)
+
+    def list_sizes(self):
+        """Rows per list, int64 [nlist] on the CPU."""
+        o = self.offsets.cpu().to(torch.int64)
+        return o[1:] - o[:-1]
+
+    # ---- building -------------------------------------------------------------------------------------------------------------
+    @classmethod
+    def from_centroids(cls, bank, centroids, nprobe=1):
+        """The index of `bank` under a given coarse quantiser (a LatentBank of 1..N rows of the same key kind): `assign`, then
+        `group_rows`.  The bank itself is left as it is; the index holds a grouped copy."""
+        nprobe = check_nprobe(nprobe)
+        if not isinstance(bank, LatentBank) or not isinstance(centroids, LatentBank):
+            raise ValueError("IVFBank: the bank and the centroids are LatentBanks")
+        if len(bank) > L.IVF_MAX_ROWS:
+            raise ValueError(f"IVFBank: a bank of {len(bank)} rows exceeds {L.IVF_MAX_ROWS}")
+        idx, _ = centroids.assign(bank)
+        grouped, offsets, order = group_rows(bank, idx, len(centroids))
+        return cls(grouped, centroids, offsets, order, nprobe)
+
+    @classmethod
+    def build(cls, bank, nlist=None, iters=10, nprobe=1):
+        """k-means with `nlist` clusters (default: `default_nlist`; empty clusters dropped), then `from_centroids` ->
+        (index, report): the k-means report plus the lists' min / median / max size."""
+        nprobe = check_nprobe(nprobe)
+        if not isinstance(bank, LatentBank):
+            raise ValueError("IVFBank: the bank is a LatentBank")
+        nlist = default_nlist(len(bank)) if nlist is None else check_clusters(nlist)
+        cent, report = kmeans(bank, nlist, iters=iters, drop_empty=True)
+        ivf = cls.from_centroids(bank, cent, nprobe)
+        sizes = sorted(ivf.list_sizes().tolist())
+        report = dict(report, lists=len(cent), list_min=sizes[0], list_median=sizes[len(sizes) // 2], list_max=sizes[-1],
+                      nprobe=nprobe)
+        return ivf, report
+
+    # ---- use ------------------------------------------------------------------------------------------------------------------
+    def workspace_bytes(self, n_queries, k, nprobe):
+        n = C.c_size_t()
+        L.check(L.lib().jat_ivf_search_workspace_bytes(self.bank._h, self.centroids._h, int(n_queries), int(k), int(nprobe),
+                                                       C.byref(n)))
+        return n.value
+
+    def search_topk(self, x, k, mean=None, std=None, nprobe=None, probes=False):
+        """The k nearest rows of every frame among the lists of its `nprobe` (default: the index's) nearest centroids, ordered
+        by (distance, position) -> (idx int32 [B, T, k], dist2 fp32 [B, T, k]); with probes also the probed lists int32
+        [B, T, nprobe] (-1: fewer lists than probes).  Fewer candidates than k: the tail is idx -1 and dist2 +inf."""
+        k = check_index_k(k)
+        nprobe = self.nprobe if nprobe is None else check_nprobe(nprobe)
+        x = self.bank._x(x)
+        B, _, T = x.shape
+        if B < 1 or T < 1:
+            raise ValueError(f"x {tuple(x.shape)}: B and T must be positive")
+        need = self.workspace_bytes(B * T, k, nprobe)
+        if self._work is None or self._work.numel() < need:
+            self._work = torch.empty(need, dtype=torch.uint8, device=self.device)
+        idx = torch.empty(B, T, k, dtype=torch.int32, device=self.device)
+        dist2 = torch.empty(B, T, k, dtype=torch.float32, device=self.device)
+        pr = torch.empty(B, T, nprobe, dtype=torch.int32, device=self.device) if probes else None
+        mean, std = self.bank._vec(mean), self.bank._vec(std)
+        with torch.cuda.device(self.device):
+            L.check(L.lib().jat_ivf_search(self.bank._h, self.centroids._h, L.ptr(self.offsets), L.ptr(x), L.ptr(mean),
+                                           L.ptr(std), B, T, k, nprobe, L.ptr(idx), L.ptr(dist2), L.ptr(pr), L.ptr(self._work),
+                                           self._work.numel(), L.stream_ptr()))
+        return (idx, dist2, pr) if probes else (idx, dist2)
+
+    def search(self, x, mean=None, std=None, nprobe=None):
+        """`search_topk` with k = 1 -> (idx int32 [B, T], dist2 fp32 [B, T])."""
+        idx, dist2 = self.search_topk(x, 1, mean, std, nprobe=nprobe)
+        return idx[..., 0], dist2[..., 0]
+
+    def retrieve(self, x, index_rate, stats=None, query=None, k=1, dist2_floor=1e-6, neighbours=False):
+        """`LatentBank.retrieve` with the IVF search in the place of the exact one; the blends are the bank's own."""
+        check_index_rate(index_rate)
+        k = check_index_k(k)
+        check_dist2_floor(dist2_floor)
+        if stats is not None:
+            self.check_stats(stats)
+        elif self.stats is None:
+            raise ValueError("the bank holds no statistics yet (nothing was added)")
+        s = self.bank._dev_stats
+        if self.key == "lr":
+            if query is None:
+                raise ValueError("a bank keyed by LR frames needs the LR latent as `query`")
+            if query.shape != x.shape:
+                raise ValueError(f"query {tuple(query.shape)} does not match x {tuple(x.shape)}")
+            q, mean, std = query.to(self.device, torch.float32), s["lr_mean"], s["lr_std"]
+        else:
+            q, mean, std = x, s["hr_mean"], s["hr_std"]
+        if k == 1:
+            idx, dist2 = self.search(q, mean, std)
+            idx, dist2 = idx.contiguous(), dist2.contiguous()
+            y = self.bank.blend(x, idx, index_rate, s["hr_mean"], s["hr_std"])
+        else:
+            idx, dist2 = self.search_topk(q, k, mean, std)
+            y = self.bank.blend_topk(x, idx, dist2, index_rate, s["hr_mean"], s["hr_std"], dist2_floor=dist2_floor)
+        return (y, idx, dist2) if neighbours else y
+
+    # ---- files ----------------------------------------------------------------------------------------------------------------
+    def state(self):
+        return pack_ivf_state(self.bank.state(), self.centroids.rows("keys")[0].cpu(), self.offsets.cpu(), self.order.cpu(),
+                              self.nprobe)
+
+    def save(self, path):
+        torch.save(self.state(), path)
+
+    @classmethod
+    def from_state(cls, d, device="cuda"):
+        bank_d, centroids, offsets, order, nprobe = unpack_ivf_state(d)
+        bank = LatentBank.from_state(bank_d, device=device)
+        cent = LatentBank(bank.channels, int(centroids.shape[0]), key="hr", device=device)   # only the keys are used
+        cent.load_rows(centroids)
+        return cls(bank, cent, offsets, order, nprobe)
+
+    @classmethod
+    def load(cls, path, device="cuda"):
+        return cls.from_state(torch.load(path, map_location="cpu", weights_only=False), device=device)
+
+
 def load_bank(path, device="cuda"):
-    """A bank file of either format -> `LatentBank` (format 1) or `MultiScaleBank` (format 2)."""
+    """A bank file of any format -> `LatentBank` (format 1), `MultiScaleBank` (format 2) or `IVFBank` (format 3)."""
     d = torch.load(path, map_location="cpu", weights_only=False)
+    if isinstance(d, dict) and d.get("format") == FORMAT_IVF:
+        return IVFBank.from_state(d, device=device)
     if isinstance(d, dict) and d.get("format") == FORMAT_MS:
         return MultiScaleBank.from_state(d, device=device)
     return LatentBank.from_state(d, device=device)
@@ -962,6 +1231,14 @@ def build_parser():
     b.add_argument("--pool-frames", type=int, default=None, metavar="N",
                    help="with --clusters: upper bound on the frames that are clustered (default: all, 2^22 at most)")
     b.add_argument("--kmeans-iters", type=int, default=10, metavar="I", help="with --clusters: iterations at most")
+    b.add_argument("--ivf", action="store_true",
+                   help="write an IVF index (format 3): the rows grouped by their nearest of N k-means centroids, searched "
+                        "through the nearest lists only.  With --clusters the bank is compacted first, then indexed.  Not "
+                        "combinable with --scales: a multi-scale IVF index is out of scope")
+    b.add_argument("--ivf-lists", type=int, default=None, metavar="N",
+                   help="with --ivf: the number of lists (default: min(int(16 sqrt(rows)), rows // 39), as RVC trains its index)")
+    b.add_argument("--ivf-nprobe", type=nprobe_arg, default=None, metavar="P",
+                   help=f"with --ivf: the lists a search scans, 1..{L.IVF_MAX_NPROBE}, stored in the file (default: 1, as RVC searches)")
     return p
 
 
@@ -976,6 +1253,10 @@ def main(argv=None):
     stats = jio.load_stats(args.stats_file or os.path.join(args.data_dir, "global_stats_separated.json"), channels=channels)
     if args.scale_weights is not None and args.scales is None:
         raise SystemExit("--scale-weights needs --scales")
+    if args.ivf and args.scales is not None:
+        raise SystemExit("--ivf cannot be combined with --scales: a multi-scale IVF index is out of scope")
+    if not args.ivf and (args.ivf_lists is not None or args.ivf_nprobe is not None):
+        raise SystemExit("--ivf-lists and --ivf-nprobe need --ivf")
     km = {}
     if args.clusters is None:
         if args.pool_frames is not None:
@@ -998,11 +1279,23 @@ def main(argv=None):
             raise SystemExit(f"--scale-weights: {e}")
         bank = MultiScaleBank.from_data_dir(args.data_dir, stats, split=args.split, max_frames=args.max_frames, key=args.key,
                                             device=args.device, scales=args.scales, weights=args.scale_weights, **km)
+    kmeans_report = bank.kmeans_report if km else None
+    if args.ivf:
+        import json
+        try:
+            bank, ivf_report = IVFBank.build(bank, nlist=args.ivf_lists, iters=args.kmeans_iters,
+                                             nprobe=1 if args.ivf_nprobe is None else args.ivf_nprobe)
+        except ValueError as e:
+            raise SystemExit(f"--ivf: {e}")
+        with open(args.out + ".ivf.json", "w") as f:
+            json.dump(ivf_report, f, indent=1)
+        print(f"IVF index: {ivf_report['lists']} lists of {ivf_report['list_min']} / {ivf_report['list_median']} / "
+              f"{ivf_report['list_max']} rows (min / median / max), nprobe {bank.nprobe}; report -> {args.out}.ivf.json")
     bank.save(args.out)
     if km:
         import json
         with open(args.out + ".kmeans.json", "w") as f:
-            json.dump(bank.kmeans_report, f, indent=1)
+            json.dump(kmeans_report, f, indent=1)
         print(f"k-means report -> {args.out}.kmeans.json")
     print(f"bank of {len(bank)} x {bank.channels} fp16 rows (key={bank.key}) from {len(files)} files" +
           (f", scales {list(args.scales)} with weights {[round(w, 6) for w in weights]}" if args.scales else "") + f" -> {args.out}")

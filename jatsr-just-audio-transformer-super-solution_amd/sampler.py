@@ -230,7 +230,7 @@ def sample_long(model, lr_latent, hr_mean, hr_std, lr_mean, lr_std, num_steps=50
     lr_latent: [C, T_total] un-normalised latent.  noise: optional list of per-chunk z0 tensors [1,C,T_i].
     Returns [1, C, T_total] de-normalised generated latent.
 
-    bank (a `jatsr_amd.retrieval.LatentBank`, or a `MultiScaleBank`: the same call, every scale's track mixed in) with index_rate > 0: latent retrieval on the whole cross-faded output, once —
+    bank (a `jatsr_amd.retrieval.LatentBank`, or a `MultiScaleBank`: the same call, every scale's track mixed in, or an `IVFBank`: the same call, the search through the probed lists only) with index_rate > 0: latent retrieval on the whole cross-faded output, once —
     every frame is looked up in the bank (by its own content under the HR statistics, or by the LR input under the LR
     statistics when the bank is keyed by LR frames) and index_rate of the retrieved HR frame is mixed in.  Without a bank, or
     at index_rate 0, nothing more is launched.  index_k in 1..8: that many nearest frames, mixed with inverse-square-distance
