@@ -228,6 +228,14 @@ IVF_SIGNATURES = {
     "jat_ivf_search_workspace_bytes": (C.c_int, [_VP, _VP, _I64, _I32, _I32, C.POINTER(_SZ)]),
     "jat_ivf_search": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _I32, _I32, _I32, _I32, _VP, _VP, _VP, _VP, _SZ, _VP]),
 }
+# name -> (restype, argtypes); every symbol include/jat_hip_rate.h declares (voicing-aware index rates)
+RATE_SIGNATURES = {
+    "jat_f0_classes": (C.c_int, [_VP, _VP, _I32, _I32, _I32, _F32, _I32, _VP, _VP, _VP, _VP]),
+    "jat_rate_track": (C.c_int, [_VP, _I32, _I32, _I32, C.POINTER(_F32), _I32, _VP, _VP]),
+    "jat_rate_mix": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _VP]),
+}
+RATE_MAX_HALF_WINDOW = 32    # JAT_RATE_MAX_HALF_WINDOW
+RATE_MAX_SMOOTH = 16         # JAT_RATE_MAX_SMOOTH
 IVF_MAX_NPROBE = 8           # JAT_IVF_MAX_NPROBE
 IVF_MAX_ROWS = 1 << 22       # JAT_IVF_MAX_ROWS
 KM_MAX_POOL = 1 << 22        # JAT_KM_MAX_POOL
@@ -261,7 +269,7 @@ def lib():
         import torch  # noqa: F401
         h = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(MS_SIGNATURES.items()) + list(HARM_SIGNATURES.items()) + \
-                list(KM_SIGNATURES.items()) + list(IVF_SIGNATURES.items()):
+                list(KM_SIGNATURES.items()) + list(IVF_SIGNATURES.items()) + list(RATE_SIGNATURES.items()):
             if not hasattr(h, name) and os.environ.get("JAT_LIB_ALLOW_MISSING"):
                 continue      # A/B against an OLDER build through JAT_LIB_PATH (tools/sampler_ab.py): it lacks the newest entry points
             fn = getattr(h, name)

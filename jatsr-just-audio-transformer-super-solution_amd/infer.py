@@ -32,6 +32,12 @@ per-channel normalisation (:381-394).  Differences, all outside the hot path's s
     A multi-scale bank file (`retrieval build --scales 1,2,4`) needs no switch: `--index-bank` loads either
     format, `--index-scale-weights W1,W2,...` replaces the stored scale weights, and the metadata gains `index_scales` and
     `index_scale_weights` (for K > 1 the lists are `idx_s{scale}` / `dist2_s{scale}`, one pair per scale).
+  * `--index-protect P`, `--index-unstable U`, `--index-smooth S` (any of them, with `--index-bank`) make the index
+    rate a per-frame track: the pitch track of the LR input at the codec's rate (hop 512, `--index-f0-method yin|pyin`; the LR
+    waveform itself with `--input-audio`, else the DAC-decoded LR latent, which needs `--dac-weights`) is classed frame by frame
+    as not live / unstable / stable, and those frames get R * P, R * U and R of the retrieved frame, averaged over S frames
+    on either side (defaults 1, 1, 2).  The `_idx.pt` file gains `rates` and `f0_classes` [frames] and its metadata the four
+    settings, `voiced_share` and `stable_share`.  Without these flags every file is what it was.
 
     python -m jatsr_amd.infer --checkpoint ckpt.pt --input-file clip.pt --stats-file stats.json --cfg-scale 3.0
 """
@@ -45,7 +51,7 @@ import torch
 
 from . import io as jio
 from .model import JaT_AudioSR_V2, JaT_AudioSR_V3, load_model
-from .retrieval import index_k_arg, index_rate_arg, nprobe_arg, scale_weights_arg
+from .retrieval import index_k_arg, index_rate_arg, nprobe_arg, protect_arg, scale_weights_arg, smooth_arg, unstable_arg
 from .sampler import chunk_plan, sample_long
 
 
@@ -113,7 +119,27 @@ def build_parser():
     p.add_argument("--index-nprobe", type=nprobe_arg, default=None, metavar="P",
                    help="with an IVF --index-bank (retrieval build --ivf): the lists a search scans, 1..8 (default: the "
                         "number stored in the bank file)")
+    p.add_argument("--index-protect", type=protect_arg, default=None, metavar="P",
+                   help="with --index-bank: frames without a pitch (consonants, breaths, noise) get R * P of the retrieved "
+                        "frame in place of R, P in [0, 1] (default 1: no effect).  This is the plain factor: RVC's slider of "
+                        "the same name means \"off\" at 0.5 and defaults to 0.33.  Makes the index rate a per-frame track")
+    p.add_argument("--index-unstable", type=unstable_arg, default=None, metavar="U",
+                   help="with --index-bank: voiced frames whose F0 is not steady (fewer than 7 of the 9 frames around them within "
+                        "50 cents) get R * U, U in [0, 1] (default 1: no effect).  Makes the index rate a per-frame track")
+    p.add_argument("--index-smooth", type=smooth_arg, default=None, metavar="S",
+                   help="with --index-bank: the per-frame rate is averaged over S frames on either side, 0..16 (default 2).  "
+                        "Makes the index rate a per-frame track")
+    p.add_argument("--index-f0-method", choices=("yin", "pyin"), default=None,
+                   help="with --index-protect / --index-unstable / --index-smooth: the tracker of the LR input's pitch (default yin)")
     return p
+
+
+RATE_FLAGS = ("index_protect", "index_unstable", "index_smooth")
+
+
+def rate_flags(args):
+    """Whether the index rate is a per-frame track: any of --index-protect, --index-unstable, --index-smooth was given."""
+    return any(getattr(args, name, None) is not None for name in RATE_FLAGS)
 
 
 def run(args):
@@ -140,6 +166,14 @@ def run(args):
     index_bank = getattr(args, "index_bank", None)
     index_rate = index_rate_arg(getattr(args, "index_rate", 0.4)) if index_bank else 0.0
     index_k = index_k_arg(getattr(args, "index_k", 1)) if index_bank else 1
+    index_track = rate_flags(args)
+    if (index_track or getattr(args, "index_f0_method", None) is not None) and not index_bank:
+        raise SystemExit("--index-protect, --index-unstable, --index-smooth and --index-f0-method need --index-bank")
+    if getattr(args, "index_f0_method", None) is not None and not index_track:
+        raise SystemExit("--index-f0-method needs --index-protect, --index-unstable or --index-smooth")
+    if index_track and not args.input_audio and not args.dac_weights:
+        raise SystemExit("--index-protect, --index-unstable and --index-smooth take the pitch of the LR audio: give "
+                         "--input-audio, or --dac-weights to decode the LR latent")
     device = torch.device(args.device)
     os.makedirs(args.output_dir, exist_ok=True)
     model = load_model(args.checkpoint, device=device, cls=JaT_AudioSR_V2 if args.layernorm else JaT_AudioSR_V3,
@@ -210,9 +244,15 @@ def run(args):
             except ValueError as e:
                 raise SystemExit(f"--index-scale-weights: {e}")
         query = lr[None, :, :total].to(device).float() if bank.key == "lr" else None
-        enhanced, nn_idx, nn_dist2 = bank.retrieve(gen, index_rate, stats=stats, query=query, k=index_k, neighbours=True)
+        lists, extra, track = {}, {}, {}
+        rate = index_rate
+        if index_track:
+            if source is None:                                 # latent-file input: the decoded LR latent
+                source = codec.decode(lr[None, :, :total].to(device))[0, 0].float().contiguous()
+            rate, cls, track = index_rate_track(args, source, codec.sample_rate, total, index_rate)
+            lists.update({"rates": rate.cpu(), "f0_classes": cls.cpu()})
+        enhanced, nn_idx, nn_dist2 = bank.retrieve(gen, rate, stats=stats, query=query, k=index_k, neighbours=True)
         idx_path = os.path.join(args.output_dir, f"{stem}_generated{suffix}_idx.pt")
-        lists, extra = {}, {}
         if multi:                                              # per scale s: idx_s{s}, dist2_s{s} [ceil(frames / s), K]
             extra = {"index_scales": list(bank.scales), "index_scale_weights": list(bank.weights)}
             if index_k > 1:
@@ -225,11 +265,14 @@ def run(args):
         jio.save_latent_file(idx_path, generated_latent=enhanced[0].to("cpu", torch.float16),
                              metadata={"source": os.path.basename(path), "index_bank": os.path.basename(index_bank),
                                        "index_rate": index_rate, "index_k": index_k, "bank_rows": len(bank),
-                                       "bank_key": bank.key, **extra}, **lists)
+                                       "bank_key": bank.key, **extra, **track}, **lists)
         print(f"retrieval: {len(bank)} bank rows (key={bank.key}), index rate {index_rate}" +
               (f", {index_k} nearest frames" if index_k > 1 else "") +
               (f", scales {list(bank.scales)}" if multi else "") +
-              (f", {bank.nlist} lists, nprobe {bank.nprobe}" if isinstance(bank, IVFBank) else "") + f" -> {idx_path}")
+              (f", {bank.nlist} lists, nprobe {bank.nprobe}" if isinstance(bank, IVFBank) else "") +
+              (f", per-frame rate: protect {track['index_protect']}, unstable {track['index_unstable']}, smooth "
+               f"{track['index_smooth']} ({track['index_f0_method']}; {track['voiced_share']:.3f} of the frames voiced, "
+               f"{track['stable_share']:.3f} stable)" if track else "") + f" -> {idx_path}")
         if args.dac_weights:
             name = f"{stem}_generated{suffix}_idx.wav"
             jio.write_wav_float32(os.path.join(args.output_dir, name), codec.decode(enhanced[:1])[0, 0], codec.sample_rate)
@@ -237,12 +280,35 @@ def run(args):
     return out_path
 
 
+def index_rate_track(args, signal, sr, frames, index_rate):
+    """The per-frame index rate of --index-protect / --index-unstable / --index-smooth from the LR waveform `signal` fp32 [L]
+    on the GPU at the codec's rate: its pitch track (jatsr_amd.pitch defaults, hop 512: one value per latent frame), the
+    stability classes, the rate track -> (rates fp32 [frames], classes uint8 [frames], metadata).  Frames behind the end of the
+    pitch track are class 0.  The shares are taken over the frames of the pitch track; they carry no speech / music label."""
+    from . import pitch
+    from .retrieval import f0_classes, rate_track
+    protect = 1.0 if getattr(args, "index_protect", None) is None else args.index_protect
+    unstable = 1.0 if getattr(args, "index_unstable", None) is None else args.index_unstable
+    smooth = 2 if getattr(args, "index_smooth", None) is None else args.index_smooth
+    method = getattr(args, "index_f0_method", None) or "yin"
+    f0, voiced, _ = (pitch.pyin if method == "pyin" else pitch.yin)(signal, sr=sr, hop_length=512)
+    cls, summary = f0_classes(f0, voiced)
+    rates = rate_track(cls, frames, index_rate, protect=protect, unstable=unstable, smooth=smooth)
+    classes = torch.zeros(frames, dtype=torch.uint8, device=cls.device)
+    n = min(frames, cls.shape[0])
+    classes[:n] = cls[:n]
+    live, stable = (int(v) for v in summary.cpu())
+    meta = {"index_protect": protect, "index_unstable": unstable, "index_smooth": smooth, "index_f0_method": method,
+            "voiced_share": live / cls.shape[0], "stable_share": stable / cls.shape[0]}
+    return rates, classes, meta
+
+
 def encode_audio(args, device):
     """--input-audio: the WAV's DAC latent (the reference's data preparation, prepare_dataset_v5.py:206-219) becomes the
     LR latent; there is no HR latent.  -> (codec, None, lr fp32 [1024, T] on the CPU, source).  With --resample a WAV of
     another rate is converted to 44.1 kHz first; with --simulate-lr the WAV is the HR recording and both latents come from
     prepare_audio -> (codec, hr, lr, source).  source: with --lf-replace the 44.1 kHz low-resolution waveform fp32 [L] on
-    the GPU, else None."""
+    the GPU (also kept for the per-frame index rate), else None."""
     from .dac import load_dac_codec
     x, sr = jio.read_wav(args.input_audio)
     if args.simulate_lr is not None:
@@ -253,7 +319,8 @@ def encode_audio(args, device):
             raise SystemExit(f"{args.input_audio}: shorter than 1 s")
         print(f"prepared {os.path.basename(args.input_audio)}: {x.shape[0]} samples at {sr} Hz -> {res['count']} frames "
               f"(HR and LR through {args.simulate_lr} Hz, DAC {args.dac_precision})")
-        source = simulated_lr_waveform(x, sr, codec, args.simulate_lr, device) if args.lf_replace is not None else None
+        keep = args.lf_replace is not None or rate_flags(args)
+        source = simulated_lr_waveform(x, sr, codec, args.simulate_lr, device) if keep else None
         return codec, res["hr_latent"].cpu(), res["lr_latent"].cpu(), source
     if sr != 44100 and not args.resample:
         raise SystemExit(f"{args.input_audio}: sample rate {sr} Hz; the DAC 44.1 kHz model needs 44100 Hz "
@@ -267,7 +334,8 @@ def encode_audio(args, device):
     z = codec.encode(audio[None])[0]
     print(f"encoded {os.path.basename(args.input_audio)}: {x.shape[0]} samples -> {z.shape[-1]} frames "
           f"(DAC {args.dac_precision})")
-    return codec, None, z[0].cpu(), audio[0].contiguous() if args.lf_replace is not None else None
+    keep = args.lf_replace is not None or rate_flags(args)
+    return codec, None, z[0].cpu(), audio[0].contiguous() if keep else None
 
 
 def simulated_lr_waveform(x, sr, codec, low_sr, device):

@@ -35,6 +35,13 @@ nearer row can be missed.  The bank file gets format 3; a multi-scale IVF is out
     python -m jatsr_amd.retrieval build --data-dir data_processed --out bank_ivf.pt --max-frames 1000000 --ivf [--ivf-lists N] [--ivf-nprobe P]
     python -m jatsr_amd.infer ... --index-bank bank_ivf.pt --index-rate 0.4 [--index-nprobe 8]
 
+Voicing-aware index rates (`f0_classes`, `rate_track`, `mix_rates`): the index rate as a per-frame track derived
+from a pitch track, in the place of one scalar.  Unvoiced frames get `index_rate * protect` (RVC's `protect`: consonants and
+breaths keep more of the prediction), voiced frames whose F0 is not steady `index_rate * unstable`, steady ones `index_rate`.
+Every `retrieve` takes such a track as `index_rate`.
+
+    python -m jatsr_amd.infer ... --index-bank bank.pt --index-rate 0.4 --index-protect 0.33 [--index-unstable 0.7] [--index-smooth 2]
+
 Whether retrieval improves audio quality is not established here: nothing in this repository was run with trained weights.
 """
 from __future__ import annotations
@@ -459,7 +466,11 @@ class LatentBank:
         frame is de-normalised in the blend.  stats: must be the statistics the bank was built with (default: those).
         k > 1: the inverse-square-distance weighted mean of the k nearest frames (`search_topk`, `blend_topk`) takes the
         place of the single nearest one; k = 1 makes exactly the calls it always made.  neighbours: return (y, idx, dist2)
-        with the lists the blend used."""
+        with the lists the blend used.  index_rate may be a per-frame track, an fp32 tensor [B, T] (or [T] for B = 1) on the
+        bank's device with values in [0, 1] (`rate_track`): this call at rate 1.0, then `mix_rates`."""
+        if is_rate_track(index_rate):
+            return _retrieve_with_track(self, x, index_rate, neighbours=neighbours, stats=stats, query=query, k=k,
+                                        dist2_floor=dist2_floor)
         check_index_rate(index_rate)
         k = check_index_k(k)
         check_dist2_floor(dist2_floor)
@@ -764,7 +775,11 @@ class MultiScaleBank:
         query (x under the HR statistics, or the LR latent `query` under the LR statistics for key == "lr") to the scales
         above 1; each scale's bank is searched (`search`, or `search_topk` for k > 1, the same k at every scale) and its
         de-normalised HR rows are written over that scale's pooled buffer by `blend` / `blend_topk` at rate 1; one `mix_scales`
-        launch interpolates and mixes.  Nothing waits for the device.  neighbours: (y, [idx per scale], [dist2 per scale])."""
+        launch interpolates and mixes.  Nothing waits for the device.  neighbours: (y, [idx per scale], [dist2 per scale]).
+        index_rate may be a per-frame track as in `LatentBank.retrieve` (its range check waits for the device)."""
+        if is_rate_track(index_rate):
+            return _retrieve_with_track(self, x, index_rate, neighbours=neighbours, stats=stats, query=query, k=k,
+                                        dist2_floor=dist2_floor)
         r = check_index_rate(index_rate)
         k = check_index_k(k)
         check_dist2_floor(dist2_floor)
@@ -1136,7 +1151,11 @@ class IVFBank:
         return idx[..., 0], dist2[..., 0]
 
     def retrieve(self, x, index_rate, stats=None, query=None, k=1, dist2_floor=1e-6, neighbours=False):
-        """`LatentBank.retrieve` with the IVF search in the place of the exact one; the blends are the bank's own."""
+        """`LatentBank.retrieve` with the IVF search in the place of the exact one; the blends are the bank's own.  index_rate
+        may be a per-frame track as there."""
+        if is_rate_track(index_rate):
+            return _retrieve_with_track(self, x, index_rate, neighbours=neighbours, stats=stats, query=query, k=k,
+                                        dist2_floor=dist2_floor)
         check_index_rate(index_rate)
         k = check_index_k(k)
         check_dist2_floor(dist2_floor)
@@ -1181,6 +1200,189 @@ class IVFBank:
     @classmethod
     def load(cls, path, device="cuda"):
         return cls.from_state(torch.load(path, map_location="cpu", weights_only=False), device=device)
+
+
+# ---- voicing-aware index rates (C ABI: include/jat_hip_rate.h) ------------------------------------------------------
+def check_half_window(half_window):
+    """The half window of the stability count as an int in 0..32 (JAT_RATE_MAX_HALF_WINDOW); ValueError otherwise."""
+    if isinstance(half_window, bool) or not isinstance(half_window, int) or not 0 <= half_window <= L.RATE_MAX_HALF_WINDOW:
+        raise ValueError(f"half_window {half_window!r} outside 0..{L.RATE_MAX_HALF_WINDOW}")
+    return half_window
+
+
+def check_smooth(smooth):
+    """The half width of the rate smoothing as an int in 0..16 (JAT_RATE_MAX_SMOOTH); ValueError otherwise."""
+    if isinstance(smooth, bool) or not isinstance(smooth, int) or not 0 <= smooth <= L.RATE_MAX_SMOOTH:
+        raise ValueError(f"smooth {smooth!r} outside 0..{L.RATE_MAX_SMOOTH}")
+    return smooth
+
+
+def smooth_arg(text):
+    """argparse type of --index-smooth."""
+    try:
+        return check_smooth(int(text))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"smooth {text!r} outside 0..{L.RATE_MAX_SMOOTH}")
+
+
+def check_rate_factor(name, value):
+    """A factor on the index rate (protect, unstable) as a float in [0, 1]; ValueError otherwise (a NaN is outside)."""
+    v = float(value)
+    if not 0.0 <= v <= 1.0:
+        raise ValueError(f"{name} {value!r} outside [0, 1]")
+    return v
+
+
+def protect_arg(text):
+    """argparse type of --index-protect."""
+    try:
+        return check_rate_factor("protect", text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
+def unstable_arg(text):
+    """argparse type of --index-unstable."""
+    try:
+        return check_rate_factor("unstable", text)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e))
+
+
+def cents_ratio(cents):
+    """float32(2 ** (cents / 1200)): the frequency ratio `jat_f0_classes` compares with.  It must come out finite and above 1
+    in fp32 (so cents is positive and at least about 1e-4); ValueError otherwise."""
+    try:
+        r = C.c_float(2.0 ** (float(cents) / 1200.0)).value
+    except OverflowError:
+        r = float("inf")
+    if not 1.0 < r < float("inf"):
+        raise ValueError(f"cents {cents!r}: the ratio {r!r} must be finite and above 1 in fp32")
+    return r
+
+
+def default_min_count(half_window):
+    """2 W + 1 - W // 2 agreeing frames of the 2 W + 1 in the window: 7 of 9 at the default W = 4."""
+    w = check_half_window(half_window)
+    return 2 * w + 1 - w // 2
+
+
+def rate_table(index_rate, protect=1.0, unstable=1.0):
+    """The three rates of the classes {not live, unstable, stable}: float32(R protect), float32(R unstable), float32(R), the
+    products taken in double (returned as Python floats holding those fp32 values)."""
+    r = check_index_rate(index_rate)
+    p, u = check_rate_factor("protect", protect), check_rate_factor("unstable", unstable)
+    return (C.c_float(r * p).value, C.c_float(r * u).value, C.c_float(r).value)
+
+
+def f0_classes(f0, voiced, half_window=4, cents=50.0, min_count=None, counts=False):
+    """The F0-stability class of every frame of a pitch track (`jat_f0_classes`): f0 fp32 and voiced bool / uint8, [F] or
+    [B, F], as `pitch.yin` / `pitch.pyin` return them -> (cls uint8, summary int32 [2] or [B, 2] = {live frames, stable
+    frames}), on the device.  A frame is live when its flag is set and its f0 is positive and finite; a live frame is stable
+    (2) when at least `min_count` (default `default_min_count`: 7 of 9) frames of the `half_window` frames on either side of it,
+    itself included, are live and within `cents` of it, unstable (1) otherwise; 0: not live.  counts: also the counts int32."""
+    if not (isinstance(f0, torch.Tensor) and isinstance(voiced, torch.Tensor)) or not (f0.is_cuda and voiced.is_cuda):
+        raise ValueError("f0_classes: f0 and voiced must be CUDA tensors (there is no CPU path)")
+    if f0.dtype != torch.float32 or voiced.dtype not in (torch.bool, torch.uint8) or f0.shape != voiced.shape or \
+            f0.dim() not in (1, 2) or f0.numel() < 1 or f0.device != voiced.device:
+        raise ValueError("f0_classes: f0 float32 and voiced bool / uint8 of one shape [F] or [B, F] on one device, not empty")
+    w = check_half_window(half_window)
+    ratio = cents_ratio(cents)
+    m = default_min_count(w) if min_count is None else min_count
+    if isinstance(m, bool) or not isinstance(m, int) or not 1 <= m <= 2 * w + 1:
+        raise ValueError(f"min_count {min_count!r} outside 1..{2 * w + 1}")
+    batched = f0.dim() == 2
+    f = f0.detach().reshape(-1, f0.shape[-1]).contiguous()
+    v = voiced.detach().reshape(f.shape).contiguous()
+    v = v.view(torch.uint8) if v.dtype == torch.bool else v
+    B, F = f.shape
+    with torch.cuda.device(f.device):
+        cls = torch.empty(B, F, dtype=torch.uint8, device=f.device)
+        cnt = torch.empty(B, F, dtype=torch.int32, device=f.device) if counts else None
+        summary = torch.empty(B, 2, dtype=torch.int32, device=f.device)
+        L.check(L.lib().jat_f0_classes(L.ptr(f), L.ptr(v), B, F, w, ratio, m, L.ptr(cls), L.ptr(cnt), L.ptr(summary),
+                                       L.stream_ptr()))
+    out = (cls, summary, cnt) if counts else (cls, summary)
+    return out if batched else tuple(t[0] for t in out)
+
+
+def rate_track(cls, frames, index_rate, protect=1.0, unstable=1.0, smooth=2):
+    """Classes to a per-frame index rate (`jat_rate_track`): cls uint8 [F] or [B, F] on the device -> rates fp32 [frames] or
+    [B, frames].  A stable frame gets `index_rate`, an unstable one `index_rate * unstable`, a frame that is not live (or
+    behind the end of the pitch track) `index_rate * protect`; the track is then averaged over `smooth` frames on either side
+    (0: not at all) in a form that leaves a frame farther than `smooth` from any change of class at its table value exactly.
+    protect = 1 and unstable = 1 change nothing.  `protect` is the plain factor on the rate of unvoiced frames: RVC's slider of
+    that name means "off" at 0.5 and defaults to 0.33; here 1 is off and RVC's default corresponds to 0.33."""
+    if not isinstance(cls, torch.Tensor) or not cls.is_cuda or cls.dtype != torch.uint8 or cls.dim() not in (1, 2) or \
+            cls.numel() < 1:
+        raise ValueError("rate_track: cls must be a CUDA uint8 tensor [F] or [B, F], not empty")
+    if isinstance(frames, bool) or not isinstance(frames, int) or frames < 1:
+        raise ValueError(f"rate_track: frames {frames!r} must be a positive integer")
+    table = rate_table(index_rate, protect, unstable)
+    s = check_smooth(smooth)
+    c = cls.detach().reshape(-1, cls.shape[-1]).contiguous()
+    B, F = c.shape
+    with torch.cuda.device(c.device):
+        r = torch.empty(B, frames, dtype=torch.float32, device=c.device)
+        L.check(L.lib().jat_rate_track(L.ptr(c), B, F, frames, (C.c_float * 3)(*table), s, L.ptr(r), L.stream_ptr()))
+    return r if cls.dim() == 2 else r[0]
+
+
+def check_rates(rates, B, T, device):
+    """A per-frame index-rate track for x [B, C, T]: an fp32 tensor [B, T] (or [T] for B = 1) on `device` with every value in
+    [0, 1] (checked on the host: this waits for the device) -> the contiguous [B, T] tensor; ValueError otherwise."""
+    if not isinstance(rates, torch.Tensor):
+        raise ValueError(f"index rates: expected a tensor, got {type(rates).__name__}")
+    device = torch.device(device)
+    if rates.device != device:
+        raise ValueError(f"index rates: on {rates.device}, expected {device}")
+    if rates.dtype != torch.float32:
+        raise ValueError(f"index rates: dtype {rates.dtype}, expected float32")
+    if tuple(rates.shape) != (B, T) and not (B == 1 and tuple(rates.shape) == (T,)):
+        raise ValueError(f"index rates: shape {tuple(rates.shape)}, expected [{B}, {T}]" + (f" or [{T}]" if B == 1 else ""))
+    r = rates.detach().reshape(B, T).contiguous()
+    if not bool(((r >= 0.0) & (r <= 1.0)).all()):
+        raise ValueError("index rates: a value outside [0, 1] (or a NaN)")
+    return r
+
+
+def _mix_rates(x, v, rates, out):
+    B, Cc, T = x.shape
+    with torch.cuda.device(x.device):
+        L.check(L.lib().jat_rate_mix(L.ptr(x), L.ptr(v), L.ptr(rates), L.ptr(out), B, Cc, T, L.stream_ptr()))
+    return out
+
+
+def mix_rates(x, v, rates, out=None):
+    """(1 - r) x + r v with r = rates[b, t], one rate per frame (`jat_rate_mix`): x and v fp32 [B, C, T], rates fp32 [B, T] (or
+    [T] for B = 1) in [0, 1].  A constant track gives the bits of `blend` / `blend_topk` / `mix_scales` at that rate when v is
+    what they return at rate 1.  out: where to write; may be x or v."""
+    x, v = _frames(x), _frames(v, "v")
+    if v.shape != x.shape or v.device != x.device:
+        raise ValueError(f"v {tuple(v.shape)} on {v.device} does not match x {tuple(x.shape)} on {x.device}")
+    rates = check_rates(rates, x.shape[0], x.shape[2], x.device)
+    if out is None:
+        out = torch.empty_like(x)
+    elif out.shape != x.shape or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
+        raise ValueError("mix_rates(out=...): out must be a contiguous fp32 tensor of x's shape")
+    return _mix_rates(x, v, rates, out)
+
+
+def is_rate_track(index_rate):
+    """Whether `retrieve` was given a per-frame track (a tensor with at least one dimension) and not a scalar rate."""
+    return isinstance(index_rate, torch.Tensor) and index_rate.dim() > 0
+
+
+def _retrieve_with_track(bank, x, rates, neighbours=False, **kw):
+    """`bank.retrieve` with a per-frame rate: the bank's own call at rate 1.0 returns the retrieved track, `jat_rate_mix` blends
+    it in (over the track's buffer).  neighbours: the lists of that call, unchanged."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 3:
+        raise ValueError("x: expected a CUDA fp32 [B, C, T] tensor")
+    rates = check_rates(rates, int(x.shape[0]), int(x.shape[2]), bank.device)
+    out = bank.retrieve(x, 1.0, neighbours=neighbours, **kw)
+    v = out[0] if neighbours else out
+    y = _mix_rates(x.contiguous(), v, rates, v)
+    return (y,) + tuple(out[1:]) if neighbours else y
 
 
 def load_bank(path, device="cuda"):

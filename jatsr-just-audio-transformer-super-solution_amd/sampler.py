@@ -222,7 +222,7 @@ def chunk_groups(lens, pad_short_chunks=True):
 @torch.no_grad()
 def sample_long(model, lr_latent, hr_mean, hr_std, lr_mean, lr_std, num_steps=50, cfg_scale=1.0,
                 chunk_frames=1378, overlap_frames=172, noise=None, pad_short_chunks=True, solver="euler", timesteps=None,
-                bank=None, index_rate=0.0, index_k=1):
+                bank=None, index_rate=0.0, index_k=1, index_rates=None):
     """Chunked long-sequence inference == the chunk loop of infer_test_v3m2.py:340-404, with the chunks of a file
     BATCHED into one sampler launch instead of the reference's serial B=1 loop (pad_short_chunks=False: one launch
     per distinct chunk length, the round-1 behaviour).
@@ -235,6 +235,9 @@ def sample_long(model, lr_latent, hr_mean, hr_std, lr_mean, lr_std, num_steps=50
     statistics when the bank is keyed by LR frames) and index_rate of the retrieved HR frame is mixed in.  Without a bank, or
     at index_rate 0, nothing more is launched.  index_k in 1..8: that many nearest frames, mixed with inverse-square-distance
     weights, stand in for the single nearest one (index_k = 1: `search` and `blend`, unchanged).
+    index_rates: a per-frame rate track, an fp32 tensor [T_total] (or [1, T_total]) on the bank's device with values in [0, 1]
+    (`jatsr_amd.retrieval.rate_track`); it takes the place of index_rate in that one retrieval call and needs a bank.
+    None: the calls made without it.
     """
     index_rate = float(index_rate)
     if not 0.0 <= index_rate <= 1.0:
@@ -242,6 +245,12 @@ def sample_long(model, lr_latent, hr_mean, hr_std, lr_mean, lr_std, num_steps=50
     from .retrieval import check_index_k
     index_k = check_index_k(index_k)
     Cc, total = lr_latent.shape
+    if index_rates is not None:
+        if bank is None:
+            raise ValueError("index_rates needs a bank")
+        if not isinstance(index_rates, torch.Tensor) or tuple(index_rates.shape) not in ((total,), (1, total)):
+            raise ValueError(f"index_rates: expected a tensor of the output's {total} frames, got "
+                             f"{tuple(index_rates.shape) if isinstance(index_rates, torch.Tensor) else type(index_rates).__name__}")
     plan = chunk_plan(total, chunk_frames, overlap_frames)
     lr = lr_latent.unsqueeze(0)
     lens = [b - a for a, b in plan]
@@ -277,7 +286,8 @@ def sample_long(model, lr_latent, hr_mean, hr_std, lr_mean, lr_std, num_steps=50
         for j, i in enumerate(idxs):
             outs[i] = gen[j:j + 1, :, :lens[i]].contiguous()
     out = crossfade_chunks(outs, overlap_frames)
-    if bank is None or index_rate == 0.0:
+    if bank is None or (index_rate == 0.0 and index_rates is None):
         return out
     stats = {"hr_mean": hr_mean, "hr_std": hr_std, "lr_mean": lr_mean, "lr_std": lr_std}
-    return bank.retrieve(out, index_rate, stats=stats, query=lr.float() if bank.key == "lr" else None, k=index_k)
+    return bank.retrieve(out, index_rate if index_rates is None else index_rates, stats=stats,
+                         query=lr.float() if bank.key == "lr" else None, k=index_k)
