@@ -28,6 +28,7 @@ _LAZY = {
     "LatentBank": "retrieval", "frame_plan": "retrieval", "MultiScaleBank": "retrieval", "load_bank": "retrieval",
     "kmeans": "retrieval", "IVFBank": "retrieval",
     "harmonic_metrics": "harmonic", "generate_harmonics": "harmonic",
+    "LowpassBank": "lowpass", "design_sos": "lowpass", "random_filter": "lowpass", "simulate_lr_filtered": "lowpass",
     "find_latest_checkpoint_dir": "fit", "resolve_run_dir": "fit",
 }
 __all__ = ["recipe"] + sorted(_LAZY)

@@ -234,6 +234,16 @@ RATE_SIGNATURES = {
     "jat_rate_track": (C.c_int, [_VP, _I32, _I32, _I32, C.POINTER(_F32), _I32, _VP, _VP]),
     "jat_rate_mix": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I32, _I32, _VP]),
 }
+# name -> (restype, argtypes); every symbol include/jat_hip_iir.h declares (IIR low-pass cascades: sosfilt, sosfiltfilt)
+IIR_SIGNATURES = {
+    "jat_iir_create": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _I32, _VP, C.POINTER(_VP)]),
+    "jat_iir_destroy": (None, [_VP]),
+    "jat_iir_geometry": (C.c_int, [C.POINTER(_I32), C.POINTER(_I32)]),
+    "jat_iir_padlen": (C.c_int, [_VP, C.POINTER(_I32)]),
+    "jat_iir_workspace_bytes": (C.c_int, [_I32, _I64, C.POINTER(_SZ)]),
+    "jat_iir_sosfilt": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I64, _VP, _SZ, _VP]),
+    "jat_iir_sosfiltfilt": (C.c_int, [_VP, _VP, _VP, _VP, _I32, _I64, _VP, _SZ, _VP]),
+}
 RATE_MAX_HALF_WINDOW = 32    # JAT_RATE_MAX_HALF_WINDOW
 RATE_MAX_SMOOTH = 16         # JAT_RATE_MAX_SMOOTH
 IVF_MAX_NPROBE = 8           # JAT_IVF_MAX_NPROBE
@@ -269,7 +279,8 @@ def lib():
         import torch  # noqa: F401
         h = C.CDLL(LIB_PATH)
         for name, (res, args) in list(SIGNATURES.items()) + list(MS_SIGNATURES.items()) + list(HARM_SIGNATURES.items()) + \
-                list(KM_SIGNATURES.items()) + list(IVF_SIGNATURES.items()) + list(RATE_SIGNATURES.items()):
+                list(KM_SIGNATURES.items()) + list(IVF_SIGNATURES.items()) + list(RATE_SIGNATURES.items()) + \
+                list(IIR_SIGNATURES.items()):
             if not hasattr(h, name) and os.environ.get("JAT_LIB_ALLOW_MISSING"):
                 continue      # A/B against an OLDER build through JAT_LIB_PATH (tools/sampler_ab.py): it lacks the newest entry points
             fn = getattr(h, name)

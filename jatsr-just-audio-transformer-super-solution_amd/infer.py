@@ -86,6 +86,13 @@ def build_parser():
     p.add_argument("--simulate-lr", type=int, nargs="?", const=16000, default=None, metavar="LOW_SR",
                    help="with --input-audio: the WAV is the HR recording; its LR latent (through LOW_SR, default 16000) "
                         "is the sampler's input, made as the training data is (implies --resample)")
+    p.add_argument("--lr-filter", choices=("butter", "cheby1"), default=None,
+                   help="with --simulate-lr: make the LR input with one zero-phase IIR low-pass at 48 kHz (jatsr_amd.lowpass) in "
+                        "place of the resampling round trip; needs --lr-cutoff-hz")
+    p.add_argument("--lr-cutoff-hz", type=float, default=None, metavar="HZ", help="with --lr-filter: the cutoff, 1000..23520 Hz")
+    p.add_argument("--lr-order", type=int, default=None, metavar="N", help="with --lr-filter: the order, 1..10 (default 8)")
+    p.add_argument("--lr-ripple-db", type=float, default=None, metavar="D",
+                   help="with --lr-filter cheby1: the passband ripple in dB, (0, 3] (default 1)")
     p.add_argument("--metrics", action="store_true",
                    help="LSD and mel losses of the decoded generated and LR audio against the HR ground truth, written as "
                         "{stem}_metrics.json (needs --dac-weights and a ground truth: --simulate-lr or a latent file with hr_latent)")
@@ -142,7 +149,32 @@ def rate_flags(args):
     return any(getattr(args, name, None) is not None for name in RATE_FLAGS)
 
 
+def lr_filter_of(args):
+    """--lr-filter and its companions -> {"kind", "order", "cutoff_hz", "ripple_db"}, or None when none of them was given"""
+    kind, cutoff = getattr(args, "lr_filter", None), getattr(args, "lr_cutoff_hz", None)
+    order, ripple = getattr(args, "lr_order", None), getattr(args, "lr_ripple_db", None)
+    if kind is None:
+        if cutoff is not None or order is not None or ripple is not None:
+            raise SystemExit("--lr-cutoff-hz, --lr-order and --lr-ripple-db need --lr-filter")
+        return None
+    if getattr(args, "simulate_lr", None) is None:
+        raise SystemExit("--lr-filter needs --simulate-lr (it replaces the resampling round trip of the simulated LR input)")
+    if cutoff is None:
+        raise SystemExit("--lr-filter needs --lr-cutoff-hz")
+    if ripple is not None and kind != "cheby1":
+        raise SystemExit("--lr-ripple-db needs --lr-filter cheby1")
+    from .lowpass import JatError, check_filter
+    from .prepare import HIGH_SR
+    filt = {"kind": kind, "order": 8 if order is None else order, "cutoff_hz": cutoff, "ripple_db": 1.0 if ripple is None else ripple}
+    try:
+        check_filter(kind, filt["order"], cutoff, HIGH_SR, filt["ripple_db"])
+    except JatError as e:
+        raise SystemExit(f"--lr-filter: {e}")
+    return filt
+
+
 def run(args):
+    lr_filter_of(args)
     if args.lf_replace is not None:
         if not args.dac_weights:
             raise SystemExit("--lf-replace needs --dac-weights")
@@ -314,13 +346,16 @@ def encode_audio(args, device):
     if args.simulate_lr is not None:
         from .prepare import prepare_audio
         codec = load_dac_codec(args.dac_weights, device=device, precision=args.dac_precision)
-        res = prepare_audio(x, sr, codec, low_sr=args.simulate_lr, device=device)
+        filt = lr_filter_of(args)
+        res = prepare_audio(x, sr, codec, low_sr=args.simulate_lr, device=device, **({"lr_filter": filt} if filt else {}))
         if res is None:
             raise SystemExit(f"{args.input_audio}: shorter than 1 s")
         print(f"prepared {os.path.basename(args.input_audio)}: {x.shape[0]} samples at {sr} Hz -> {res['count']} frames "
-              f"(HR and LR through {args.simulate_lr} Hz, DAC {args.dac_precision})")
+              f"(HR and LR through " + (f"{args.simulate_lr} Hz" if not filt else
+                                         f"{filt['kind']} order {filt['order']} at {filt['cutoff_hz']:g} Hz") +
+              f", DAC {args.dac_precision})")
         keep = args.lf_replace is not None or rate_flags(args)
-        source = simulated_lr_waveform(x, sr, codec, args.simulate_lr, device) if keep else None
+        source = simulated_lr_waveform(x, sr, codec, args.simulate_lr, device, **({"lr_filter": filt} if filt else {})) if keep else None
         return codec, res["hr_latent"].cpu(), res["lr_latent"].cpu(), source
     if sr != 44100 and not args.resample:
         raise SystemExit(f"{args.input_audio}: sample rate {sr} Hz; the DAC 44.1 kHz model needs 44100 Hz "
@@ -338,7 +373,7 @@ def encode_audio(args, device):
     return codec, None, z[0].cpu(), audio[0].contiguous() if keep else None
 
 
-def simulated_lr_waveform(x, sr, codec, low_sr, device):
+def simulated_lr_waveform(x, sr, codec, low_sr, device, lr_filter=None):
     """The whole recording through the resample calls prepare_audio runs on its chunks (peak rule, -> 48 kHz ->
     simulate_lr -> codec rate): the low-resolution waveform at 44.1 kHz, fp32 [L] on the GPU."""
     from .prepare import HIGH_SR, to_codec_rate
@@ -350,6 +385,9 @@ def simulated_lr_waveform(x, sr, codec, low_sr, device):
     if peak > 1.0:
         w = w / peak
     hr48 = resample(w[None], sr, HIGH_SR) if sr != HIGH_SR else w[None]
+    if lr_filter is not None:
+        from .lowpass import simulate_lr_filtered
+        return to_codec_rate(simulate_lr_filtered(hr48, HIGH_SR, lr_filter), codec)[0].contiguous()
     return to_codec_rate(simulate_lr(hr48, HIGH_SR, low_sr), codec)[0].contiguous()
 
 

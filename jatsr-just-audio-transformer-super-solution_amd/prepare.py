@@ -137,12 +137,15 @@ def hr_harmonic_table(signal, codec, hr_f0, hr_voiced, n_harmonics: int, method:
 
 
 def prepare_audio(audio, sr: int, codec, low_sr: int = 16000, batch: int = 8, device="cuda", timings: dict | None = None,
-                  f0: bool = False, f0_method: str = "yin", harmonics: int = 0):
+                  f0: bool = False, f0_method: str = "yin", harmonics: int = 0, lr_filter: dict | None = None):
     """One recording -> dict(hr_latent fp32 [1024, T], lr_latent, sum fp64 [2048], sq_sum, count, metadata), tensors on the
     GPU; None for a recording shorter than 1 s.  `audio`: [L] or [channels, L], array or tensor; `codec`: a DacCodec with an
     encoder.  sum / sq_sum: HR channels first, then LR, over the values rounded to fp16; count: T (frames of each).
     With `f0` also hr_f0 fp32 [T] and hr_voiced uint8 [T] (hr_pitch_track), and with f0_method "pyin" hr_voiced_prob fp32 [T];
-    with `f0` and `harmonics` = H > 0 also hr_harmonics fp16 [T, H] (hr_harmonic_table)."""
+    with `f0` and `harmonics` = H > 0 also hr_harmonics fp16 [T, H] (hr_harmonic_table).
+    `lr_filter` = {"kind": "butter" | "cheby1", "order", "cutoff_hz"[, "ripple_db"]}: the LR half is made with that zero-phase
+    IIR low-pass at 48 kHz (jatsr_amd.lowpass) in the place of the round trip through `low_sr`, and the result holds `lr_filter`;
+    None or {"kind": "sinc"}: the round trip."""
     import torch
 
     from . import _lib as L
@@ -155,6 +158,12 @@ def prepare_audio(audio, sr: int, codec, low_sr: int = 16000, batch: int = 8, de
     if harmonics and not f0:
         raise ValueError("prepare_audio: harmonics needs f0 (the table is taken at the stored track)")
     sr, low_sr = int(sr), int(low_sr)
+    iir = lr_filter if lr_filter is not None and lr_filter.get("kind") != "sinc" else None
+    if iir is not None:
+        from .lowpass import check_filter, simulate_lr_filtered
+        iir = {"kind": iir["kind"], "order": int(iir["order"]), "cutoff_hz": float(iir["cutoff_hz"]),
+               "ripple_db": float(iir.get("ripple_db", 1.0))}
+        check_filter(iir["kind"], iir["order"], iir["cutoff_hz"], HIGH_SR, iir["ripple_db"])
     x = torch.as_tensor(audio)
     if not x.is_cuda:
         x = x.to(device)
@@ -185,7 +194,7 @@ def prepare_audio(audio, sr: int, codec, low_sr: int = 16000, batch: int = 8, de
 
         def both(raw=raw):
             hr = resample(raw, sr, HIGH_SR) if sr != HIGH_SR else raw                    # :197-200
-            lr = simulate_lr(hr, HIGH_SR, low_sr)                                         # :203-205
+            lr = simulate_lr(hr, HIGH_SR, low_sr) if iir is None else simulate_lr_filtered(hr, HIGH_SR, iir)   # :203-205
             return hr, to_codec_rate(hr, codec), to_codec_rate(lr, codec)
         hr48, hr44, lr44 = clock.run("resample", both)
         z_hr, z_lr = clock.run("encode", lambda: (codec.encode(hr44[:, None])[0], codec.encode(lr44[:, None])[0]))
@@ -209,6 +218,8 @@ def prepare_audio(audio, sr: int, codec, low_sr: int = 16000, batch: int = 8, de
     out = {"hr_latent": hr, "lr_latent": lr, "sum": s, "sq_sum": q, "count": hr.shape[-1],
            "metadata": {"duration": duration, "sr": sr, "chunks": len(chunks), "frames": hr.shape[-1],
                         "hop_48k": hop48, "trim_frames": trim, "valid_frames": valid}}
+    if lr_filter is not None:
+        out["lr_filter"] = iir if iir is not None else {"kind": "sinc", "low_sr": low_sr}
     sig_kw = {"signal": hr_codec_signal(x, sr, codec)} if f0 and harmonics else {}     # resampled once for the track and the table
     if f0 and f0_method == "yin":
         out["hr_f0"], out["hr_voiced"] = clock.run("f0", lambda: hr_pitch_track(x, sr, codec, hr.shape[-1], **sig_kw))
@@ -250,8 +261,49 @@ def build_parser():
                    help="with --f0: the tracker; pyin also stores hr_voiced_prob fp32 [T]")
     p.add_argument("--harmonics", type=int, default=0, metavar="H",
                    help="with --f0: also store hr_harmonics fp16 [T, H], the amplitudes of the track's first H harmonics (1..128)")
+    p.add_argument("--lr-filter", choices=("sinc", "butter", "cheby1", "mix"), default="sinc",
+                   help="how the LR half is made: sinc (the round trip through --low-sr), or one zero-phase IIR low-pass per "
+                        "recording at 48 kHz, drawn from (--lr-seed, the file's stem); mix draws among the three kinds")
+    p.add_argument("--lr-cutoff-hz", type=str, default=None, metavar="LO,HI",
+                   help="with --lr-filter butter / cheby1 / mix: the cutoff is drawn log-uniformly from LO..HI Hz (default 4000,12000)")
+    p.add_argument("--lr-order", type=str, default=None, metavar="LO,HI",
+                   help="with --lr-filter butter / cheby1 / mix: the order is drawn uniformly from LO..HI, within 1..10 (default 4,10)")
+    p.add_argument("--lr-ripple-db", type=float, default=None, metavar="D",
+                   help="with --lr-filter cheby1 / mix: the Chebyshev passband ripple in dB, (0, 3] (default 1)")
+    p.add_argument("--lr-seed", type=int, default=None, help="with --lr-filter butter / cheby1 / mix: seed of the draw (default --seed)")
     p.add_argument("--device", default="cuda", help="an AMD GPU; there is no CPU path")
     return p
+
+
+LR_KINDS = {"butter": ("butter",), "cheby1": ("cheby1",), "mix": ("sinc", "butter", "cheby1")}
+
+
+def lr_filter_plan(args):
+    """--lr-filter and its companions -> None (sinc: today's path) or the keyword arguments of lowpass.random_filter; refuses
+    the combinations that mean nothing"""
+    kind = getattr(args, "lr_filter", "sinc") or "sinc"
+    given = {k: getattr(args, "lr_" + k, None) for k in ("cutoff_hz", "order", "ripple_db", "seed")}
+    if kind == "sinc":
+        extra = [k for k, v in given.items() if v is not None]
+        if extra:
+            raise SystemExit("--lr-" + extra[0].replace("_", "-") + " means nothing with --lr-filter sinc")
+        return None
+    if given["ripple_db"] is not None and kind == "butter":
+        raise SystemExit("--lr-ripple-db means nothing with --lr-filter butter")
+    from .lowpass import JatError, check_filter, parse_range
+    cutoff = parse_range(given["cutoff_hz"] or "4000,12000", "--lr-cutoff-hz", float)
+    order = parse_range(given["order"] or "4,10", "--lr-order", int)
+    ripple = 1.0 if given["ripple_db"] is None else given["ripple_db"]
+    if cutoff[0] > cutoff[1] or order[0] > order[1]:
+        raise SystemExit("--lr-cutoff-hz and --lr-order: LO must not exceed HI")
+    try:
+        for c in cutoff:
+            for o in order:
+                check_filter("cheby1", o, c, HIGH_SR, ripple)
+    except JatError as e:
+        raise SystemExit(f"--lr-filter: {e}")
+    return {"seed": args.seed if given["seed"] is None else given["seed"], "kinds": LR_KINDS[kind], "cutoff_hz": cutoff,
+            "order": order, "ripple_db": ripple}
 
 
 def find_wavs(dirs):
@@ -281,7 +333,10 @@ def run(args):
         total_sum = total_sq = None
         total_count = 0
     codec = None
+    lr_plan = lr_filter_plan(args)
     report = {"written": [], "skipped": [], "existing": []}
+    if lr_plan is not None:
+        report["lr_filters"] = {}
     for path, sub in tasks:
         stem = os.path.splitext(os.path.basename(path))[0]
         out_path = os.path.join(args.output_dir, sub, f"{stem}.pt")
@@ -297,7 +352,12 @@ def run(args):
         harmonics = getattr(args, "harmonics", 0)
         if harmonics and not want_f0:
             raise SystemExit("--harmonics needs --f0")
-        res = prepare_audio(x, sr, codec, low_sr=args.low_sr, batch=args.batch, device=args.device, f0=want_f0,
+        lr_kw = {}
+        if lr_plan is not None:
+            from .lowpass import random_filter
+            lr_kw = {"lr_filter": random_filter(lr_plan["seed"], stem, lr_plan["kinds"], lr_plan["cutoff_hz"], lr_plan["order"],
+                                                lr_plan["ripple_db"])}
+        res = prepare_audio(x, sr, codec, low_sr=args.low_sr, batch=args.batch, device=args.device, f0=want_f0, **lr_kw,
                             **({"f0_method": f0_method} if f0_method != "yin" else {}),
                             **({"harmonics": harmonics} if harmonics else {}))
         if res is None:
@@ -306,6 +366,7 @@ def run(args):
             continue
         jio.save_latent_file(out_path, hr_latent=res["hr_latent"], lr_latent=res["lr_latent"],
                              metadata={"name": stem, "path": path, "duration": res["metadata"]["duration"], "sr": sr},
+                             **({"lr_filter": res["lr_filter"]} if "lr_filter" in res else {}),
                              **({k: res[k].cpu() for k in ("hr_f0", "hr_voiced", "hr_voiced_prob", "hr_harmonics") if k in res} if want_f0 else {}))
         s, q = res["sum"].cpu(), res["sq_sum"].cpu()
         total_sum = s if total_sum is None else total_sum + s
@@ -313,12 +374,16 @@ def run(args):
         total_count += res["count"]
         torch.save({"sum": total_sum, "sq_sum": total_sq, "count": total_count}, stats_path)
         report["written"].append(out_path)
-        print(f"{path} -> {out_path}: {res['count']} frames")
+        if "lr_filter" in res:
+            kinds = report["lr_filters"]
+            kinds[res["lr_filter"]["kind"]] = kinds.get(res["lr_filter"]["kind"], 0) + 1
+        print(f"{path} -> {out_path}: {res['count']} frames" + (f", LR through {res['lr_filter']}" if "lr_filter" in res else ""))
     if total_count > 0:
         with open(os.path.join(args.output_dir, "global_stats_separated.json"), "w") as f:
             json.dump(final_stats(total_sum, total_sq, total_count, total_sum.numel() // 2), f, indent=4)
     print(f"prepared {len(report['written'])} file(s), skipped {len(report['skipped'])}, "
-          f"{len(report['existing'])} already present; {total_count} frames in the statistics")
+          f"{len(report['existing'])} already present; {total_count} frames in the statistics" +
+          (f"; LR filters {report['lr_filters']}" if lr_plan is not None else ""))
     return report
 
 
