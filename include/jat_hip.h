@@ -577,6 +577,17 @@ void jat_resampler_destroy(jat_resampler* r);
 int jat_resample_out_length(const jat_resampler* r, int64_t L, int64_t* L_out);
 /* x fp32 [B, L] -> y fp32 [B, L_out], both dense; 1 <= B <= 65535; L = 0 does nothing. */
 int jat_resample(jat_resampler* r, const float* x, float* y, int32_t B, int64_t L, void* stream);
+/* [host, no GPU needed] how jat_resample launches a conversion, from the functions it launches by (resample_geometry,
+ * resample_launch_shape of csrc/resample.hip).  The block shape: K taps per phase; a thread owns ph phases (1 or 4); a block
+ * holds pn phases, so gridDim.y = slices = ceil(n / pn); lanes = ceil(pn / ph) threads per frame group; at most groups_max
+ * frame groups of 8 frames per block (the most whose window of (8 groups - 1) o + K samples fits 12288 floats of LDS).  The
+ * launch for rows of L samples: groups frame groups per block, gridDim.x = grid_x blocks of 8 groups frames along a row,
+ * block = lanes * groups threads, lds_bytes of dynamic LDS; all four are 0 for L = 0, and every field but K is 0 for
+ * orig == new (a copy: no kernel).  Fails exactly where jat_resampler_create (the arguments, a table of more than 2^26
+ * entries, no block shape whose window fits) or jat_resample_out_length (L) does.  Any output pointer may be null. */
+int jat_k_resample_geometry(int32_t orig, int32_t new_, int32_t lowpass_filter_width, double rolloff, int64_t L, int32_t* K,
+                            int32_t* ph, int32_t* pn, int32_t* slices, int32_t* lanes, int32_t* groups_max, int32_t* groups,
+                            int32_t* grid_x, int32_t* block, int32_t* lds_bytes);
 
 /* ---- per-channel latent statistics (prepare_dataset_v5.py:251-253, recalculate_stats.py:60-110) -------------------- */
 /* sum[c] += sum_{b,t} v, sq_sum[c] += sum_{b,t} v^2 with v = z[b, c, t] rounded to fp16 (what the latent files store), in

@@ -156,6 +156,7 @@ SIGNATURES = {
     "jat_resampler_destroy": (None, [_VP]),
     "jat_resample_out_length": (C.c_int, [_VP, _I64, C.POINTER(_I64)]),
     "jat_resample": (C.c_int, [_VP, _VP, _VP, _I32, _I64, _VP]),
+    "jat_k_resample_geometry": (C.c_int, [_I32, _I32, _I32, C.c_double, _I64] + [C.POINTER(_I32)] * 10),
     "jat_channel_stats": (C.c_int, [_VP, _I32, _I32, _I32, _VP, _VP, _VP, _SZ, _VP]),
     "jat_mel_filterbank": (C.c_int, [_I32, _I32, _I32, _VP]),
     "jat_stft_frames": (C.c_int, [_I64, _I32, C.POINTER(_I64)]),

@@ -48,6 +48,24 @@ double tap(int p, int k, int o, int n, int width, int lpw, double base) {
   return s * (c * c) * (base / o);
 }
 
+// the checks of jat_resampler_create that need no GPU: the table's dimensions, then a block shape whose window fits
+int plan_dims(int orig, int new_, int lpw, double rolloff, int* o, int* n, int* width, int* K, ResampleGeom* geom) {
+  JCHK(table_dims(orig, new_, lpw, rolloff, o, n, width, K));
+  if (*o != *n && !resample_geometry(*o, *n, *K, geom))
+    return fail(JAT_E_INVALID, "resample: %d -> %d: a window of %d + 7 x %d samples does not fit one block (limit %d)", orig,
+                new_, *K, *o, RS_MAX_WINDOW);
+  return JAT_OK;
+}
+
+// L_out = ceil(n L / o), refused as include/jat_hip.h says
+int out_length(int orig, int new_, int o, int n, int K, int64_t L, int64_t* L_out) {
+  if (L < 0) return fail(JAT_E_INVALID, "resample: length %lld is negative", (long long)L);
+  if (L + K > kMax31 || L > (kMax31 - o) / n * o)   // the second bound keeps ceil(n L / o) within 31 bits
+    return fail(JAT_E_INVALID, "resample: length %lld (%d -> %d) does not fit 31 bits", (long long)L, orig, new_);
+  *L_out = (L * n + o - 1) / o;
+  return JAT_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -71,11 +89,8 @@ int jat_resampler_create(int32_t orig, int32_t new_, int32_t lpw, double rolloff
   *out = nullptr;
   std::unique_ptr<jat_resampler> r(new jat_resampler);
   r->orig = orig, r->new_ = new_, r->lpw = lpw, r->rolloff = rolloff;
-  JCHK(table_dims(orig, new_, lpw, rolloff, &r->o, &r->n, &r->width, &r->K));
+  JCHK(plan_dims(orig, new_, lpw, rolloff, &r->o, &r->n, &r->width, &r->K, &r->geom));
   if (r->o != r->n) {
-    if (!resample_geometry(r->o, r->n, r->K, &r->geom))
-      return fail(JAT_E_INVALID, "resample: %d -> %d: a window of %d + 7 x %d samples does not fit one block", orig, new_,
-                  r->K, r->o);
     const double base = std::min(r->o, r->n) * rolloff;
     std::vector<float> ht((size_t)r->K * r->n);
     for (int p = 0; p < r->n; ++p)
@@ -101,10 +116,24 @@ void jat_resampler_destroy(jat_resampler* r) {
 
 int jat_resample_out_length(const jat_resampler* r, int64_t L, int64_t* L_out) {
   if (!r || !L_out) return fail(JAT_E_INVALID, "jat_resample_out_length: null argument");
-  if (L < 0) return fail(JAT_E_INVALID, "resample: length %lld is negative", (long long)L);
-  if (L + r->K > kMax31 || L > (kMax31 - r->o) / r->n * r->o)   // the second bound keeps ceil(n L / o) within 31 bits
-    return fail(JAT_E_INVALID, "resample: length %lld (%d -> %d) does not fit 31 bits", (long long)L, r->orig, r->new_);
-  *L_out = (L * r->n + r->o - 1) / r->o;
+  return out_length(r->orig, r->new_, r->o, r->n, r->K, L, L_out);
+}
+
+int jat_k_resample_geometry(int32_t orig, int32_t new_, int32_t lpw, double rolloff, int64_t L, int32_t* K, int32_t* ph,
+                            int32_t* pn, int32_t* slices, int32_t* lanes, int32_t* groups_max, int32_t* groups,
+                            int32_t* grid_x, int32_t* block, int32_t* lds_bytes) {
+  int o, n, width, k;
+  ResampleGeom g;
+  JCHK(plan_dims(orig, new_, lpw, rolloff, &o, &n, &width, &k, &g));
+  int64_t L_out = 0;
+  JCHK(out_length(orig, new_, o, n, k, L, &L_out));
+  ResampleLaunch a;                                   // all zero: orig == new is a copy and L == 0 launches nothing
+  if (o == n) g = ResampleGeom{0, 0, 0, 0, 0};
+  else if (L > 0) a = resample_launch_shape(g, (int)L_out, o, n, k);
+  const int32_t vals[10] = {k, g.ph, g.pn, g.slices, g.lanes, g.groups, a.groups, (int32_t)a.grid_x, a.block, (int32_t)a.lds};
+  int32_t* const outs[10] = {K, ph, pn, slices, lanes, groups_max, groups, grid_x, block, lds_bytes};
+  for (int i = 0; i < 10; ++i)
+    if (outs[i]) *outs[i] = vals[i];
   return JAT_OK;
 }
 

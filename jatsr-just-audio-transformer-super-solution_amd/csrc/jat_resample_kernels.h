@@ -20,6 +20,18 @@ struct ResampleGeom {
 // false when no block shape keeps the staged window within RS_MAX_WINDOW
 bool resample_geometry(int o, int n, int K, ResampleGeom* g);
 
+// One launch over rows of L_out outputs: the frame groups pick_groups gives its n_frames = ceil(L_out / n) frames, and the
+// grid, block and dynamic LDS that follow.  resample_launch launches by it; jat_k_resample_geometry reports it.
+struct ResampleLaunch {
+  int groups = 0;      // frame groups per block of this launch (<= ResampleGeom::groups)
+  int fpb = 0;         // frames per block = groups * RS_FRAMES
+  int n_frames = 0;
+  unsigned grid_x = 0; // blocks along the frames; gridDim = (grid_x, slices, B)
+  int block = 0;       // threads = lanes * groups
+  size_t lds = 0;      // bytes of the staged window: ((fpb - 1) o + K) floats
+};
+ResampleLaunch resample_launch_shape(const ResampleGeom& g, int L_out, int o, int n, int K);
+
 // y[b, f n + p] = sum_k ht[k, p] * x[b, f o + k - width] (x = 0 outside [0, L)); ht is the tap table transposed to [K, n]
 hipError_t resample_launch(const float* x, float* y, const float* ht, int B, int L, int L_out, int o, int n, int width, int K,
                            const ResampleGeom& g, hipStream_t s);

@@ -196,17 +196,25 @@ static int pick_groups(const ResampleGeom& g, int n_frames) {
   return want;
 }
 
+ResampleLaunch resample_launch_shape(const ResampleGeom& g, int L_out, int o, int n, int K) {
+  ResampleLaunch a;
+  a.n_frames = (int)(((int64_t)L_out + n - 1) / n);
+  a.groups = pick_groups(g, a.n_frames);
+  a.fpb = a.groups * RS_FRAMES;
+  a.grid_x = (unsigned)((a.n_frames + a.fpb - 1) / a.fpb);
+  a.block = g.lanes * a.groups;
+  a.lds = ((size_t)(a.fpb - 1) * o + K) * sizeof(float);
+  return a;
+}
+
 hipError_t resample_launch(const float* x, float* y, const float* ht, int B, int L, int L_out, int o, int n, int width, int K,
                            const ResampleGeom& g, hipStream_t s) {
-  const int n_frames = (L_out + n - 1) / n;
-  const int groups = pick_groups(g, n_frames);
-  const int fpb = groups * RS_FRAMES;
-  const dim3 grid((n_frames + fpb - 1) / fpb, g.slices, B), block(g.lanes * groups);
-  const size_t lds = ((size_t)(fpb - 1) * o + K) * sizeof(float);
+  const ResampleLaunch a = resample_launch_shape(g, L_out, o, n, K);
+  const dim3 grid(a.grid_x, g.slices, B), block(a.block);
   if (g.ph == 4)
-    resample_kernel<4><<<grid, block, lds, s>>>(x, y, ht, L, L_out, n_frames, o, n, width, K, g.pn, g.lanes, groups);
+    resample_kernel<4><<<grid, block, a.lds, s>>>(x, y, ht, L, L_out, a.n_frames, o, n, width, K, g.pn, g.lanes, a.groups);
   else
-    resample_kernel<1><<<grid, block, lds, s>>>(x, y, ht, L, L_out, n_frames, o, n, width, K, g.pn, g.lanes, groups);
+    resample_kernel<1><<<grid, block, a.lds, s>>>(x, y, ht, L, L_out, a.n_frames, o, n, width, K, g.pn, g.lanes, a.groups);
   return hipGetLastError();
 }
 
